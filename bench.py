@@ -3,14 +3,19 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts N ranks itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full   (also every extra stage, box state and CPU baseline)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
 
 Headline (`value`): MFCC frames/s on BASELINE.json configs[1] — 100k x 3 s synthetic 16 kHz utterances per GPU,
 sidekit-dialect MFCC + delta + delta-delta = 39-d, inputs resident in HBM, one fused kernel launch per step.
 A "step" = one pass of the fused MFCC kernel over the rank's whole batch.  Weak scaling: every rank owns its own
 100k utterances (utterances shard with no data-path collective); the only collective on the path is the gather of
 per-utterance speaker decisions after GMM scoring (stage "gmm").
-Extra stages reported in the same JSON line (not part of `value`): GMM-UBM scoring on configs[2] and cosine
-scoring on configs[4].
+A plain run sets up, warms up, times the steps and prints the line.  With --full, extra stages are reported in the
+same JSON line (not part of `value`): GMM-UBM scoring on configs[2], cosine scoring on configs[4] and the rest of
+--stages, the box's clocks / power and calibration kernels (`env`, `value_normalised`), the CPU baselines and the
+detail file (--detail).
+--dump-outputs DIR: after the timed steps, a fixed, seeded sample of the features the last step computed (dump_outputs).
 """
 from __future__ import annotations
 
@@ -30,6 +35,21 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s 
 VALU_FP32_PEAK_TF = 157.3     # packed fp32 FMA on the vector ALU: 256 CUs x 4 SIMDs x 16 lanes x 2 (packed) x 2 flop x 2.4 GHz (MI355X_MICROARCH.md)
 MFMA_BF16_PEAK_TF = 2500.0   # dense bf16 MFMA peak (MI355X_MICROARCH.md; never the 2:1-sparsity figure)
 MFMA_F32_PEAK_TF = 157.3     # v_mfma_f32_32x32x2_f32 dense peak (MI355X_MICROARCH.md, Matrix cores)
+FULL_STAGES = "mfcc,ref26,hostfed,inrepo,librosa,gmm,gmm4,cosine,closecalls,em,dnn,dvec,dtw,plp"
+DUMP_BYTES = 48 << 20        # --dump-outputs: at most this many bytes of feature rows + row indices (configs[1]'s output is 4.6 GB)
+DUMP_SEED = 20240607         # ... and the rows are always the same draw: two builds are compared row for row
+
+
+def dump_outputs(torch, feats, out_dir):
+    """DIR/mfcc_features.npy (float32): a fixed, seeded sample of the rows of `feats` (what the timed MFCC pass returned in its last
+    step), in row order; DIR/mfcc_feature_rows.npy (float64): their row indices.  The whole output when it fits DUMP_BYTES."""
+    n, d = feats.shape
+    k = min(n, DUMP_BYTES // (d * 4 + 8))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    sample = feats.index_select(0, torch.from_numpy(rows).to(feats.device)).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "mfcc_features.npy"), sample.astype(np.float32, copy=False))
+    np.save(os.path.join(out_dir, "mfcc_feature_rows.npy"), rows.astype(np.float64))
 
 
 def synth_audio_device(torch, n_utt, n_samp, fs, seed, device, out=None, chunk=2000, n_spk=50):
@@ -490,14 +510,18 @@ def main():
     ap.add_argument("--variant", type=int, default=0, help="0 auto | 1 generic kernel | 2 fused workgroup kernel | 3 fused wave-stream kernel (| 4: the 2048-point one, librosa stage only)")
     ap.add_argument("--ref26-variant", type=int, default=0, help="kernel variant of the 26-d + CMVN stage (as --variant)")
     ap.add_argument("--inrepo-variant", type=int, default=0, help="kernel variant of the in-repo MFCC stage (as --variant)")
-    ap.add_argument("--stages", default="mfcc,ref26,hostfed,inrepo,librosa,gmm,gmm4,cosine,closecalls,em,dnn,dvec,dtw,plp")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the extra stages (--stages), the box state (env) and the CPU "
+                    "baselines, and the detail file (--detail); a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write a fixed, seeded sample of the features the last step "
+                    "computed to DIR/*.npy (float32 / float64, < 64 MB)")
+    ap.add_argument("--stages", default=None, help="extra stages of --full (default: %s); a plain run takes only mfcc" % FULL_STAGES)
     ap.add_argument("--hostfed-utts", type=int, default=25000, help="utterances of the host-fed stage's pinned batch (25000 x 3 s = 4.8 GB in, 1.16 GB out)")
     ap.add_argument("--gmm4-utts", type=int, default=12000, help="utterances per GPU of the configs[3]-shaped sample (full: 150000 per GPU; SURVEY.md 8(d) asks for >= 12000)")
     ap.add_argument("--no-gmm4-full", dest="gmm4_full", action="store_false", help="skip the measured full per-GPU share of configs[3] (150000 utterances, bf16x3 path, ~12 s)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--gmm-precision", type=int, default=0, help="0 exact-fp32 MFMA (parity path) | 1 bf16x3 split MFMA")
     ap.add_argument("--detail", default=os.environ.get("SSP_BENCH_DETAIL", os.path.join(ROOT, "gpurun_out", "bench_detail.json")),
-                    help="where the full result goes (every stage's dict, env windows, close-call tables); the last stdout line is the compact summary")
+                    help="where --full writes the full result (every stage's dict, env windows, close-call tables); the last stdout line is the compact summary")
     ap.add_argument("--full-line", action="store_true", help="print the FULL result as the last stdout line (tools/ab*.sh, stage_ms.sh read stage internals from it); the driver's run never sets this")
     ap.add_argument("--env-sampler", action="store_true", help="(internal) run as the sysfs sampler child")
     ap.add_argument("--no-env", action="store_true", help="no sysfs sampler child, no calibration kernels")
@@ -505,9 +529,15 @@ def main():
     args = ap.parse_args()
     if args.env_sampler:
         return env_sampler_main()
+    if args.stages is None:
+        args.stages = FULL_STAGES
+    elif not args.full and set(args.stages.split(",")) - {"mfcc"}:
+        ap.error("--stages %s: the extra stages run with --full only" % args.stages)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
-    sampler = env_sampler_start() if (int(os.environ.get("RANK", "0")) == 0 and not args.no_env) else None
+    sampler = env_sampler_start() if (int(os.environ.get("RANK", "0")) == 0 and args.full and not args.no_env) else None
 
     import torch
     import torch.distributed as dist
@@ -546,7 +576,7 @@ def main():
         if world > 1:
             dist.barrier()
 
-    stages = set(args.stages.split(","))
+    stages = set(args.stages.split(",")) if args.full else set()
     fs = 16000
     n_samp = int(round(args.seconds * fs))
     n_utt = args.utts
@@ -588,10 +618,12 @@ def main():
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, device)
     wall1 = time.time()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, feats, args.dump_outputs)
     # ---- box state, behind the timed region (not part of `value`): the same launch repeated for --sustain-s seconds under the sampler,
     # then two calibration kernels (what this box sustains on a float4 copy and on packed-FMA chains)
     env = None
-    if rank == 0 and not args.no_env:
+    if rank == 0 and args.full and not args.no_env:
         sustain_ms, ws0 = [], time.time()
         while time.time() - ws0 < args.sustain_s:
             _, ms = plan.run(flat, seg, fseg, out=feats, variant=args.variant, timing=True)
@@ -1417,7 +1449,7 @@ def main():
         del logspec
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_mfcc(20000, n_samp, fs)
         if "mfcc_inrepo" in result:
             result["mfcc_inrepo"]["cpu_baseline_reference_loop"] = cpu_baseline_mfcc_loop(n_samp, fs)
@@ -1445,15 +1477,15 @@ def main():
     elif rank == 0:
         # the key stays in the line: the CPU baseline is a rank-0, one-GPU measurement (its worker processes would compete with the
         # other ranks for the host's cores)
-        result["cpu_baseline"] = {"skipped": "world > 1" if world > 1 else "--no-cpu-baseline"}
+        result["cpu_baseline"] = {"skipped": "world > 1" if world > 1 else ("--no-cpu-baseline" if args.full else "measured with --full")}
     try:  # how the shipped libsspgpu.so came to be (speech_signal_processing_amd/build.py records it)
         result["build"] = {k: v for k, v in json.load(open(os.path.join(ROOT, "speech_signal_processing_amd", "build_info.json"))).items()
                            if k in ("build_mode", "compiled_sources", "lib_bytes")}
     except Exception:
         result["build"] = None
     if rank == 0:
-        # the full result goes to the detail file; stdout carries exactly ONE line, the compact one (compact_line)
-        detail = write_detail(result, args.detail)
+        # with --full the full result goes to the detail file; stdout carries exactly ONE line, the compact one (compact_line)
+        detail = write_detail(result, args.detail) if args.full else None
         sys.stdout.flush()
         if args.full_line:
             print(json.dumps(clean_json(result), allow_nan=False), flush=True)

@@ -133,3 +133,72 @@ def test_tools_read_the_detail_file():
                          capture_output=True, text=True)
     assert out.returncode == 0, out.stderr[-1500:]
     assert "frames/s" in out.stdout
+
+
+def test_plain_run_refuses_extra_stages_and_empty_timing():
+    """the extra stages run under --full only (a plain run must not quietly measure less than was asked), and --steps sets the number of
+    timed steps: zero of them is refused.  Both before the GPU is touched."""
+    import subprocess
+    for args, what in ((["--stages", "mfcc,gmm"], "--full"), (["--steps", "0"], "--steps")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and what in out.stderr, (args, out.stderr[-500:])
+
+
+def test_dump_outputs_is_a_fixed_sample(tmp_path):
+    """--dump-outputs: the same rows of the output for every run with the same shape, float32 features + float64 row indices under
+    64 MB at configs[1]'s shape; the whole output when it is small"""
+    import numpy as np
+    import torch
+    import bench
+    n, d = 100000 * 298, 39
+    feats = torch.arange(n, dtype=torch.float32)[:, None].expand(n, d)
+    for sub in ("a", "b"):
+        bench.dump_outputs(torch, feats, str(tmp_path / sub))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["mfcc_feature_rows.npy", "mfcc_features.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    rows, got = np.load(tmp_path / "a" / files[0]), np.load(tmp_path / "a" / files[1])
+    assert rows.dtype == np.float64 and got.dtype == np.float32 and got.shape == (len(rows), d) and len(rows) > 200000
+    assert np.array_equal(rows, np.load(tmp_path / "b" / files[0])) and np.array_equal(got, np.load(tmp_path / "b" / files[1]))
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < n and rows[-1] > 0.9 * n
+    assert np.array_equal(got[:, 0], rows.astype(np.float32)) and (got == got[:, :1]).all()
+    small = torch.randn(500, d)
+    bench.dump_outputs(torch, small, str(tmp_path / "s"))
+    assert np.array_equal(np.load(tmp_path / "s" / "mfcc_features.npy"), small.numpy())
+    assert np.array_equal(np.load(tmp_path / "s" / "mfcc_feature_rows.npy"), np.arange(500.0))
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_features(tmp_path):
+    """a plain run: the headline only (no extra stage, no detail file, no CPU baseline), `steps` timed steps, and --dump-outputs writes the
+    features of the timed pass — equal to the same MFCC plan run here on the same seeded audio"""
+    import subprocess
+    import numpy as np
+    import torch
+    import bench
+    import speech_signal_processing_amd as pkg
+    from speech_signal_processing_amd import api
+    utts = 200
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--utts", str(utts), "--steps", "3", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = _strict(out.stdout.strip().splitlines()[-1])
+    for k in CONTRACT + ("roofline",):
+        assert k in line, k
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["dtype"] == "f32"
+    assert line["detail"] is None and "skipped" in line["cpu_baseline"]
+    for k in ("gmm", "cosine", "mfcc_ref26_cmvn", "plp", "env", "value_normalised"):
+        assert k not in line, k
+    rows = np.load(tmp_path / "out" / "mfcc_feature_rows.npy").astype(np.int64)
+    got = np.load(tmp_path / "out" / "mfcc_features.npy")
+    dev = torch.device("cuda", 0)
+    audio = bench.synth_audio_device(torch, utts, 48000, 16000, seed=1234, device=dev)
+    ctx = api.Context.for_torch(0)
+    plan = api.MfccPlan(ctx, pkg.preset_sidekit(fs=16000, delta_order=2, cmvn=0))
+    seg = api.Segments.from_lengths(ctx, np.full(utts, 48000, dtype=np.int64))
+    fseg = plan.frame_segments(seg)
+    feats = torch.empty((fseg.total, plan.d_out), dtype=torch.float32, device=dev)
+    plan.run(audio.view(-1), seg, fseg, out=feats)
+    torch.cuda.synchronize()
+    assert np.array_equal(rows, np.arange(fseg.total)) and np.array_equal(got, feats.cpu().numpy())

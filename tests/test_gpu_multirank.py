@@ -23,7 +23,7 @@ def test_bench_two_ranks_hip_scorer():
     env.pop("RANK", None)
     utts = 600
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--utts", str(utts), "--steps", "2", "--warmup", "1",
-           "--stages", "mfcc,gmm", "--no-cpu-baseline"]
+           "--full", "--stages", "mfcc,gmm", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -50,7 +50,7 @@ def test_bench_four_ranks_rehearsal_ragged_gather():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--utts", "300", "--steps", "2", "--warmup", "1",
-           "--stages", "mfcc,gmm", "--no-cpu-baseline"]
+           "--full", "--stages", "mfcc,gmm", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -24,5 +24,7 @@ for p in "${pids[@]}"; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -shared-libsan -o $OUT/libsspgpu_asan.so $OUT/*.o
 RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 echo "built $OUT/libsspgpu_asan.so; running the CPU suite under $RT"
+# (the ThreadSanitizer test builds its own host-only binary: the ASan runtime preloaded here must not reach it, and it never loads the library)
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
-  LD_PRELOAD=$RT SSP_LIB_PATH=$PWD/$OUT/libsspgpu_asan.so python -m pytest tests -x -q -m "not gpu" 2>&1 | tail -15
+  LD_PRELOAD=$RT SSP_LIB_PATH=$PWD/$OUT/libsspgpu_asan.so python -m pytest tests -x -q -m "not gpu" \
+  --deselect tests/test_host.py::test_staging_pool_under_thread_sanitizer 2>&1 | tail -15

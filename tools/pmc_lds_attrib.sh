@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 : > $ROOT/gpurun_out/lds_attrib.txt
 for v in "$@"; do
   if [ "$v" = "-" ]; then unset SSP_LIB_PATH; else export SSP_LIB_PATH=$ROOT/tools/scratch/variants/$v.so; fi
-  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/p_$v -- python3 $ROOT/bench.py --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline --no-env --detail $O/d_$v.json > $O/$v.log 2>&1
+  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/p_$v -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline --no-env --detail $O/d_$v.json > $O/$v.log 2>&1
   python3 - $v $(find $O/p_$v -name "*counter_collection.csv" | head -1) >> $ROOT/gpurun_out/lds_attrib.txt <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(list)

@@ -58,7 +58,7 @@ def store(prefix, names, fname, workload, stage, sha_names):
         return
     doc = {"round": R, "git": git, "kernel_source_sha256": bench.kernel_source_sha256(sha_names), "kernel_source_files": list(sha_names),
            "workload": workload,
-           "command": "tools/pmc_mfma.sh  (rocprofv3 --pmc <group> --output-format csv -- python3 bench.py --steps 2 --warmup 1 --stages %s --no-cpu-baseline --no-env; "
+           "command": "tools/pmc_mfma.sh  (rocprofv3 --pmc <group> --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --stages %s --no-cpu-baseline --no-env; "
                       "one pass per counter group; per-dispatch means over the launches with the kernel's largest grid)" % stage,
            "kernels": {}, "notes": "SQ_VALU_MFMA_BUSY_CYCLES is summed over the 1024 SIMDs, GRBM_GUI_ACTIVE over the 8 XCDs; SQ_ACTIVE_INST_* and "
                                    "SQ_WAVE_CYCLES count in units of 4 cycles."}

@@ -23,7 +23,7 @@ for n in ("bench_line.json", "bench_detail.json"):   # the compact line the driv
 if have("kernel_stats.csv"):
     shutil.copy(os.path.join(S, "kernel_stats.csv"), os.path.join(P, "%s_kernel_stats.csv" % R))
     md = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "stats_md.py"), os.path.join(S, "kernel_stats.csv"),
-                         "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-env   (MI355X, %s, tree %s)" % (R, git)],
+                         "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-env   (MI355X, %s, tree %s)" % (R, git)],
                         capture_output=True, text=True).stdout
     md = "\n".join(l for l in md.splitlines() if "at::native" not in l) + "\n"
     if have("kernel_trace.csv"):   # the same run, per launch: full-size launches of the kernels the rooflines are quoted on
@@ -65,7 +65,7 @@ for st, (kern, key) in DOM.items():
     line = json.load(open(os.path.join(S, "stage_%s_bench_detail.json" % st)))   # the full result of the stage's run
     shutil.copy(os.path.join(S, "stage_%s_bench_detail.json" % st), os.path.join(P, "%s_stage_%s_bench_detail.json" % (R, st)))
     shutil.copy(os.path.join(S, "stage_%s_kernel_stats.csv" % st), os.path.join(P, "%s_stage_%s_kernel_stats.csv" % (R, st)))
-    out = ["# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --stages %s --no-cpu-baseline   (MI355X, %s, tree %s)" % (st, R, git), "",
+    out = ["# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --stages %s --no-cpu-baseline   (MI355X, %s, tree %s)" % (st, R, git), "",
            "Every launch of the stage's dominant kernel(s), in launch order (ms, rocprofv3 kernel trace).  The set-up launch and the warm-up launches come first;",
            "the bench's own figure (hipEvents, same run) is quoted below each listing.", ""]
     for name, d in by.items():
@@ -136,7 +136,7 @@ if a:
     if rd is not None and wr is not None:
         doc = {"kernel": "ssp::mfcc_stream512_kernel<13,2,1,3,6,2,3,0,0> (wave-stream, 3 workgroups per CU)", "round": R, "git": git, "kernel_source_sha256": sha,
                "workload": "configs[1]: 100000 x 3 s @16 kHz, 39-d",
-               "command": "tools/profile_round.sh %s pmc512  (rocprofv3 --pmc <counter group> --output-format csv -- python3 bench.py --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline; one pass per counter group; mean over the kernel's launches of the pass)" % R,
+               "command": "tools/profile_round.sh %s pmc512  (rocprofv3 --pmc <counter group> --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline; one pass per counter group; mean over the kernel's launches of the pass)" % R,
                "raw": {k: v["mean_per_launch"] for k, v in a.items() if k.startswith(("FETCH", "WRITE", "TCC"))},
                "corrections": "gfx950: FETCH_SIZE counts 128-B read requests at 64 B (MI355X_MICROARCH.md, HBM): read bytes = 2 * FETCH_SIZE * 1024 = TCC_EA0_RDREQ * 128 B; WRITE_SIZE * 1024 is exact (= WRREQ * 64 B)",
                "hbm_read_bytes_per_launch": rd, "hbm_write_bytes_per_launch": wr, "hbm_bytes_per_launch": rd + wr,
