@@ -76,20 +76,12 @@ void ctx_unregister(const ssp_ctx* c) {
     std::lock_guard<std::mutex> lk(g_live_mu);
     live_set().erase(c);
 }
-// hipStreamSynchronize on a stream its owner has already destroyed (a borrowed stream at process exit) does not return an error on
-// ROCm 7.2 — it throws std::bad_variant_access out of the C API; nothing may escape a destroy function
-static void sync_quietly(hipStream_t s) {
-    try {
-        (void)hipStreamSynchronize(s);
-    } catch (...) {
-    }
-}
 void quiesce_ctx(const ssp_ctx* ctx) {
     if (!ctx) return;
     std::lock_guard<std::mutex> lk(g_live_mu);
     if (!live_set().count(ctx)) return;
     (void)hipSetDevice(ctx->device);
-    sync_quietly(ctx->stream);
+    (void)sync_quietly(ctx->stream);
 }
 
 int segments_make(ssp_ctx* ctx, const int64_t* offsets, int64_t n, ssp_segments** out) {
@@ -190,14 +182,9 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
     if (!ctx) return SSP_OK;
     ssp::ctx_unregister(ctx);
     (void)hipSetDevice(ctx->device);
-    ssp::sync_quietly(ctx->stream);
+    (void)ssp::drain_pipe(ctx);
     (void)ssp_comm_destroy(ctx);
-    if (ctx->pipe) {
-        ssp::sync_quietly(ctx->pipe->h2d);
-        ssp::sync_quietly(ctx->pipe->d2h);
-        delete ctx->pipe;
-        ctx->pipe = nullptr;
-    }
+    delete ctx->pipe;
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     for (hipEvent_t& ev : ctx->order_ev)
         if (ev) (void)hipEventDestroy(ev);

@@ -585,12 +585,6 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
                       float* feats_out, bool host, size_t slice_bytes, float* kernel_ms) {
     ssp_ctx* ctx = plan->ctx;
     hipStream_t cs = ctx->stream;
-    if (!ctx->pipe) {
-        ctx->pipe = new (std::nothrow) HostPipe;
-        if (!ctx->pipe) SSP_FAIL(SSP_ERR_NOMEM, "mfcc: host alloc (pipeline)");
-    }
-    HostPipe& hp = *ctx->pipe;
-    SSP_TRY(hp.init());
     const int64_t n = frame_seg->n, D = plan->d_out;
     const std::vector<int64_t>&so = sample_seg->host, &fo = frame_seg->host;
     // slices: [cut[i], cut[i + 1]) utterances
@@ -609,38 +603,22 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
         }
     }
     const int n_slices = (int)cut.size() - 1;
-    // (a slot that has to grow may still be read by work of an earlier call on the other streams: everything is drained first)
-    bool grow = false;
-    for (int k = 0; k < HostPipe::RING; ++k)
-        grow = grow || hp.in[k].bytes < max_in * 4 + 4096 || (host && hp.out[k].bytes < max_out * 4 + 16) || (stype == 1 && host && hp.raw[k].bytes < max_in * 2 + 64);
-    if (grow) {
-        SSP_HIP(hipStreamSynchronize(cs));
-        SSP_HIP(hipStreamSynchronize(hp.h2d));
-        SSP_HIP(hipStreamSynchronize(hp.d2h));
-        for (int k = 0; k < HostPipe::RING; ++k) {
-            SSP_TRY(hp.in[k].reserve(max_in * 4 + 4096));
-            if (host) SSP_TRY(hp.out[k].reserve(max_out * 4 + 16));
-            if (stype == 1 && host) SSP_TRY(hp.raw[k].reserve(max_in * 2 + 64));
-        }
-    }
-    if (plan->cache_variant == 3)   // (the launcher's grow-only counter / flag buffer: sized for the whole table now, not by a later, larger slice)
-        SSP_TRY(plan->f_counter.reserve(64 + (size_t)std::max(plan->cache_n_chunks, 1) * sizeof(int32_t)));
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, cs));
-    // the copy streams start behind whatever the ctx stream holds (the slots' last readers of an earlier call included)
-    SSP_HIP(hipEventRecord(hp.computed[0], cs));
-    SSP_HIP(hipStreamWaitEvent(hp.h2d, hp.computed[0], 0));
-    SSP_HIP(hipStreamWaitEvent(hp.d2h, hp.computed[0], 0));
-    const size_t esz = stype == 1 ? sizeof(int16_t) : sizeof(float);
+    SSP_TRY(pipe_reserve(ctx, max_in * 4 + 4096, stype == 1 && host ? max_in * 2 + 64 : 0, host ? max_out * 4 + 16 : 0));
+    HostPipe& hp = *ctx->pipe;
     // SSP_HOST_TRACE=1 (diagnostic): per slice, when its copy-in, its kernels and its copy-back ended (ms from the call's start, stderr)
     const bool trace = getenv("SSP_HOST_TRACE") != nullptr;
-    std::vector<hipEvent_t> tev;
-    hipEvent_t t_start = nullptr;
+    EventSet tev;   // (3 a slice, then the call's start)
+    Timer tm;
+    DrainIfFailed guard{ctx};   // (declared after the events: an early return drains before they are destroyed)
+    if (plan->cache_variant == 3)   // (the launcher's grow-only counter / flag buffer: sized for the whole table now, not by a later, larger slice)
+        SSP_TRY(plan->f_counter.reserve(64 + (size_t)std::max(plan->cache_n_chunks, 1) * sizeof(int32_t)));
+    SSP_TRY(tm.start(kernel_ms != nullptr, cs));
+    SSP_TRY(hp.start(cs));
+    const size_t esz = stype == 1 ? sizeof(int16_t) : sizeof(float);
+    const size_t t_start = (size_t)n_slices * 3;
     if (trace) {
-        tev.resize((size_t)n_slices * 3, nullptr);
-        for (hipEvent_t& e : tev) SSP_HIP(hipEventCreate(&e));
-        SSP_HIP(hipEventCreate(&t_start));
-        SSP_HIP(hipEventRecord(t_start, cs));
+        SSP_TRY(tev.create(t_start + 1));
+        SSP_HIP(hipEventRecord(tev[t_start], cs));
     }
     for (int i = 0; i < n_slices; ++i) {
         const int k = i % HostPipe::RING;
@@ -679,23 +657,19 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
     }
     SSP_TRY(tm.stop(cs, kernel_ms));
     if (host) SSP_HIP(hipStreamSynchronize(cs));
-    if (trace) {
-        if (host) {
-            fprintf(stderr, "[ssp host pipeline] %d slices of <= %zu MiB (fp32); ms from start: copy-in done | kernels done | copy-back done\n", n_slices, slice_bytes >> 20);
-            for (int i = 0; i < n_slices; ++i) {
-                float a = 0.f, b = 0.f, c = 0.f;
-                (void)hipEventElapsedTime(&a, t_start, tev[(size_t)i * 3]);
-                (void)hipEventElapsedTime(&b, t_start, tev[(size_t)i * 3 + 1]);
-                (void)hipEventElapsedTime(&c, t_start, tev[(size_t)i * 3 + 2]);
-                fprintf(stderr, "[ssp host pipeline] slice %3d: %8.3f %8.3f %8.3f\n", i, a, b, c);
-            }
+    guard.ok = true;
+    if (trace && host) {
+        fprintf(stderr, "[ssp host pipeline] %d slices of <= %zu MiB (fp32); ms from start: copy-in done | kernels done | copy-back done\n", n_slices, slice_bytes >> 20);
+        for (int i = 0; i < n_slices; ++i) {
+            float a = 0.f, b = 0.f, c = 0.f;
+            (void)hipEventElapsedTime(&a, tev[t_start], tev[(size_t)i * 3]);
+            (void)hipEventElapsedTime(&b, tev[t_start], tev[(size_t)i * 3 + 1]);
+            (void)hipEventElapsedTime(&c, tev[t_start], tev[(size_t)i * 3 + 2]);
+            fprintf(stderr, "[ssp host pipeline] slice %3d: %8.3f %8.3f %8.3f\n", i, a, b, c);
         }
-        for (hipEvent_t e : tev) (void)hipEventDestroy(e);
-        (void)hipEventDestroy(t_start);
     }
     return SSP_OK;
 }
-
 
 static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg, const void* samples, int stype,
                         float* feats_out, int where, int variant, float* kernel_ms) {
@@ -717,18 +691,7 @@ static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, con
     const bool two_pass = plan->cache_split_topdb && (v == 1 || v == 4);   // (needs the whole batch's rows in one scratch)
     const bool big = (size_t)n_samp_total * sizeof(float) >= 2 * slice && frame_seg->n >= 2 && sample_seg->host.front() == 0 && frame_seg->host.front() == 0;
     if (!two_pass && ((where == SSP_HOST && big) || (stype == 1 && where == SSP_DEVICE && sample_seg->host.front() == 0 && frame_seg->host.front() == 0)))
-    {
-        const int src = run_sliced(plan, sample_seg, frame_seg, samples, stype, feats_out, where == SSP_HOST, slice, kernel_ms);
-        if (src != SSP_OK && plan->ctx->pipe) {
-            // a call that failed half way must not leave copies in flight that read / write the CALLER's arrays after it has returned:
-            // the three streams are drained before the error goes up (the message of the first failure stays)
-            HostPipe& hp = *plan->ctx->pipe;
-            (void)hipStreamSynchronize(s);
-            if (hp.h2d) (void)hipStreamSynchronize(hp.h2d);
-            if (hp.d2h) (void)hipStreamSynchronize(hp.d2h);
-        }
-        return src;
-    }
+        return run_sliced(plan, sample_seg, frame_seg, samples, stype, feats_out, where == SSP_HOST, slice, kernel_ms);
 
     // one piece: the operands as they are (device pointers), or staged whole through the ctx's pool (host pointers)
     Staged sin, sout, sraw;

@@ -45,23 +45,19 @@ struct StagePoolT {
 };
 #ifndef SSP_STAGING_NO_HIP
 using StagePool = StagePoolT<DevBuf>;
-// Pipeline of large SSP_HOST MFCC batches (mfcc_plan.hip, mfcc_run_host_sliced): the batch goes through RING slots of slice size — slice
-// i + 1 is copied in (own stream) while slice i computes (the ctx stream) and slice i - 1's features are copied back (third stream).
-// The slots, streams and events live on the ctx, are made on first use and kept (grow-only); ssp_ctx_destroy frees them.
+// Ring of device slots that large SSP_HOST calls stream through, on two copy streams beside the ctx stream: run_sliced (mfcc_plan.hip)
+// copies slice i + 1 in while slice i computes and slice i - 1's features go back; feed_rows (below) copies rows in ahead of the scorers.
+// The ctx makes it on first use and keeps it (slots grow-only: pipe_reserve); ssp_ctx_destroy drains and frees it.
 struct HostPipe {
     static constexpr int RING = 3;
     hipStream_t h2d = nullptr, d2h = nullptr;
     DevBuf in[RING], raw[RING], out[RING];          // fp32 samples | int16 samples as copied in (widened into `in`) | features
     hipEvent_t in_ready[RING] = {}, computed[RING] = {}, out_done[RING] = {};
-    int init() {
-        if (h2d) return SSP_OK;
-        SSP_HIP(hipStreamCreateWithFlags(&h2d, hipStreamNonBlocking));
-        SSP_HIP(hipStreamCreateWithFlags(&d2h, hipStreamNonBlocking));
-        for (int i = 0; i < RING; ++i) {
-            SSP_HIP(hipEventCreateWithFlags(&in_ready[i], hipEventDisableTiming));
-            SSP_HIP(hipEventCreateWithFlags(&computed[i], hipEventDisableTiming));
-            SSP_HIP(hipEventCreateWithFlags(&out_done[i], hipEventDisableTiming));
-        }
+    // a call's prologue: the copy streams start behind whatever the ctx stream holds (the slots' last readers of an earlier call included)
+    int start(hipStream_t cs) {
+        SSP_HIP(hipEventRecord(computed[0], cs));
+        SSP_HIP(hipStreamWaitEvent(h2d, computed[0], 0));
+        SSP_HIP(hipStreamWaitEvent(d2h, computed[0], 0));
         return SSP_OK;
     }
     ~HostPipe() {
@@ -79,6 +75,7 @@ struct HostPipe {
 #elif SSP_STAGING_PART == 2
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 namespace ssp {
 // Staging helper for SSP_HOST calls: device copy of a host input / device scratch for an output.
 struct Staged {
@@ -131,6 +128,76 @@ struct Staged {
     }
 };
 
+// hipStreamSynchronize on a stream its owner has already destroyed (a borrowed stream at process exit) does not return an error on
+// ROCm 7.2 — it throws std::bad_variant_access out of the C API; nothing may escape a destroy function
+static inline bool sync_quietly(hipStream_t s) {
+    try {
+        return hipStreamSynchronize(s) == hipSuccess;
+    } catch (...) {
+        return false;
+    }
+}
+// Waits for the ctx stream and the ring's copy streams.  Throws nothing and sets no error message (false = a wait failed).
+static inline bool drain_pipe(const ssp_ctx* ctx) {
+    bool ok = sync_quietly(ctx->stream);
+    if (ctx->pipe) {
+        ok = sync_quietly(ctx->pipe->h2d) && ok;
+        ok = sync_quietly(ctx->pipe->d2h) && ok;
+    }
+    return ok;
+}
+// Scope guard of a ring call: a return before `ok` is set drains the streams, so no copy outlives the call on the CALLER's arrays
+struct DrainIfFailed {
+    const ssp_ctx* ctx;
+    bool ok = false;
+    ~DrainIfFailed() {
+        if (!ok) (void)drain_pipe(ctx);
+    }
+};
+// The ctx's ring for one call, slots of at least in / raw / out bytes (0: unused).  Made on first use, all or nothing (a half-made pipe
+// is freed, the next call starts afresh).  A slot about to grow may still be read by an earlier call's work: all streams drain first.
+static inline int pipe_reserve(ssp_ctx* ctx, size_t in, size_t raw, size_t out) {
+    if (!ctx->pipe) {
+        std::unique_ptr<HostPipe> p(new (std::nothrow) HostPipe);
+        if (!p) SSP_FAIL(SSP_ERR_NOMEM, "host alloc (pipeline)");
+        SSP_HIP(hipStreamCreateWithFlags(&p->h2d, hipStreamNonBlocking));
+        SSP_HIP(hipStreamCreateWithFlags(&p->d2h, hipStreamNonBlocking));
+        for (int i = 0; i < HostPipe::RING; ++i) {
+            SSP_HIP(hipEventCreateWithFlags(&p->in_ready[i], hipEventDisableTiming));
+            SSP_HIP(hipEventCreateWithFlags(&p->computed[i], hipEventDisableTiming));
+            SSP_HIP(hipEventCreateWithFlags(&p->out_done[i], hipEventDisableTiming));
+        }
+        ctx->pipe = p.release();
+    }
+    HostPipe& hp = *ctx->pipe;
+    bool grow = false;
+    for (int k = 0; k < HostPipe::RING; ++k) grow = grow || hp.in[k].bytes < in || hp.raw[k].bytes < raw || hp.out[k].bytes < out;
+    if (!grow) return SSP_OK;
+    if (!drain_pipe(ctx)) SSP_FAIL(SSP_ERR_HIP, "host pipeline: draining the streams before its slots grow failed");
+    for (int k = 0; k < HostPipe::RING; ++k) {
+        if (hp.in[k].bytes < in) SSP_TRY(hp.in[k].alloc(in));
+        if (hp.raw[k].bytes < raw) SSP_TRY(hp.raw[k].alloc(raw));
+        if (hp.out[k].bytes < out) SSP_TRY(hp.out[k].alloc(out));
+    }
+    return SSP_OK;
+}
+struct EventSet {  // hipEvents that live as long as the holder (every return path destroys them)
+    std::vector<hipEvent_t> ev;
+    EventSet() = default;
+    EventSet(const EventSet&) = delete;
+    EventSet& operator=(const EventSet&) = delete;
+    ~EventSet() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create(size_t n) {
+        ev.assign(n, nullptr);
+        for (hipEvent_t& e : ev) SSP_HIP(hipEventCreate(&e));
+        return SSP_OK;
+    }
+    hipEvent_t operator[](size_t i) const { return ev[i]; }
+};
+
 // feed_rows — a HOST matrix through the ctx's ring of device slots, copied in ahead of its consumer (the scorers' host-fed batches: the
 // rows of slice i + 1 and i + 2 cross PCIe on the copy stream while `consume` has slice i's kernels on the ctx stream).  `cuts`: row
 // indices 0 = c0 < c1 < ... < cn of the slices; consume(i, dev) launches slice i's work on ctx->stream, dev = device copy of rows
@@ -140,48 +207,29 @@ template <class F>
 static int feed_rows(ssp_ctx* ctx, const void* host, size_t row_bytes, const std::vector<int64_t>& cuts, F&& consume) {
     const int n = (int)cuts.size() - 1;
     if (n <= 0) return SSP_OK;
-    if (!ctx->pipe) {
-        ctx->pipe = new (std::nothrow) HostPipe;
-        if (!ctx->pipe) SSP_FAIL(SSP_ERR_NOMEM, "host alloc (pipeline)");
-    }
-    HostPipe& hp = *ctx->pipe;
-    SSP_TRY(hp.init());
-    hipStream_t cs = ctx->stream;
     size_t max_bytes = 0;
     for (int i = 0; i < n; ++i) max_bytes = std::max(max_bytes, (size_t)(cuts[(size_t)i + 1] - cuts[(size_t)i]) * row_bytes);
-    bool grow = false;
-    for (int k = 0; k < HostPipe::RING; ++k) grow = grow || hp.in[k].bytes < max_bytes + 256;
-    if (grow) {  // (a slot that has to grow may still be read by work of an earlier call: everything is drained first)
-        SSP_HIP(hipStreamSynchronize(cs));
-        SSP_HIP(hipStreamSynchronize(hp.h2d));
-        SSP_HIP(hipStreamSynchronize(hp.d2h));
-        for (int k = 0; k < HostPipe::RING; ++k) SSP_TRY(hp.in[k].reserve(max_bytes + 256));
-    }
-    auto body = [&]() -> int {
-        auto issue = [&](int i) -> int {
-            const int k = i % HostPipe::RING;
-            SSP_HIP(hipMemcpyAsync(hp.in[k].p, static_cast<const char*>(host) + (size_t)cuts[(size_t)i] * row_bytes,
-                                   (size_t)(cuts[(size_t)i + 1] - cuts[(size_t)i]) * row_bytes, hipMemcpyHostToDevice, hp.h2d));
-            SSP_HIP(hipEventRecord(hp.in_ready[k], hp.h2d));
-            return SSP_OK;
-        };
-        SSP_HIP(hipEventRecord(hp.computed[0], cs));   // the copy stream starts behind what the ctx stream holds (the slots' last readers)
-        SSP_HIP(hipStreamWaitEvent(hp.h2d, hp.computed[0], 0));
-        for (int i = 0; i < n && i < HostPipe::RING - 1; ++i) SSP_TRY(issue(i));
-        for (int i = 0; i < n; ++i) {
-            if (i + HostPipe::RING - 1 < n) SSP_TRY(issue(i + HostPipe::RING - 1));   // its slot's last reader was slice i - 1: waited for below
-            SSP_HIP(hipStreamWaitEvent(cs, hp.in_ready[i % HostPipe::RING], 0));
-            SSP_TRY(consume(i, hp.in[i % HostPipe::RING].p));
-            SSP_HIP(hipStreamSynchronize(cs));
-        }
+    SSP_TRY(pipe_reserve(ctx, max_bytes + 256, 0, 0));
+    HostPipe& hp = *ctx->pipe;
+    hipStream_t cs = ctx->stream;
+    DrainIfFailed guard{ctx};
+    auto issue = [&](int i) -> int {
+        const int k = i % HostPipe::RING;
+        SSP_HIP(hipMemcpyAsync(hp.in[k].p, static_cast<const char*>(host) + (size_t)cuts[(size_t)i] * row_bytes,
+                               (size_t)(cuts[(size_t)i + 1] - cuts[(size_t)i]) * row_bytes, hipMemcpyHostToDevice, hp.h2d));
+        SSP_HIP(hipEventRecord(hp.in_ready[k], hp.h2d));
         return SSP_OK;
     };
-    const int rc = body();
-    if (rc != SSP_OK) {
-        (void)hipStreamSynchronize(cs);
-        (void)hipStreamSynchronize(hp.h2d);
+    SSP_TRY(hp.start(cs));
+    for (int i = 0; i < n && i < HostPipe::RING - 1; ++i) SSP_TRY(issue(i));
+    for (int i = 0; i < n; ++i) {
+        if (i + HostPipe::RING - 1 < n) SSP_TRY(issue(i + HostPipe::RING - 1));   // its slot's last reader was slice i - 1: waited for below
+        SSP_HIP(hipStreamWaitEvent(cs, hp.in_ready[i % HostPipe::RING], 0));
+        SSP_TRY(consume(i, hp.in[i % HostPipe::RING].p));
+        SSP_HIP(hipStreamSynchronize(cs));
     }
-    return rc;
+    guard.ok = true;
+    return SSP_OK;
 }
 
 static inline size_t host_slice_bytes() {
