@@ -257,6 +257,21 @@ int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, 
                      const float* feats, int64_t n_frames, double* nk_out, double* sx_out, double* sxx_out,
                      double* loglik_sum_out, int where, float* kernel_ms);
 
+/* The same statistics for M models in one call (one EM iteration of many speaker models; GMM_UBM.py:154-170 trains one per speaker).
+ * Model m is scored over rows [row_off[m], row_off[m] + n_frames[m]) of feats (float[n_rows x D], on the side `where` names); the ranges
+ * may come in any order, leave gaps and overlap.  HOST double weights[M x K], means[M x K x D], covars[M x K x D]; outputs (HOST double)
+ * nk_out[M x K], sx_out / sxx_out[M x K x D], loglik_sum_out[M], each model's as ssp_gmm_em_stats defines them.  row_off / n_frames:
+ * HOST int64[M].  SSP_ERR_INVALID: M < 1, a model without frames, a range outside [0, n_rows), a non-positive weight or covariance
+ * (the messages name the model).  SSP_ERR_UNSUPPORTED: D > 47.
+ * Contract.  K <= 64: each model's outputs are BIT-IDENTICAL to ssp_gmm_em_stats on that model's rows (same kernel body, same partition
+ * of its frames, same float64 reduction order).  K > 64: fp32 MFMA log-sum-exp per frame and fp32 partial sums reduced in float64, within
+ * fp32 rounding of ssp_gmm_em_stats (whose log-sum-exp comes from the scoring kernel) but not bit for bit.
+ * Work: one upload of the parameters and one result copy + host wait per call; the models' partial sums are grouped into launches under
+ * a scratch budget (SSP_EM_BATCH_SCRATCH_MB, default 1024). */
+int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                           const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
+                           double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms);
+
 /* ---- DTW template matching: replaces the distance_dtw double loop of MFCC_DTW.py:57-108,187-217
  *      (dtw.accelerated_dtw(x, y, dist='euclidean'), warp 1) for every (query, template) pair ---- */
 /* xq: float[total query rows x dim] with q_seg row offsets; xt, t_seg likewise for the templates (dim = 1: the reference's

@@ -15,7 +15,7 @@ import pickle as pkl
 import numpy as np
 
 from . import api, frontend
-from .gmm_train import GaussianMixture
+from .gmm_train import GaussianMixture, fit_many
 from .sidekit_features import mfcc, plp, plp_batch  # noqa: F401  (GMM_UBM.py:20 imports both names)
 
 
@@ -124,7 +124,8 @@ def load_models(model_dir="Model"):
 def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None):
     """GMM_UBM.py:134-199.  ``model`` falsy (the reference's default): one ``GaussianMixture(n_components, 'diag')`` per
     speaker is fitted on ``train[speaker]`` (speakers in ascending label order, like label_encoder.values()) and the UBM
-    on the stacked training data (GMM_UBM.py:154-170), EM on the GPU; with ``model_dir`` (the reference always uses
+    on the stacked training data (GMM_UBM.py:154-170), EM on the GPU (the speaker models together through gmm_train.fit_many for
+    n_components <= 64 and D <= 47, bit for bit the loop's models); with ``model_dir`` (the reference always uses
     "Model") the two pickles of GMM_UBM.py:173-179 are written.  ``model=True``: load those pickles from ``model_dir``
     (default "Model", GMM_UBM.py:141-146).  ``model`` = (list_of_speaker_GMMs, UBM): use them as given.
     Prints and returns the train/test accuracies the reference prints; the models are left in ``GMM.last_model``."""
@@ -132,8 +133,12 @@ def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, ra
         model = load_models(model_dir or "Model")
     elif not model:
         speakers = sorted(train.keys())
-        gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state).fit(train[s])
-                for s in speakers]
+        D = np.asarray(train[speakers[0]]).shape[1] if speakers else 0
+        if n_components <= 64 and D <= 47:  # one EM launch per iteration for all speakers; the same bits as the loop below
+            gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type='diag', random_state=random_state)
+        else:
+            gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state).fit(train[s])
+                    for s in speakers]
         ubm_train = np.vstack([train[s] for s in speakers])
         ubm = GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state).fit(ubm_train)
         model = (gmms, ubm)

@@ -428,6 +428,39 @@ def gmm_em_stats(ctx: "Context", weights, means, covars, feats, timing: bool = F
     return res
 
 
+def gmm_em_stats_batch(ctx: "Context", weights, means, covars, feats, row_off, n_frames, timing: bool = False) -> dict:
+    """gmm_em_stats for M models in one call (ssp_gmm_em_stats_batch): model m over rows [row_off[m], row_off[m] + n_frames[m]) of feats.
+    weights (M,K), means (M,K,D), covars (M,K,D) float64; feats (n_rows, D) float32 (numpy or device tensor); row_off, n_frames (M,).
+    Returns nk (M,K), sx (M,K,D), sxx (M,K,D), loglik_sum (M,) as float64; for K <= 64 each model's are the bits gmm_em_stats gives
+    on its rows.  D > 47: NotImplementedError."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    mu = np.ascontiguousarray(means, dtype=np.float64)
+    cv = np.ascontiguousarray(covars, dtype=np.float64)
+    if w.ndim != 2 or mu.ndim != 3 or mu.shape != cv.shape or mu.shape[:2] != w.shape:
+        raise ValueError("expected weights (M,K), means (M,K,D), covars (M,K,D)")
+    M, K, D = mu.shape
+    off = np.ascontiguousarray(row_off, dtype=np.int64)
+    cnt = np.ascontiguousarray(n_frames, dtype=np.int64)
+    if off.shape != (M,) or cnt.shape != (M,):
+        raise ValueError("row_off and n_frames must be (%d,)" % M)
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2 or keep.shape[1] != D:
+        raise ValueError("feats must be (frames, %d)" % D)
+    nk = np.empty((M, K), dtype=np.float64)
+    sx = np.empty((M, K, D), dtype=np.float64)
+    sxx = np.empty((M, K, D), dtype=np.float64)
+    ll = np.empty(M, dtype=np.float64)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_gmm_em_stats_batch(ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
+                                                    off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
+                                                    ll.ctypes.data, where, C.byref(ms) if timing else None))
+    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll}
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 class GmmScorer:
     """Packed diagonal GMMs (ssp_gmm).  weights (M,K), means (M,K,D), covars (M,K,D) float64.
     has_ubm: model 0 is the UBM (GMM_UBM.py:169-170); scores/argmax are then taken against it."""

@@ -15,6 +15,10 @@
 //   gmm_em_reduce_kernel partials -> float64 sums in a fixed order (bit-reproducible)
 // Parameters enter as A = mu P, B = -P/2, c = ln w + 1/2 sum ln P - 1/2 sum mu^2 P - D/2 ln 2pi (float64 on the host, fp32
 // on the device): lp = c + sum_d x_d (A_d + x_d B_d).
+// Batched form (ssp_gmm_em_stats_batch, D <= 47): M models over row ranges of one feature buffer, one launch group per scratch budget:
+//   gmm_em_acc_mfma_seg_kernel  the body of gmm_em_acc_mfma_kernel over a work table of (model, walker) — K <= 64 bit-identical per model
+//   gmm_em_lse_mfma_seg_kernel  K > 64: per-frame log-sum-exp over every 64-mixture chunk of a model (MFMA, online max / sum)
+//   gmm_em_reduce_seg_kernel    the body of gmm_em_reduce_kernel per model
 #include <cmath>
 
 #include "common.hpp"
@@ -160,8 +164,12 @@ __global__ __launch_bounds__(64) void gmm_em_lsesum_kernel(const float* __restri
 // FUSE (K <= 64: the workgroup sees every mixture of a frame): the per-frame log-sum-exp is taken right here from the GEMM1
 // accumulators (in-lane over 16 mixtures, across the two half-waves, across the two waves that share a frame through LDS) instead of a
 // separate scoring pass; sum_t lse[t] leaves as one partial per workgroup.
-template <int NCT, bool FUSE>
-__global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
+// The body of gmm_em_acc_mfma_kernel, shared with its batched form gmm_em_acc_mfma_seg_kernel so that a model's frames meet the same
+// instructions in both (the batched path is bit-identical to the single-model call): `a` describes ONE model's frames, parameters and
+// partials, `wg` is this workgroup's walker index among a.G (tiles wg, wg + a.G, ...).  SEG: the staging loops run with wave-uniform
+// trip counts (the batched kernels keep no loop over lane masks; the single-model kernel keeps its instructions as they were).
+template <int NCT, bool FUSE, bool SEG>
+__device__ __forceinline__ void em_mfma_body(const EmArgs& a, unsigned wg) {
     extern __shared__ float sm[];
     const int D = a.D, W = 2 * D + 1, KS = (W + 1) / 2;  // KS k-steps of 2 over [x, x^2, 1] (+ a zero pad column)
     const int XS = (2 * KS) | 1;       // odd row stride of the augmented frame tile
@@ -174,13 +182,30 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fl = lane & 31, h = lane >> 5;
     const int kc = blockIdx.y * EM_KC;
-    for (int i = tid; i < 2 * KS * EM_KC; i += 256) {
-        const int k = i / EM_KC, m = i - k * EM_KC;
-        wsT[i] = k < W ? a.par[(size_t)(kc + m) * W + k] : 0.f;
-    }
-    for (int i = tid; i < EM_TF * (2 * KS - 2 * D); i += 256) {  // the constant columns [1, 0...] of every row, written once
-        const int r = i / (2 * KS - 2 * D), c = i - r * (2 * KS - 2 * D);
-        xs[r * XS + 2 * D + c] = c == 0 ? 1.f : 0.f;
+    if constexpr (SEG) {
+        for (int i0 = 0; i0 < 2 * KS * EM_KC; i0 += 256) {
+            const int i = i0 + tid;
+            if (i < 2 * KS * EM_KC) {
+                const int k = i / EM_KC, m = i - k * EM_KC;
+                wsT[i] = k < W ? a.par[(size_t)(kc + m) * W + k] : 0.f;
+            }
+        }
+        for (int i0 = 0; i0 < EM_TF * (2 * KS - 2 * D); i0 += 256) {
+            const int i = i0 + tid;
+            if (i < EM_TF * (2 * KS - 2 * D)) {
+                const int r = i / (2 * KS - 2 * D), c = i - r * (2 * KS - 2 * D);
+                xs[r * XS + 2 * D + c] = c == 0 ? 1.f : 0.f;
+            }
+        }
+    } else {
+        for (int i = tid; i < 2 * KS * EM_KC; i += 256) {
+            const int k = i / EM_KC, m = i - k * EM_KC;
+            wsT[i] = k < W ? a.par[(size_t)(kc + m) * W + k] : 0.f;
+        }
+        for (int i = tid; i < EM_TF * (2 * KS - 2 * D); i += 256) {  // the constant columns [1, 0...] of every row, written once
+            const int r = i / (2 * KS - 2 * D), c = i - r * (2 * KS - 2 * D);
+            xs[r * XS + 2 * D + c] = c == 0 ? 1.f : 0.f;
+        }
     }
     const int r1 = wave >> 1, c1 = wave & 1;  // GEMM1 tile of this wave
     f32x16 acc2[2][NCT];
@@ -208,8 +233,8 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
         if (FUSE) lpre = fr < nt ? 0.f : INFINITY;
         else lpre = fr < nt ? a.lse[base + fr] : INFINITY;  // frames beyond the end: resp = exp(-inf) = 0
     };
-    fetch(blockIdx.x);
-    for (int tile = blockIdx.x; tile < a.n_tiles; tile += a.G) {
+    fetch(wg);
+    for (int tile = wg; tile < a.n_tiles; tile += a.G) {
         __syncthreads();  // the previous tile's GEMM2 is done with xs / rs
 #pragma unroll
         for (int u = 0; u < EM_XP; ++u) {
@@ -296,9 +321,9 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
         __syncthreads();
         if (lane == 0 && r1 == 0) ex[c1] = lsum;
         __syncthreads();
-        if (tid == 0) a.lse_part[blockIdx.x] = ex[0] + ex[1];
+        if (tid == 0) a.lse_part[wg] = ex[0] + ex[1];
     }
-    float* out = a.part + ((size_t)(blockIdx.x * 4 + wave) * a.Kp + kc) * W;
+    float* out = a.part + ((size_t)(wg * 4 + wave) * a.Kp + kc) * W;
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -310,13 +335,18 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
         }
 }
 
+template <int NCT, bool FUSE>
+__global__ __launch_bounds__(256) void gmm_em_acc_mfma_kernel(EmArgs a) {
+    em_mfma_body<NCT, FUSE, false>(a, blockIdx.x);
+}
+
 // out[j] = sum_g part[g][j] (float64, fixed order): block = 32 columns x 8 slices of the partial index (coalesced 128-byte
 // reads), the 8 slice sums are added in slice order;  block 0 also reduces the lse partials
-__global__ __launch_bounds__(256) void gmm_em_reduce_kernel(const float* part, int G, int64_t cols, const float* lse_part, int64_t n_lse,
-                                                            double* out) {
+__device__ __forceinline__ void em_reduce_body(const float* part, int G, int64_t cols, const float* lse_part, int64_t n_lse, double* out,
+                                               unsigned bx) {
     __shared__ double sh[256];
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    const int64_t j = (int64_t)blockIdx.x * 32 + tx;
+    const int64_t j = (int64_t)bx * 32 + tx;
     double s = 0.0;
     if (j < cols)
         for (int g = ty; g < G; g += 8) s += (double)part[(size_t)g * cols + j];
@@ -327,7 +357,7 @@ __global__ __launch_bounds__(256) void gmm_em_reduce_kernel(const float* part, i
         for (int k = 0; k < 8; ++k) t += sh[k * 32 + tx];
         out[j] = t;
     }
-    if (blockIdx.x == 0) {  // sum_t lse[t]: fixed strided order + tree
+    if (bx == 0) {  // sum_t lse[t]: fixed strided order + tree
         __syncthreads();
         double v = 0.0;
         for (int64_t i = threadIdx.x; i < n_lse; i += 256) v += (double)lse_part[i];
@@ -341,9 +371,199 @@ __global__ __launch_bounds__(256) void gmm_em_reduce_kernel(const float* part, i
     }
 }
 
+__global__ __launch_bounds__(256) void gmm_em_reduce_kernel(const float* part, int G, int64_t cols, const float* lse_part, int64_t n_lse,
+                                                            double* out) {
+    em_reduce_body(part, G, cols, lse_part, n_lse, out, blockIdx.x);
+}
+
+// ---- batched form (ssp_gmm_em_stats_batch): M models, each scored over its own row range of one feature buffer
+// one model of a batched call: where its frames, parameters and partials live
+struct EmModel {
+    int64_t x_off;     // first feature row of its range
+    int64_t n;         // frames
+    int64_t lse_off;   // its per-frame lse values in the call's lse buffer (K > 64)
+    int64_t part_off;  // its [4 G][Kp][2D+1] wave partials in the launch group's partial buffer (floats)
+    int64_t lsep_off;  // its lse partials: G of them (K <= 64, fused), n_tiles otherwise
+    int32_t n_tiles, G;
+};
+
+struct EmBatchArgs {
+    const float* x;         // [n_rows x D]
+    const float* par;       // [M][Kp][2D+1]
+    float* lse;             // [sum of n]  (K > 64)
+    float* lse_part;        // [sum of the models' lse partials]
+    float* part;            // the launch group's wave partials
+    const EmModel* models;  // [M]
+    const int2* work;       // per workgroup: (model, walker g) for the accumulation kernel, (model, tile) for the lse kernel
+    int32_t D, K, Kp;
+};
+
+__device__ __forceinline__ int em_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t em_uniform64(int64_t v) {
+    const uint64_t u = (uint64_t)v;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// model m of a batched call as the EmArgs of a single-model call; every value wave-uniform (read through readfirstlane: a persistent
+// walk whose bounds the compiler cannot prove uniform may be rebuilt as a loop over lane masks — tests/test_isa_guards.py)
+__device__ __forceinline__ EmArgs em_seg_args(const EmBatchArgs& b, int m) {
+    const EmModel& md = b.models[m];
+    EmArgs a;
+    const int D = b.D;
+    a.x = b.x + em_uniform64(md.x_off) * D;
+    a.par = b.par + (size_t)m * b.Kp * (2 * D + 1);
+    a.lse = b.lse + em_uniform64(md.lse_off);
+    a.lse_part = b.lse_part + em_uniform64(md.lsep_off);
+    a.part = b.part + em_uniform64(md.part_off);
+    a.n = em_uniform64(md.n);
+    a.D = D;
+    a.K = b.K;
+    a.Kp = b.Kp;
+    a.G = em_uniform(md.G);
+    a.n_tiles = em_uniform(md.n_tiles);
+    return a;
+}
+
+// gmm_em_acc_mfma_kernel over a work table: workgroup (x, y) = walker g of model m (work[x]), mixture chunk y.  What it reads and
+// writes for its model is exactly what the single-model kernel does for walker g of a call on that model's rows.
+template <int NCT, bool FUSE>
+__global__ __launch_bounds__(256) void gmm_em_acc_mfma_seg_kernel(EmBatchArgs b) {
+    const int2 w = b.work[blockIdx.x];
+    const int m = em_uniform(w.x), g = em_uniform(w.y);
+    em_mfma_body<NCT, FUSE, true>(em_seg_args(b, m), (unsigned)g);
+}
+
+// per-frame log-sum-exp for K > 64 (several 64-mixture chunks): workgroup = one 64-frame tile of one model (work[x] = (model, tile)).
+// Per chunk: GEMM1 as in em_mfma_body (wave (r1, c1): mixtures 32 r1.., frames 32 c1..), then an online (max, sum) per frame over the
+// chunks; the two mixture halves meet in LDS.  Writes lse[t] of the tile's frames and one lse partial per tile.
+__global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b) {
+    extern __shared__ float sm[];
+    const int2 w = b.work[blockIdx.x];
+    const int mi = em_uniform(w.x), tile = em_uniform(w.y);
+    const EmArgs a = em_seg_args(b, mi);
+    const int D = a.D, W = 2 * D + 1, KS = (W + 1) / 2;
+    const int XS = (2 * KS) | 1;
+    float* xs = sm;                    // [64 frames][XS]  aug = [x, x^2, 1, 0]
+    float* wsT = xs + EM_TF * XS;      // [2 KS][64 mix]   parameter chunk, k-major
+    float* ex = wsT + 2 * KS * EM_KC;  // [2 mixture halves][64 frames][2]  (max, sum) exchange, then 4 wave sums
+    const int tid = threadIdx.x, lane = tid & 63, wave = em_uniform(tid >> 6);
+    const int fl = lane & 31, h = lane >> 5, r1 = wave >> 1, c1 = wave & 1;
+    const int64_t base = (int64_t)tile * EM_TF;
+    const int nt = (int)min<int64_t>(EM_TF, a.n - base);
+    for (int i0 = 0; i0 < EM_TF * 2 * KS; i0 += 256) {
+        const int i = i0 + tid;
+        if (i < EM_TF * 2 * KS) {
+            const int r = i / (2 * KS), c = i - r * (2 * KS);
+            float v = c == 2 * D ? 1.f : 0.f;
+            if (c < 2 * D) {
+                const int cd = c < D ? c : c - D;
+                const float xv = r < nt ? a.x[(base + r) * D + cd] : 0.f;
+                v = c < D ? xv : xv * xv;
+            }
+            xs[r * XS + c] = v;
+        }
+    }
+    const float* xrow = xs + (32 * c1 + fl) * XS;
+    const float* wcol = wsT + h * EM_KC + 32 * r1 + fl;
+    float m = -INFINITY, s = 0.f;  // this lane's frame over the mixtures of half r1 seen so far
+    for (int kc = 0; kc < a.Kp; kc += EM_KC) {
+        __syncthreads();  // the previous chunk's GEMM1 is done with wsT
+        for (int i0 = 0; i0 < 2 * KS * EM_KC; i0 += 256) {
+            const int i = i0 + tid;
+            if (i < 2 * KS * EM_KC) {
+                const int k = i / EM_KC, mm = i - k * EM_KC;
+                wsT[i] = k < W ? a.par[(size_t)(kc + mm) * W + k] : 0.f;
+            }
+        }
+        __syncthreads();
+        f32x16 acc1;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc1[i] = 0.f;
+        int s2 = 0;
+        for (; s2 + 3 < KS; s2 += 4) {
+            float av[4], bv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                av[u] = wcol[(2 * (s2 + u)) * EM_KC];
+                bv[u] = xrow[2 * (s2 + u) + h];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc1, 0, 0, 0);
+        }
+        for (; s2 < KS; ++s2)
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * EM_KC], xrow[2 * s2 + h], acc1, 0, 0, 0);
+        float cm = acc1[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i) cm = fmaxf(cm, acc1[i]);
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        float cs = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) cs += __expf(acc1[i] - cm);
+        cs += __shfl_xor(cs, 32);
+        const float mn = fmaxf(m, cm);  // (padded mixtures: c = -1e30, finite; the first chunk makes m finite)
+        s = s * __expf(m - mn) + cs * __expf(cm - mn);
+        m = mn;
+    }
+    const int fr = 32 * c1 + fl;
+    if (h == 0) *reinterpret_cast<float2*>(ex + (r1 * 64 + fr) * 2) = make_float2(m, s);
+    __syncthreads();
+    const float2 o = *reinterpret_cast<const float2*>(ex + ((1 - r1) * 64 + fr) * 2);
+    const float mm = fmaxf(m, o.x);
+    const float l = mm + __logf(s * __expf(m - mm) + o.y * __expf(o.x - mm));
+    const bool mine = r1 == 0 && h == 0 && fr < nt;  // waves 0 and 1 own frames 0..31 and 32..63
+    if (mine) a.lse[base + fr] = l;
+    float v = mine ? l : 0.f;
+    for (int o2 = 32; o2 > 0; o2 >>= 1) v += __shfl_xor(v, o2);
+    __syncthreads();  // every wave has read the exchange
+    if (lane == 0) ex[wave] = v;
+    __syncthreads();
+    if (tid == 0) a.lse_part[tile] = ex[0] + ex[1];
+}
+
+// gmm_em_reduce_kernel per model: grid (column blocks, models of the launch group from m0); out[m][cols + 1]
+__global__ __launch_bounds__(256) void gmm_em_reduce_seg_kernel(EmBatchArgs b, int m0, int64_t cols, int fused, double* out) {
+    const int m = m0 + blockIdx.y;
+    const EmModel& md = b.models[m];
+    em_reduce_body(b.part + md.part_off, 4 * md.G, cols, b.lse_part + md.lsep_off, fused ? (int64_t)md.G : (int64_t)md.n_tiles,
+                   out + (size_t)m * (cols + 1), blockIdx.x);
+}
+
 }  // namespace ssp
 
 using namespace ssp;
+
+// float64 parameters of one model -> the fp32 rows [Kp][2D+1] the EM kernels read (A = mu P, B = -P/2, c; padded rows c = -1e30).
+// par must be zeroed.  model >= 0: a batched call's model index, named in the messages.
+static int em_pack(int K, int D, int Kp, const double* weights, const double* means, const double* covars, float* par, int model) {
+    const int W = 2 * D + 1;
+    const double ln2pi = std::log(2.0 * M_PI);
+    for (int k = 0; k < Kp; ++k) {
+        float* w = par + (size_t)k * W;
+        if (k >= K) {
+            w[2 * D] = -1.0e30f;  // padded mixture: resp = exp(-1e30 - lse) = 0
+            continue;
+        }
+        if (!(weights[k] > 0.0)) {
+            if (model < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive weight (mix %d)", k);
+            SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: non-positive weight (model %d, mix %d)", model, k);
+        }
+        double c = std::log(weights[k]) - 0.5 * D * ln2pi;
+        for (int d = 0; d < D; ++d) {
+            const double cv = covars[(size_t)k * D + d], mu = means[(size_t)k * D + d];
+            if (!(cv > 0.0)) {
+                if (model < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive covariance (mix %d)", k);
+                SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: non-positive covariance (model %d, mix %d)", model, k);
+            }
+            const double P = 1.0 / cv;
+            w[d] = (float)(mu * P);
+            w[D + d] = (float)(-0.5 * P);
+            c += 0.5 * std::log(P) - 0.5 * mu * mu * P;
+        }
+        w[2 * D] = (float)c;
+    }
+    return SSP_OK;
+}
 
 extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, const double* means,
                                 const double* covars, const float* feats, int64_t n_frames, double* nk_out, double* sx_out,
@@ -358,25 +578,7 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: where");
     const int W = 2 * D + 1, Kp = (K + EM_KC - 1) / EM_KC * EM_KC;
     std::vector<float> par((size_t)Kp * W, 0.f);
-    const double ln2pi = std::log(2.0 * M_PI);
-    for (int k = 0; k < Kp; ++k) {
-        float* w = par.data() + (size_t)k * W;
-        if (k >= K) {
-            w[2 * D] = -1.0e30f;  // padded mixture: resp = exp(-1e30 - lse) = 0
-            continue;
-        }
-        if (!(weights[k] > 0.0)) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive weight (mix %d)", k);
-        double c = std::log(weights[k]) - 0.5 * D * ln2pi;
-        for (int d = 0; d < D; ++d) {
-            const double cv = covars[(size_t)k * D + d], mu = means[(size_t)k * D + d];
-            if (!(cv > 0.0)) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive covariance (mix %d)", k);
-            const double P = 1.0 / cv;
-            w[d] = (float)(mu * P);
-            w[D + d] = (float)(-0.5 * P);
-            c += 0.5 * std::log(P) - 0.5 * mu * mu * P;
-        }
-        w[2 * D] = (float)c;
-    }
+    SSP_TRY(em_pack(K, D, Kp, weights, means, covars, par.data(), -1));
     hipStream_t s = ctx->stream;
     const int64_t n_tiles = (n_frames + EM_TF - 1) / EM_TF;
     if (n_tiles > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats: too many frames");
@@ -479,5 +681,157 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
         nk_out[k] = r[2 * D];
     }
     *loglik_sum_out = host[(size_t)cols];
+    return SSP_OK;
+}
+
+extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                                      const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off,
+                                      const int64_t* n_frames, double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out,
+                                      int where, float* kernel_ms) {
+    ssp::TraceRange trace_("ssp_gmm_em_stats_batch");
+    SSP_TRY(use_ctx(ctx));
+    if (kernel_ms) *kernel_ms = 0.f;
+    if (M < 1 || K < 1 || D < 1 || !weights || !means || !covars || !row_off || !n_frames || !nk_out || !sx_out || !sxx_out ||
+        !loglik_sum_out)
+        SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: bad shape or null array");
+    const int W = 2 * D + 1, nct = (W + 31) / 32;
+    if (nct > 3) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: D=%d exceeds the batched path's feature dimension (47)", D);
+    if (n_rows < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: no frames");
+    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: where");
+    for (int m = 0; m < M; ++m) {
+        if (n_frames[m] < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: model %d has no frames", m);
+        if (row_off[m] < 0 || row_off[m] > n_rows - n_frames[m])
+            SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: model %d: rows [%lld, %lld) outside the %lld feature rows", m,
+                     (long long)row_off[m], (long long)(row_off[m] + n_frames[m]), (long long)n_rows);
+    }
+    const int Kp = (K + EM_KC - 1) / EM_KC * EM_KC, chunks = Kp / EM_KC;
+    const bool fuse = chunks == 1;  // K <= 64: the fused kernel, bit-identical to ssp_gmm_em_stats per model
+    const int64_t cols = (int64_t)Kp * W;
+    std::vector<float> par((size_t)M * Kp * W, 0.f);
+    for (int m = 0; m < M; ++m)
+        SSP_TRY(em_pack(K, D, Kp, weights + (size_t)m * K, means + (size_t)m * K * D, covars + (size_t)m * K * D, par.data() + (size_t)m * Kp * W, m));
+    // partition: K <= 64 as the single call (G = min(tiles, 2 CUs' worth)); K > 64: G capped so that G x chunks <= 2 x num_cu
+    // workgroups per model (bounded partials: 4 G Kp (2D+1) floats)
+    const int64_t gcap = fuse ? 2 * (int64_t)ctx->num_cu : std::max<int64_t>(1, 2 * (int64_t)ctx->num_cu / chunks);
+    // launch groups: consecutive models whose partials fit the scratch budget (SSP_EM_BATCH_SCRATCH_MB, default 1024); the partial
+    // buffer is reused group after group on the ctx stream
+    int64_t budget = (int64_t)1 << 30;
+    if (const char* e = getenv("SSP_EM_BATCH_SCRATCH_MB")) budget = std::max<int64_t>(1, atoll(e)) << 20;
+    const int64_t budget_f = budget / (int64_t)sizeof(float);
+    std::vector<EmModel> md(M);
+    std::vector<int> gstart;                         // first model of every launch group (+ M)
+    std::vector<int64_t> wstart;                     // first work item of every group (+ total)
+    std::vector<int2> work, tiles;
+    int64_t lse_tot = 0, lsep_tot = 0, cur = 0, part_max = 0;
+    for (int m = 0; m < M; ++m) {
+        const int64_t nt = (n_frames[m] + EM_TF - 1) / EM_TF;
+        if (nt > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: too many frames (model %d)", m);
+        const int G = (int)std::min<int64_t>(nt, gcap);
+        const int64_t pf = 4 * (int64_t)G * cols;
+        if (m == 0 || (cur > 0 && cur + pf > budget_f) || m - gstart.back() >= 65535) {
+            gstart.push_back(m);
+            wstart.push_back((int64_t)work.size());
+            cur = 0;
+        }
+        md[m] = EmModel{row_off[m], n_frames[m], lse_tot, cur, lsep_tot, (int32_t)nt, G};
+        cur += pf;
+        part_max = std::max(part_max, cur);
+        if (!fuse) lse_tot += n_frames[m];
+        lsep_tot += fuse ? G : nt;
+        for (int g = 0; g < G; ++g) work.push_back(make_int2(m, g));
+        if (!fuse)
+            for (int64_t t = 0; t < nt; ++t) tiles.push_back(make_int2(m, (int)t));
+    }
+    gstart.push_back(M);
+    wstart.push_back((int64_t)work.size());
+    if ((int64_t)tiles.size() > INT32_MAX || (int64_t)work.size() > INT32_MAX)
+        SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: too many frames");
+    hipStream_t s = ctx->stream;
+    DevBuf &d_par = ctx->scratch[0], &d_lse = ctx->scratch[1], &d_lsep = ctx->scratch[2], &d_part = ctx->scratch[3],
+           &d_out = ctx->scratch[4], &d_tab = ctx->scratch[5];
+    Staged sx;
+    int rc;
+    const float* d_x = (const float*)sx.in(ctx, feats, (size_t)n_rows * D * sizeof(float), where, &rc);
+    SSP_TRY(rc);
+    const size_t tab_models = (size_t)M * sizeof(EmModel), tab_work = work.size() * sizeof(int2), tab_tiles = tiles.size() * sizeof(int2);
+    SSP_TRY(d_par.reserve(par.size() * sizeof(float)));
+    SSP_TRY(d_lse.reserve((size_t)std::max<int64_t>(lse_tot, 1) * sizeof(float)));
+    SSP_TRY(d_lsep.reserve((size_t)lsep_tot * sizeof(float)));
+    SSP_TRY(d_part.reserve((size_t)part_max * sizeof(float)));
+    SSP_TRY(d_out.reserve((size_t)M * (cols + 1) * sizeof(double)));
+    SSP_TRY(d_tab.reserve(tab_models + tab_work + tab_tiles));
+    std::vector<char> tab(tab_models + tab_work + tab_tiles);
+    memcpy(tab.data(), md.data(), tab_models);
+    memcpy(tab.data() + tab_models, work.data(), tab_work);
+    if (tab_tiles) memcpy(tab.data() + tab_models + tab_work, tiles.data(), tab_tiles);
+    SSP_HIP(hipMemcpyAsync(d_par.p, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    SSP_HIP(hipMemcpyAsync(d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    const EmModel* d_models = (const EmModel*)d_tab.p;
+    const int2* d_work = (const int2*)((char*)d_tab.p + tab_models);
+    const int2* d_tiles = (const int2*)((char*)d_tab.p + tab_models + tab_work);
+    EmBatchArgs b{d_x, d_par.as<float>(), d_lse.as<float>(), d_lsep.as<float>(), d_part.as<float>(), d_models, d_work, D, K, Kp};
+    const size_t lds_acc = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + (size_t)EM_TF * 65 + 256) * sizeof(float);
+    const size_t lds_lse = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + 256) * sizeof(float);
+    const void* acc_k = nullptr;
+    switch (nct * 2 + (fuse ? 1 : 0)) {
+        case 2: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<1, false>); break;
+        case 3: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<1, true>); break;
+        case 4: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<2, false>); break;
+        case 5: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<2, true>); break;
+        case 6: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<3, false>); break;
+        default: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<3, true>); break;
+    }
+    if (lds_acc > 64 * 1024) SSP_HIP(hipFuncSetAttribute(acc_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_acc));
+    if (!fuse && lds_lse > 64 * 1024)
+        SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_em_lse_mfma_seg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lse));
+    Timer tm;
+    rc = tm.start(kernel_ms != nullptr, s);
+    if (rc == SSP_OK) {
+        if (!fuse) {
+            EmBatchArgs bt = b;
+            bt.work = d_tiles;
+            hipLaunchKernelGGL(gmm_em_lse_mfma_seg_kernel, dim3((unsigned)tiles.size()), dim3(256), lds_lse, s, bt);
+        }
+        for (size_t gi = 0; gi + 1 < gstart.size(); ++gi) {
+            EmBatchArgs bg = b;
+            bg.work = d_work + wstart[gi];
+            const dim3 grid((unsigned)(wstart[gi + 1] - wstart[gi]), (unsigned)chunks);
+            switch (nct * 2 + (fuse ? 1 : 0)) {
+                case 2: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<1, false>), grid, dim3(256), lds_acc, s, bg); break;
+                case 3: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<1, true>), grid, dim3(256), lds_acc, s, bg); break;
+                case 4: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<2, false>), grid, dim3(256), lds_acc, s, bg); break;
+                case 5: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<2, true>), grid, dim3(256), lds_acc, s, bg); break;
+                case 6: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<3, false>), grid, dim3(256), lds_acc, s, bg); break;
+                default: hipLaunchKernelGGL((gmm_em_acc_mfma_seg_kernel<3, true>), grid, dim3(256), lds_acc, s, bg); break;
+            }
+            hipLaunchKernelGGL(gmm_em_reduce_seg_kernel, dim3((unsigned)((cols + 31) / 32), (unsigned)(gstart[gi + 1] - gstart[gi])), dim3(256), 0,
+                               s, b, gstart[gi], cols, fuse ? 1 : 0, d_out.as<double>());
+        }
+        if (hipGetLastError() != hipSuccess) {
+            set_error("ssp_gmm_em_stats_batch: kernel launch failed");
+            rc = SSP_ERR_HIP;
+        }
+    }
+    if (rc == SSP_OK) rc = tm.stop(s, kernel_ms);
+    if (rc != SSP_OK) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    std::vector<double> host((size_t)M * (cols + 1));
+    hipError_t he = hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "ssp_gmm_em_stats_batch: result copy failed: %s", hipGetErrorString(he));
+    for (int m = 0; m < M; ++m) {
+        const double* o = host.data() + (size_t)m * (cols + 1);
+        for (int k = 0; k < K; ++k) {
+            const double* r = o + (size_t)k * W;
+            for (int d = 0; d < D; ++d) {
+                sx_out[((size_t)m * K + k) * D + d] = r[d];
+                sxx_out[((size_t)m * K + k) * D + d] = r[D + d];
+            }
+            nk_out[(size_t)m * K + k] = r[2 * D];
+        }
+        loglik_sum_out[m] = o[cols];
+    }
     return SSP_OK;
 }

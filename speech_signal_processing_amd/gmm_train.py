@@ -56,8 +56,8 @@ class GaussianMixture:
     def _rows(self, X, idx):
         return np.asarray(X[idx].cpu() if api._is_torch(X) else X[idx], dtype=np.float64)
 
-    def _kmeans(self, ctx, X, n, D, rng, gvar):
-        """k-means++ seeds (host, on <= 20000 sampled frames) + Lloyd on the GPU; returns the clusters' (nk, sx, sxx)."""
+    def _kmeanspp(self, X, n, D, rng):
+        """k-means++ seeds on <= 20000 sampled frames (host; the only random draws of the k-means start)"""
         K = self.n_components
         sub = self._rows(X, np.sort(rng.choice(n, size=min(n, max(20000, 50 * K)), replace=False)))
         centres = np.empty((K, D))
@@ -73,31 +73,60 @@ class GaussianMixture:
             b = int(np.argmin(pot))
             centres[k] = sub[cand[b]]
             d2 = np.minimum(d2, dc[:, b])
-        tau = np.full((K, D), max(1e-2 * float(gvar.mean()), 1e-12))  # hard-assignment limit of the E step
-        w = np.full(K, 1.0 / K)
+        return centres
+
+    @staticmethod
+    def _lloyd_start(K, D, gvar):
+        """(weights, spherical variances) of the Lloyd passes: the hard-assignment limit of the E step"""
+        return np.full(K, 1.0 / K), np.full((K, D), max(1e-2 * float(gvar.mean()), 1e-12))
+
+    @staticmethod
+    def _lloyd_update(st, centres, gvar):
+        """one Lloyd step from the statistics at `centres` -> (new centres, done)"""
+        nk = np.maximum(st["nk"], 1e-12)
+        new = np.where(st["nk"][:, None] > 0.5, st["sx"] / nk[:, None], centres)  # an empty cluster keeps its centre
+        shift = float(((new - centres) ** 2).sum())
+        return new, shift <= 1e-4 * float(gvar.sum())
+
+    def _kmeans(self, ctx, X, n, D, rng, gvar):
+        """k-means++ seeds (host, on <= 20000 sampled frames) + Lloyd on the GPU; returns the clusters' (nk, sx, sxx)."""
+        K = self.n_components
+        centres = self._kmeanspp(X, n, D, rng)
+        w, tau = self._lloyd_start(K, D, gvar)
         st = None
         for _ in range(30):
             st = api.gmm_em_stats(ctx, w, centres, tau, X)
-            nk = np.maximum(st["nk"], 1e-12)
-            new = np.where(st["nk"][:, None] > 0.5, st["sx"] / nk[:, None], centres)  # an empty cluster keeps its centre
-            shift = float(((new - centres) ** 2).sum())
-            centres = new
-            if shift <= 1e-4 * float(gvar.sum()):
+            centres, done = self._lloyd_update(st, centres, gvar)
+            if done:
                 break
         return st, centres
 
+    def _need_start(self):
+        return self.means_init is None or self.precisions_init is None or self.weights_init is None
+
+    def _global_var(self, g, n):
+        """global variance (+ reg_covar) from the K = 1 statistics with unit responsibilities"""
+        mu = g["sx"][0] / n
+        return np.maximum(g["sxx"][0] / n - mu * mu, 0.0) + self.reg_covar
+
     def _initial(self, ctx, X, n, D, rng):
         K = self.n_components
-        need = self.means_init is None or self.precisions_init is None or self.weights_init is None
-        gvar = None
-        st = centres = None
-        if need:
+        gvar = g = None
+        st = centres = drawn = None
+        if self._need_start():
             # global variance through the same kernels: one component with unit responsibilities
             g = api.gmm_em_stats(ctx, np.ones(1), np.zeros((1, D)), np.ones((1, D)), X)
-            mu = g["sx"][0] / n
-            gvar = np.maximum(g["sxx"][0] / n - mu * mu, 0.0) + self.reg_covar
+            gvar = self._global_var(g, n)
             if self.init_params == 'kmeans' and K > 1:
                 st, centres = self._kmeans(ctx, X, n, D, rng, gvar)
+        if self.means_init is None and centres is None and K != 1:
+            drawn = self._rows(X, np.sort(rng.choice(n, size=K, replace=False)))
+        return self._start(n, D, g, gvar, st, centres, drawn)
+
+    def _start(self, n, D, g, gvar, st, centres, drawn):
+        """the initial (weights, means, covars) from the given *_init arrays, else the k-means clusters (st, centres), the frames
+        drawn for 'random_from_data' and the global statistics g / variance gvar"""
+        K = self.n_components
         if self.means_init is not None:
             means = np.array(self.means_init, dtype=np.float64).reshape(K, D)
         elif centres is not None:
@@ -105,7 +134,7 @@ class GaussianMixture:
         elif K == 1:
             means = (g["sx"][0] / n)[None]
         else:
-            means = self._rows(X, np.sort(rng.choice(n, size=K, replace=False)))
+            means = drawn
         if self.precisions_init is not None:
             covars = 1.0 / np.array(self.precisions_init, dtype=np.float64).reshape(K, D)
         elif st is not None:  # per-cluster variances (sklearn: _estimate_gaussian_covariances_diag of the one-hot resp)
@@ -173,3 +202,180 @@ class GaussianMixture:
         X = np.ascontiguousarray(X, dtype=np.float32)
         seg = api.Segments.from_lengths(ctx, [X.shape[0]])
         return float(np.asarray(sc.score(X, seg, loglik=False, scores=True, argmax=False)["scores"])[0, 0])
+
+
+def _m_step_many(nk, sx, sxx, n, reg_covar):
+    """GaussianMixture._m_step over a batch of models, element for element the same float64 operations: nk (B,K), sx / sxx (B,K,D),
+    n (B,) frames per model."""
+    nk = nk + 10 * np.finfo(np.float64).eps
+    means = sx / nk[:, :, None]
+    avg_X2 = sxx / nk[:, :, None]
+    covars = avg_X2 - 2 * (means * sx / nk[:, :, None]) + means ** 2 + reg_covar
+    weights = nk / n[:, None]
+    return weights / weights.sum(axis=1, keepdims=True), means, covars
+
+
+def _per_model(v, M, base_ndim):
+    """an *_init argument of fit_many: None, one array for every model, or a sequence of M arrays -> list of M"""
+    if v is None:
+        return [None] * M
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim == base_ndim + 1 and a.shape[0] == M:
+        return [a[m] for m in range(M)]
+    return [v] * M
+
+
+def _host_f32(X):
+    if api._is_torch(X):
+        X = X.detach().cpu().numpy()
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2:
+        raise ValueError("X must be (n_samples, n_features)")
+    return X
+
+
+def fit_many(Xs, n_components=1, profile=None, **kwargs):
+    """Fit one GaussianMixture per array of ``Xs`` (the per-speaker loop of GMM_UBM.py:154-170) with ONE ssp_gmm_em_stats_batch call
+    per iteration for all models still running; returns the fitted GaussianMixture objects in the order of ``Xs``.
+
+    ``kwargs`` are the constructor's; ``weights_init`` / ``means_init`` / ``precisions_init`` may be one array or a sequence of M.
+    The features go to the device once.  Every stage is batched over the models (and ``n_init`` starts) still active: the global
+    variance pass, Lloyd with per-model stop tests, EM with per-model convergence and best-start selection.  k-means++ seeding stays on
+    the host: an int or None ``random_state`` gives every model its own RandomState (as a loop of ``fit`` does; the seeding then runs in
+    a thread pool), a shared RandomState instance is drawn from in model order, as the loop draws.  For K <= 64, D <= 47 the fitted
+    attributes are bit for bit those of ``GaussianMixture(**kwargs).fit(X)`` per model.  D > 47: the loop of ``fit``.
+    ``profile``: a dict that receives the time split (kernel ms, host M step, k-means++ seconds; measurement only)."""
+    import time
+    Xs = list(Xs)
+    M = len(Xs)
+    if M == 0:
+        return []
+    inits = {name: _per_model(kwargs.pop(name, None), M, nd)
+             for name, nd in (("weights_init", 1), ("means_init", 2), ("precisions_init", 2))}
+    gms = [GaussianMixture(n_components=n_components, weights_init=inits["weights_init"][m], means_init=inits["means_init"][m],
+                           precisions_init=inits["precisions_init"][m], **kwargs) for m in range(M)]
+    hosts = [_host_f32(X) for X in Xs]
+    D = int(hosts[0].shape[1])
+    K = gms[0].n_components
+    for X in hosts:
+        if X.shape[1] != D:
+            raise ValueError("every X must have the same number of features")
+        if X.shape[0] < K:
+            raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, X.shape[0]))
+    if 2 * D + 1 > 96:  # no batched kernel (ssp_gmm_em_stats_batch: D <= 47)
+        return [gm.fit(X) for gm, X in zip(gms, hosts)]
+    g0 = gms[0]
+    ctx = g0._ctx or api.default_context()
+    ns = np.array([X.shape[0] for X in hosts], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    import torch
+    feats = torch.from_numpy(np.concatenate(hosts)).to("cuda:%d" % ctx.device)
+    torch.cuda.synchronize()
+    prof = profile if profile is not None else {}
+    for k in ("kernel_ms", "mstep_s", "kmeanspp_s", "calls", "em_iters"):
+        prof.setdefault(k, 0.0)
+    timing = profile is not None
+
+    def stats(w, mu, cv, models):
+        st = api.gmm_em_stats_batch(ctx, w, mu, cv, feats, offs[models], ns[models], timing=timing)
+        prof["kernel_ms"] += st.get("kernel_ms", 0.0)
+        prof["calls"] += 1
+        return st
+
+    # ---- global variance of every model that needs a start (K = 1, unit responsibilities)
+    g_st, gvar = [None] * M, [None] * M
+    need = [m for m in range(M) if gms[m]._need_start()]
+    if need:
+        B = len(need)
+        st = stats(np.ones((B, 1)), np.zeros((B, 1, D)), np.ones((B, 1, D)), np.array(need))
+        for i, m in enumerate(need):
+            g_st[m] = {"nk": st["nk"][i], "sx": st["sx"][i], "sxx": st["sxx"][i], "loglik_sum": float(st["loglik_sum"][i])}
+            gvar[m] = gms[m]._global_var(g_st[m], int(ns[m]))
+    # ---- the random draws of every start, model by model and start by start (what a loop of fit draws, in its order)
+    items = [(m, r) for m in range(M) for r in range(gms[m].n_init)]
+    seeds = {}
+
+    def draw(m):
+        gm, X, n = gms[m], hosts[m], int(ns[m])
+        rs = gm.random_state
+        rng = rs if isinstance(rs, np.random.RandomState) else np.random.RandomState(rs)
+        out = []
+        for _ in range(gm.n_init):
+            centres = drawn = None
+            if gm._need_start() and gm.init_params == 'kmeans' and K > 1:
+                centres = gm._kmeanspp(X, n, D, rng)
+            if gm.means_init is None and centres is None and K != 1:
+                drawn = gm._rows(X, np.sort(rng.choice(n, size=K, replace=False)))
+            out.append((centres, drawn))
+        return out
+
+    t0 = time.perf_counter()
+    shared = any(isinstance(gm.random_state, np.random.RandomState) for gm in gms)
+    if shared or M == 1:
+        drawn_all = [draw(m) for m in range(M)]
+    else:
+        import os
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, M))) as ex:
+            drawn_all = list(ex.map(draw, range(M)))
+    prof["kmeanspp_s"] += time.perf_counter() - t0
+    for m, r in items:
+        seeds[(m, r)] = drawn_all[m][r]
+    # ---- Lloyd on every k-means start at once, each with its own stop test
+    lloyd = {it: None for it in items if seeds[it][0] is not None}
+    cen = {it: seeds[it][0] for it in lloyd}
+    active = list(lloyd)
+    for _ in range(30):
+        if not active:
+            break
+        ws, taus = zip(*(GaussianMixture._lloyd_start(K, D, gvar[m]) for m, _r in active))
+        st = stats(np.stack(ws), np.stack([cen[it] for it in active]), np.stack(taus), np.array([m for m, _r in active]))
+        still = []
+        for i, it in enumerate(active):
+            sti = {"nk": st["nk"][i], "sx": st["sx"][i], "sxx": st["sxx"][i], "loglik_sum": float(st["loglik_sum"][i])}
+            lloyd[it] = sti
+            cen[it], done = GaussianMixture._lloyd_update(sti, cen[it], gvar[it[0]])
+            if not done:
+                still.append(it)
+        active = still
+    # ---- starts, then EM on every start of every model at once
+    par = {}
+    for it in items:
+        m = it[0]
+        centres = cen.get(it)
+        par[it] = gms[m]._start(int(ns[m]), D, g_st[m], gvar[m], lloyd.get(it), centres, seeds[it][1])
+    state = {it: [-np.inf, False, 0] for it in items}  # lower bound, converged, n_iter
+    tol, reg, max_iter = g0.tol, g0.reg_covar, g0.max_iter
+    active = list(items)
+    for n_iter in range(1, max_iter + 1):
+        if not active:
+            break
+        models = np.array([m for m, _r in active])
+        st = stats(np.stack([par[it][0] for it in active]), np.stack([par[it][1] for it in active]),
+                   np.stack([par[it][2] for it in active]), models)
+        prof["em_iters"] += 1
+        t0 = time.perf_counter()
+        n_act = ns[models].astype(np.float64)
+        w, mu, cv = _m_step_many(st["nk"], st["sx"], st["sxx"], n_act, reg)
+        lower = st["loglik_sum"] / n_act
+        prof["mstep_s"] += time.perf_counter() - t0
+        still = []
+        for i, it in enumerate(active):
+            par[it] = (w[i], mu[i], cv[i])
+            prev = state[it][0]
+            state[it] = [float(lower[i]), False, n_iter]
+            if abs(state[it][0] - prev) < tol:
+                state[it][1] = True
+            else:
+                still.append(it)
+        active = still
+    for m, gm in enumerate(gms):
+        best = None
+        for r in range(gm.n_init):
+            lower, converged, n_iter = state[(m, r)]
+            if best is None or lower > best[0]:
+                best = (lower, *par[(m, r)], n_iter, converged)
+        gm.lower_bound_, gm.weights_, gm.means_, gm.covariances_, gm.n_iter_, gm.converged_ = best
+        gm.precisions_cholesky_ = 1.0 / np.sqrt(gm.covariances_)
+        gm.precisions_ = gm.precisions_cholesky_ ** 2
+    return gms
