@@ -168,6 +168,17 @@ int ssp_mfcc_run(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_
  * slice by slice through the same ring. */
 int ssp_mfcc_run_i16(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg,
                      const int16_t* samples, float* feats_out, int where, int variant, float* kernel_ms);
+/* ssp_mfcc_run_list: the same pass on a LIST of host arrays, one per utterance, as the reference's callers hold them
+ * (GMM_UBM.py:72-118 extract_feature, d_vector.py:80-98), without first concatenating them on the host.  utt: HOST array of n pointers
+ * (n = sample_seg's count); utterance u is sample_seg's length u of sample_type 0 float32 | 1 int16, read straight from the caller's
+ * (pageable or pinned) arrays; a null pointer only for a zero-length utterance.  feats_out: HOST, contiguous (total frames x d_out) of
+ * out_type 0 float32 | 1 float64 (widened exactly).  sample_seg must start at sample 0 and frame_seg at frame 0.  Same kernels, same
+ * slicing and one-piece / ring decisions as ssp_mfcc_run / ssp_mfcc_run_i16 on the concatenation of the list: bit-identical features.
+ * Worker threads (SSP_HOST_THREADS, default min(8, hardware threads), at most 16; they make no HIP call) gather the utterances into
+ * pinned slots kept on the ctx — slice i + 1 while slice i copies and computes — and copy or widen the features out of pinned slots.
+ * A bad argument answers SSP_ERR_INVALID before any GPU work. */
+int ssp_mfcc_run_list(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg, const void* const* utt,
+                      int sample_type, void* feats_out, int out_type, int variant, float* kernel_ms);
 
 /* ---- stand-alone framing and cepstrum steps of the in-repo dialect (kept for API parity; ssp_mfcc_run fuses them) ---- */
 /* utils.processing.enframe (utils/processing.py:19-38): frame i = x[i*step : i*step+frame_size], zero padded tail, times
@@ -232,6 +243,14 @@ int ssp_gmm_destroy(ssp_gmm* gmm);
  * Without loglik_out the per-utterance means are formed inside the scoring kernel (the [n_models x frames] matrix never exists). */
 int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_seg, float* loglik_out,
                   float* scores_out, int32_t* argmax_out, int where, int precision, float* kernel_ms);
+/* ssp_gmm_score_list: the scoring loops GMM_UBM.py:181-197 on a LIST of per-utterance feature matrices, without the host's vstack and
+ * astype.  rows: HOST array of n pointers (n = frame_seg's count) to (T_u x dim) row-major matrices of row_type 0 float32 | 1 float64
+ * (narrowed to float32 on the host, round to nearest, as numpy's astype does); T_u from frame_seg, which starts at frame 0 and belongs
+ * to the gmm's ctx; a null pointer only for T_u = 0.  dim: the D the gmm was packed with (the caller's promise, as feats' size is
+ * ssp_gmm_score's).  Worker threads gather the rows into a pinned buffer kept on the ctx; ssp_gmm_score(SSP_HOST) then scores it:
+ * scores_out / argmax_out as there, bit for bit, every precision.  A bad argument answers SSP_ERR_INVALID before any GPU work. */
+int ssp_gmm_score_list(ssp_gmm* gmm, const void* const* rows, int row_type, int32_t dim, const ssp_segments* frame_seg,
+                       float* scores_out, int32_t* argmax_out, int precision, float* kernel_ms);
 /* utterances the last precision = 1 call scored again on the fp32 path (diagnostics) */
 int ssp_gmm_last_rescored(const ssp_gmm* gmm, int32_t* n_out);
 /* precision = 4 (auto; GMM_UBM.py:183-187's arg-max with the fp32 path's result on every utterance, never dearer than the cheaper of the

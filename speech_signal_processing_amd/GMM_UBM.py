@@ -52,11 +52,10 @@ def extract_feature(x, y, is_train=False, feature_type='MFCC', fs=16000, delta_o
             train_data[lab] = np.vstack((train_data[lab], f)) if lab in train_data else f
         return train_data, feature, y
     plan = _feature_plan(feature_type, int(fs), int(delta_order))
-    flat, lens = api.flatten_signals(x)   # (int16 PCM — what load_data reads, GMM_UBM.py:24-50 — goes to the device as int16)
-    seg = api.Segments.from_lengths(plan.ctx, lens)
-    fseg = plan.frame_segments(seg)
-    feats = np.asarray(plan.run(flat, seg, fseg), dtype=np.float64)
-    feature = [feats[fseg.offsets[i]:fseg.offsets[i + 1]] for i in range(len(lens))]
+    # the utterances are read from their own arrays (int16 PCM — what load_data reads, GMM_UBM.py:24-50 — goes to the device as int16)
+    # and the float64 features are written by the library: no concatenation or widening pass here
+    feats, fseg = api.mfcc_run_list(plan, x, out_dtype=np.float64)
+    feature = [feats[fseg.offsets[i]:fseg.offsets[i + 1]] for i in range(fseg.n)]
     if not is_train:
         return feature, y
     train_data = {}
@@ -83,9 +82,7 @@ def score_matrix(models, ubm, feats):
     means_, covariances_).  feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64)."""
     ctx = api.default_context()
     scorer = api.GmmScorer.from_sklearn(ctx, models, ubm)
-    fseg = api.Segments.from_lengths(ctx, [len(f) for f in feats])
-    flat = np.ascontiguousarray(np.vstack(feats), dtype=np.float32) if len(feats) else np.zeros((0, scorer.D), np.float32)
-    r = scorer.score(flat, fseg, scores=True, argmax=True)
+    r = scorer.score_list(feats)   # (the rows are gathered and narrowed by the library: no vstack + astype here)
     sc = np.asarray(r["scores"], dtype=np.float64)
     return sc[:, 1:] - sc[:, :1], np.asarray(r["argmax"]).astype(np.int64)
 

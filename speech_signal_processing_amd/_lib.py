@@ -63,6 +63,7 @@ SIGNATURES = {
     "ssp_mfcc_frame_segments": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "ssp_mfcc_run": (C.c_int, [_P, _P, _P, _F32P, _F32P, C.c_int, C.c_int, _MSP]),
     "ssp_mfcc_run_i16": (C.c_int, [_P, _P, _P, _F32P, _F32P, C.c_int, C.c_int, _MSP]),
+    "ssp_mfcc_run_list": (C.c_int, [_P, _P, _P, _P, C.c_int, _F32P, C.c_int, C.c_int, _MSP]),
     "ssp_enframe": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int, _MSP]),
     "ssp_cepstrum": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, C.c_int32, _F32P, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, _F32P, C.c_int, _MSP]),
@@ -73,6 +74,7 @@ SIGNATURES = {
     "ssp_gmm_pack": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(_P)]),
     "ssp_gmm_destroy": (C.c_int, [_P]),
     "ssp_gmm_score": (C.c_int, [_P, _F32P, _P, _F32P, _F32P, _P, C.c_int, C.c_int, _MSP]),
+    "ssp_gmm_score_list": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, _F32P, _P, C.c_int, _MSP]),
     "ssp_gmm_last_rescored": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "ssp_gmm_em_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, C.c_int, _MSP]),
     "ssp_gmm_em_stats_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, _P, _P,

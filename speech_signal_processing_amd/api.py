@@ -306,6 +306,58 @@ def flatten_signals(signals):
     return (np.concatenate(sig) if sig else np.zeros(0, dtype=np.float32)), [s.shape[0] for s in sig]
 
 
+def list_table(arrays, kind="samples"):
+    """The pointer table of a list-fed call (ssp_mfcc_run_list / ssp_gmm_score_list) -> (table np.uintp[n], kept arrays, element type).
+
+    kind "samples": 1-D utterances after reshape(-1), with flatten_signals' dtype rule (all int16 -> int16, type 1; anything else float32
+    per array, type 0).  kind "rows": 2-D feature matrices as np.vstack(...).astype(float32) would stack them (float32 -> type 0, float64 ->
+    type 1 and narrowed by the library; any other common type is converted to it per array, then to float32 here).  A non-contiguous
+    array is made contiguous for that array alone.  The kept arrays own the memory the table points into: hold them until the call
+    returns."""
+    if kind == "samples":
+        keep = [np.asarray(a).reshape(-1) for a in arrays]
+        if keep and all(a.dtype == np.int16 for a in keep):
+            typ = 1
+            keep = [np.ascontiguousarray(a) for a in keep]
+        else:
+            typ = 0
+            keep = [np.ascontiguousarray(a, dtype=np.float32) for a in keep]
+    elif kind == "rows":
+        keep = [np.asarray(a) for a in arrays]
+        rt = np.result_type(*{a.dtype for a in keep}) if keep else np.dtype(np.float32)   # (dtypes, not arrays: any count)
+        if rt == np.float64:
+            typ = 1
+        else:
+            typ = 0
+            if rt != np.float32:   # (vstack promotes to the common type first, then astype rounds once)
+                keep = [np.asarray(a, dtype=rt).astype(np.float32) for a in keep]
+        keep = [np.ascontiguousarray(a, dtype=np.float64 if typ else np.float32) for a in keep]
+    else:
+        raise ValueError("kind must be 'samples' or 'rows'")
+    # (__array_interface__ costs a fraction of .ctypes.data per array: thousands of utterances make that visible)
+    table = np.fromiter((a.__array_interface__["data"][0] for a in keep), dtype=np.uintp, count=len(keep))
+    return table, keep, typ
+
+
+def mfcc_run_list(plan: "MfccPlan", signals, out_dtype=np.float64, timing: bool = False):
+    """The MFCC pass on a list of 1-D utterances, read by the library from each array as it is (ssp_mfcc_run_list: no concatenation on
+    the host; pinned slots filled by worker threads).  The same bits as plan.run(*flatten_signals(signals)) widened to out_dtype
+    (float32 or float64).  Returns (feats (sum T_i, d_out), frame Segments) [and kernel milliseconds when timing=True]."""
+    out_dtype = np.dtype(out_dtype)
+    if out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("out_dtype must be float32 or float64")
+    table, keep, typ = list_table(signals, "samples")
+    seg = Segments.from_lengths(plan.ctx, [a.shape[0] for a in keep])
+    fseg = plan.frame_segments(seg)
+    out = np.empty((fseg.total, plan.d_out), dtype=out_dtype)
+    ms = C.c_float(0.0)
+    with plan.ctx._ordered(_lib.HOST):
+        _lib.check(plan._lib.ssp_mfcc_run_list(plan._h, seg._h, fseg._h, table.ctypes.data if table.size else None, typ, out.ctypes.data,
+                                               1 if out_dtype == np.float64 else 0, 0, C.byref(ms) if timing else None))
+    del keep   # (held until the call has returned)
+    return (out, fseg, ms.value) if timing else (out, fseg)
+
+
 def pinned_empty(shape, dtype=np.float32):
     """a numpy array over page-locked host memory (torch's pinned allocator = hipHostMalloc): host-fed calls copy from / to such arrays
     asynchronously and at the full PCIe rate; the array keeps its tensor alive"""
@@ -528,6 +580,29 @@ class GmmScorer:
             res["scores"] = sc
         if argmax:
             res["argmax"] = am
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def score_list(self, feats_list, precision: int = 0, timing: bool = False) -> dict:
+        """score() on a list of (T_j, D) feature matrices without stacking them on the host (ssp_gmm_score_list: the rows are gathered
+        and narrowed to float32 into pinned memory by worker threads): the same bits as score(np.vstack(feats_list).astype(float32),
+        ...) with scores=True, argmax=True.  Returns a dict with scores (U, M) and argmax (U,) [and kernel_ms]."""
+        if precision == "auto":
+            precision = 4
+        table, keep, typ = list_table(feats_list, "rows")
+        for a in keep:
+            if a.ndim != 2 or a.shape[1] != self.D:
+                raise ValueError("every feature matrix must be (frames, %d)" % self.D)
+        fseg = Segments.from_lengths(self.ctx, [a.shape[0] for a in keep])
+        sc = np.empty((fseg.n, self.n_models), dtype=np.float32)
+        am = np.empty((fseg.n,), dtype=np.int32)
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(_lib.HOST):
+            _lib.check(self._lib.ssp_gmm_score_list(self._h, table.ctypes.data if table.size else None, typ, self.D, fseg._h,
+                                                     sc.ctypes.data, am.ctypes.data, int(precision), C.byref(ms) if timing else None))
+        del keep
+        res = {"scores": sc, "argmax": am}
         if timing:
             res["kernel_ms"] = ms.value
         return res

@@ -1,4 +1,5 @@
 // Host side of the MFCC pass: plan (device tables), framing rules, chunk work table, launch.
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 
@@ -577,12 +578,40 @@ static int run_launch(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
     return SSP_OK;
 }
 
+// List-fed host operands (ssp_mfcc_run_list): utterance u's samples are read from utt[u], the features go to a float32 (out_type 0) or
+// float64 (1) host array.  The batch's decisions (slices, one piece or ring, kernels) are those of the flat call on the concatenation;
+// only the host end of each copy changes: the caller's arrays are gathered into pinned memory, and features leave pinned memory, by
+// the pipe's copying threads.
+struct ListFeed {
+    const void* const* utt;
+    int out_type;
+};
+// utterances [u0, u1) to dst (their samples contiguous, esz bytes each)
+static void gather_pieces(std::vector<CopyPiece>& v, const ListFeed& l, const std::vector<int64_t>& so, int64_t u0, int64_t u1, size_t esz, void* dst) {
+    for (int64_t u = u0; u < u1; ++u) {
+        const size_t len = (size_t)(so[(size_t)u + 1] - so[(size_t)u]);
+        if (len) add_pieces(v, l.utt[u], static_cast<char*>(dst) + (size_t)(so[(size_t)u] - so[(size_t)u0]) * esz, len * esz, COPY_BYTES);
+    }
+}
+// `n` floats of features from pinned `src` to the caller's array from element `at` on
+static void scatter_pieces(std::vector<CopyPiece>& v, const ListFeed& l, const float* src, void* out, size_t at, size_t n) {
+    if (l.out_type == 1)
+        add_pieces(v, src, static_cast<double*>(out) + at, n, COPY_F32_TO_F64);
+    else
+        add_pieces(v, src, static_cast<float*>(out) + at, n * sizeof(float), COPY_BYTES);
+}
+static double host_ms_since(const std::chrono::steady_clock::time_point& t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // Large host-fed batches (and int16 input from either side): the batch goes through the ctx's ring of slice-sized slots — slice i + 1
 // copies in while slice i computes and slice i - 1's features copy back (HostPipe, staging.hpp).  Slices are runs of whole utterances of
 // about `slice_bytes` of fp32 samples (an utterance longer than that is a slice of its own).  host_in / host_out: where the operand
 // lives (int16 device input with device output only widens through the ring; nothing is copied).
+// list (host only): the samples of slice i + 1 are gathered into its pinned slot while slice i copies and computes, and slice i - 1's
+// features leave their pinned slot after that; feats_out is then the caller's float32 / float64 array.
 static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg, const void* samples, int stype,
-                      float* feats_out, bool host, size_t slice_bytes, float* kernel_ms) {
+                      void* feats_out, bool host, size_t slice_bytes, float* kernel_ms, const ListFeed* list) {
     ssp_ctx* ctx = plan->ctx;
     hipStream_t cs = ctx->stream;
     const int64_t n = frame_seg->n, D = plan->d_out;
@@ -603,8 +632,38 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
         }
     }
     const int n_slices = (int)cut.size() - 1;
-    SSP_TRY(pipe_reserve(ctx, max_in * 4 + 4096, stype == 1 && host ? max_in * 2 + 64 : 0, host ? max_out * 4 + 16 : 0));
+    const size_t esz = stype == 1 ? sizeof(int16_t) : sizeof(float);
+    SSP_TRY(pipe_reserve(ctx, max_in * 4 + 4096, stype == 1 && host ? max_in * 2 + 64 : 0, host ? max_out * 4 + 16 : 0,
+                         list ? max_in * esz + 64 : 0, list ? max_out * 4 + 16 : 0));
     HostPipe& hp = *ctx->pipe;
+    CopyPool* pool = list ? &pipe_pool(ctx) : nullptr;
+    std::vector<CopyPiece> pieces;
+    double gather_ms = 0.0, scatter_ms = 0.0, wait_ms = 0.0;   // (list: host time of the copying threads' runs, and of the waits for copy-backs)
+    // gathers slice i into its pinned slot, once the slot's last copy-in (slice i - RING's) has ended
+    auto gather = [&](int i) -> int {
+        const int k = i % HostPipe::RING;
+        if (i >= HostPipe::RING) SSP_HIP(hipEventSynchronize(hp.in_ready[k]));
+        const auto t0 = std::chrono::steady_clock::now();
+        pieces.clear();
+        gather_pieces(pieces, *list, so, cut[(size_t)i], cut[(size_t)i + 1], esz, hp.pin_in[k].p);
+        run_pieces(*pool, pieces);
+        gather_ms += host_ms_since(t0);
+        return SSP_OK;
+    };
+    // slice i's features from its pinned slot to the caller's array, once they have been copied back
+    auto scatter = [&](int i) -> int {
+        const int k = i % HostPipe::RING;
+        const int64_t f0 = fo[(size_t)cut[(size_t)i]], nf = fo[(size_t)cut[(size_t)i + 1]] - f0;
+        auto t0 = std::chrono::steady_clock::now();
+        SSP_HIP(hipEventSynchronize(hp.out_done[k]));
+        wait_ms += host_ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        pieces.clear();
+        scatter_pieces(pieces, *list, hp.pin_out[k].as<float>(), feats_out, (size_t)(f0 - fo[0]) * (size_t)D, (size_t)nf * (size_t)D);
+        run_pieces(*pool, pieces);
+        scatter_ms += host_ms_since(t0);
+        return SSP_OK;
+    };
     // SSP_HOST_TRACE=1 (diagnostic): per slice, when its copy-in, its kernels and its copy-back ended (ms from the call's start, stderr)
     const bool trace = getenv("SSP_HOST_TRACE") != nullptr;
     EventSet tev;   // (3 a slice, then the call's start)
@@ -614,17 +673,18 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
         SSP_TRY(plan->f_counter.reserve(64 + (size_t)std::max(plan->cache_n_chunks, 1) * sizeof(int32_t)));
     SSP_TRY(tm.start(kernel_ms != nullptr, cs));
     SSP_TRY(hp.start(cs));
-    const size_t esz = stype == 1 ? sizeof(int16_t) : sizeof(float);
     const size_t t_start = (size_t)n_slices * 3;
     if (trace) {
         SSP_TRY(tev.create(t_start + 1));
         SSP_HIP(hipEventRecord(tev[t_start], cs));
     }
+    if (list) SSP_TRY(gather(0));
     for (int i = 0; i < n_slices; ++i) {
         const int k = i % HostPipe::RING;
         const int64_t u0 = cut[(size_t)i], u1 = cut[(size_t)i + 1];
         const int64_t s0 = so[(size_t)u0], ns = so[(size_t)u1] - s0, f0 = fo[(size_t)u0], nf = fo[(size_t)u1] - f0;
-        const char* src = static_cast<const char*>(samples) + (size_t)(s0 - so[0]) * esz;   // (the caller's array starts at the first utterance's first sample)
+        const char* src = list ? hp.pin_in[k].as<const char>()   // (gathered: the slot holds the slice alone)
+                               : static_cast<const char*>(samples) + (size_t)(s0 - so[0]) * esz;   // (the caller's array starts at the first utterance's first sample)
         float* d_in = hp.in[k].as<float>();
         if (host) {
             // slot k's last reader was slice i - RING.  The HOST waits for it (it runs at most RING slices ahead, and the call is synchronous
@@ -640,16 +700,21 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
         } else {
             SSP_TRY(launch_widen_i16(reinterpret_cast<const int16_t*>(src), d_in, ns, cs));   // (in-order on cs: slot k's last reader is long done)
         }
-        float* d_o = host ? hp.out[k].as<float>() - (size_t)(f0 - fo[0]) * (size_t)D : feats_out;
+        float* d_o = host ? hp.out[k].as<float>() - (size_t)(f0 - fo[0]) * (size_t)D : static_cast<float*>(feats_out);
         // pointers biased by the slice's first offsets: the kernels address with the batch's absolute offsets (run_launch)
         SSP_TRY(run_launch(plan, sample_seg, frame_seg, d_in - (size_t)(s0 - so[0]), d_o, u0, u1, cs));
         if (host) {
             SSP_HIP(hipEventRecord(hp.computed[k], cs));
             if (trace) SSP_HIP(hipEventRecord(tev[(size_t)i * 3 + 1], cs));
             SSP_HIP(hipStreamWaitEvent(hp.d2h, hp.computed[k], 0));
-            SSP_HIP(hipMemcpyAsync(feats_out + (size_t)(f0 - fo[0]) * (size_t)D, hp.out[k].p, (size_t)nf * (size_t)D * sizeof(float), hipMemcpyDeviceToHost, hp.d2h));
+            void* dst = list ? hp.pin_out[k].p : (void*)(static_cast<float*>(feats_out) + (size_t)(f0 - fo[0]) * (size_t)D);
+            SSP_HIP(hipMemcpyAsync(dst, hp.out[k].p, (size_t)nf * (size_t)D * sizeof(float), hipMemcpyDeviceToHost, hp.d2h));
             SSP_HIP(hipEventRecord(hp.out_done[k], hp.d2h));
             if (trace) SSP_HIP(hipEventRecord(tev[(size_t)i * 3 + 2], hp.d2h));
+        }
+        if (list) {   // (the next slice's gather overlaps this slice's copies and kernels; the previous slice's copy-back has had them too)
+            if (i + 1 < n_slices) SSP_TRY(gather(i + 1));
+            if (i >= 1) SSP_TRY(scatter(i - 1));
         }
     }
     if (host) {   // the ctx stream ends behind the last copy-back (one stream to wait on, for this call and for whoever comes next)
@@ -657,9 +722,13 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
     }
     SSP_TRY(tm.stop(cs, kernel_ms));
     if (host) SSP_HIP(hipStreamSynchronize(cs));
+    if (list) SSP_TRY(scatter(n_slices - 1));
     guard.ok = true;
     if (trace && host) {
         fprintf(stderr, "[ssp host pipeline] %d slices of <= %zu MiB (fp32); ms from start: copy-in done | kernels done | copy-back done\n", n_slices, slice_bytes >> 20);
+        if (list)
+            fprintf(stderr, "[ssp host pipeline] list: %d copying threads; host ms: gather %.3f, copy-back waits %.3f, features out %.3f\n",
+                    pool->threads(), gather_ms, wait_ms, scatter_ms);
         for (int i = 0; i < n_slices; ++i) {
             float a = 0.f, b = 0.f, c = 0.f;
             (void)hipEventElapsedTime(&a, tev[t_start], tev[(size_t)i * 3]);
@@ -672,7 +741,7 @@ static int run_sliced(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const
 }
 
 static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg, const void* samples, int stype,
-                        float* feats_out, int where, int variant, float* kernel_ms) {
+                        void* feats_out, int where, int variant, float* kernel_ms, const ListFeed* list = nullptr) {
     if (!plan || !sample_seg || !frame_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run: null handle");
     SSP_TRY(use_ctx(plan->ctx));
     if (sample_seg->n != frame_seg->n) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run: sample/frame segment counts differ");
@@ -691,9 +760,23 @@ static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, con
     const bool two_pass = plan->cache_split_topdb && (v == 1 || v == 4);   // (needs the whole batch's rows in one scratch)
     const bool big = (size_t)n_samp_total * sizeof(float) >= 2 * slice && frame_seg->n >= 2 && sample_seg->host.front() == 0 && frame_seg->host.front() == 0;
     if (!two_pass && ((where == SSP_HOST && big) || (stype == 1 && where == SSP_DEVICE && sample_seg->host.front() == 0 && frame_seg->host.front() == 0)))
-        return run_sliced(plan, sample_seg, frame_seg, samples, stype, feats_out, where == SSP_HOST, slice, kernel_ms);
+        return run_sliced(plan, sample_seg, frame_seg, samples, stype, feats_out, where == SSP_HOST, slice, kernel_ms, list);
 
-    // one piece: the operands as they are (device pointers), or staged whole through the ctx's pool (host pointers)
+    // one piece: the operands as they are (device pointers), or staged whole through the ctx's pool (host pointers; a list: through the
+    // ctx's pinned bounces, gathered before and widened / copied out after)
+    double gather_ms = 0.0, scatter_ms = 0.0;
+    std::vector<CopyPiece> pieces;
+    void* host_out = feats_out;
+    if (list) {
+        const size_t esz = stype == 1 ? sizeof(int16_t) : sizeof(float);
+        SSP_TRY(pipe_bounce(plan->ctx, (size_t)n_samp_total * esz + 16, out_bytes + 16));
+        const auto t0 = std::chrono::steady_clock::now();
+        gather_pieces(pieces, *list, sample_seg->host, 0, sample_seg->n, esz, plan->ctx->pipe->bounce_in.p);
+        run_pieces(pipe_pool(plan->ctx), pieces);
+        gather_ms = host_ms_since(t0);
+        samples = plan->ctx->pipe->bounce_in.p;
+        feats_out = plan->ctx->pipe->bounce_out.p;
+    }
     Staged sin, sout, sraw;
     int rc;
     const float* d_samples;
@@ -707,7 +790,7 @@ static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, con
         d_samples = (const float*)sin.in(plan->ctx, samples, (size_t)n_samp_total * sizeof(float), where, &rc);
         SSP_TRY(rc);
     }
-    float* d_out = (float*)sout.out(plan->ctx, feats_out, out_bytes, where, &rc);
+    float* d_out = (float*)sout.out(plan->ctx, static_cast<float*>(feats_out), out_bytes, where, &rc);
     SSP_TRY(rc);
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
@@ -715,6 +798,16 @@ static int mfcc_run_any(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, con
     SSP_TRY(tm.stop(s, kernel_ms));
     SSP_TRY(sout.back(plan->ctx, feats_out, out_bytes, where));
     if (where == SSP_HOST || stype == 1) SSP_HIP(hipStreamSynchronize(s));   // (the staging slots are given back at return)
+    if (list) {
+        const auto t0 = std::chrono::steady_clock::now();
+        pieces.clear();
+        scatter_pieces(pieces, *list, static_cast<const float*>(feats_out), host_out, 0, out_bytes / sizeof(float));
+        run_pieces(plan->ctx->pipe->pool, pieces);
+        scatter_ms = host_ms_since(t0);
+        if (getenv("SSP_HOST_TRACE"))
+            fprintf(stderr, "[ssp host pipeline] list, one piece: %d copying threads; host ms: gather %.3f, features out %.3f\n",
+                    plan->ctx->pipe->pool.threads(), gather_ms, scatter_ms);
+    }
     return SSP_OK;
 }
 
@@ -732,6 +825,26 @@ int ssp_mfcc_run_i16(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const 
                      const int16_t* samples, float* feats_out, int where, int variant, float* kernel_ms) {
     ssp::TraceRange trace_("ssp_mfcc_run_i16");
     return mfcc_run_any(plan, sample_seg, frame_seg, samples, 1, feats_out, where, variant, kernel_ms);
+}
+
+int ssp_mfcc_run_list(ssp_mfcc_plan* plan, const ssp_segments* sample_seg, const ssp_segments* frame_seg, const void* const* utt,
+                      int sample_type, void* feats_out, int out_type, int variant, float* kernel_ms) {
+    ssp::TraceRange trace_("ssp_mfcc_run_list");
+    // (every argument is checked before the ctx is touched)
+    if (!plan || !sample_seg || !frame_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: null handle");
+    if (sample_seg->n != frame_seg->n) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: sample/frame segment counts differ");
+    if (sample_seg->host.front() != 0 || frame_seg->host.front() != 0)
+        SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: segments must start at sample 0 and frame 0");
+    if (sample_type != 0 && sample_type != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: sample_type must be 0 (float32) or 1 (int16)");
+    if (out_type != 0 && out_type != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: out_type must be 0 (float32) or 1 (float64)");
+    if (sample_seg->n > 0 && !utt) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: null utterance table");
+    for (int64_t u = 0; u < sample_seg->n; ++u)
+        if (!utt[u] && sample_seg->host[(size_t)u + 1] > sample_seg->host[(size_t)u])
+            SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: null pointer for utterance %lld of %lld samples", (long long)u,
+                     (long long)(sample_seg->host[(size_t)u + 1] - sample_seg->host[(size_t)u]));
+    if (frame_seg->total() > 0 && !feats_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_run_list: null feats_out");
+    const ListFeed list{utt, out_type};
+    return mfcc_run_any(plan, sample_seg, frame_seg, utt, sample_type, feats_out, SSP_HOST, variant, kernel_ms, &list);
 }
 
 }  // extern "C"

@@ -1,7 +1,14 @@
 // Host-side staging of SSP_HOST calls (included twice by common.hpp: part 1 before ssp_ctx — the pool it holds —, part 2 behind it — the
 // per-operand helper).  No device code here: the file is deliberately NOT part of bench.py's kernel-source hash.
 #if SSP_STAGING_PART == 1
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
+#include <thread>
+#include <vector>
 namespace ssp {
 // Staging buffers of SSP_HOST calls, kept by the ctx between calls: the reference's callers loop over utterances in Python, and a
 // hipMalloc + hipFree pair per staged operand costs up to 0.7 ms each once the allocator has no small block at hand (GMM_UBM.delta
@@ -43,8 +50,158 @@ struct StagePoolT {
         return fit;
     }
 };
+
+// Host copies of the list-fed entry points (ssp_mfcc_run_list, ssp_gmm_score_list): the caller's per-utterance arrays are gathered into
+// pinned slots, and features leave pinned slots for the caller's array, in pieces of about 1 MiB that a pool of worker threads runs.
+// Workers only copy and convert: every stream and event call stays on the calling thread.
+enum { COPY_BYTES = 0, COPY_F32_TO_F64 = 1, COPY_F64_TO_F32 = 2 };
+struct CopyPiece {
+    const void* src;
+    void* dst;
+    size_t n;   // bytes (COPY_BYTES) or elements
+    int kind;
+};
+// appends the pieces of one span: n bytes (COPY_BYTES) or n elements
+static inline void add_pieces(std::vector<CopyPiece>& v, const void* src, void* dst, size_t n, int kind, size_t piece_bytes = (size_t)1 << 20) {
+    const size_t ss = kind == COPY_F64_TO_F32 ? 8 : kind == COPY_F32_TO_F64 ? 4 : 1, ds = kind == COPY_F32_TO_F64 ? 8 : kind == COPY_F64_TO_F32 ? 4 : 1;
+    const size_t per = std::max<size_t>(1, piece_bytes / std::max(ss, ds));
+    for (size_t i = 0; i < n; i += per)
+        v.push_back({static_cast<const char*>(src) + i * ss, static_cast<char*>(dst) + i * ds, std::min(per, n - i), kind});
+}
+static inline void run_piece(const CopyPiece& p) {
+    if (p.kind == COPY_BYTES) {
+        memcpy(p.dst, p.src, p.n);
+    } else if (p.kind == COPY_F32_TO_F64) {   // exact
+        const float* s = static_cast<const float*>(p.src);
+        double* d = static_cast<double*>(p.dst);
+        for (size_t i = 0; i < p.n; ++i) d[i] = (double)s[i];
+    } else {                                  // round to nearest even, as numpy's astype(float32)
+        const double* s = static_cast<const double*>(p.src);
+        float* d = static_cast<float*>(p.dst);
+        for (size_t i = 0; i < p.n; ++i) d[i] = (float)s[i];
+    }
+}
+struct CopyJob {
+    const CopyPiece* piece;
+    void operator()(size_t i) const { run_piece(piece[i]); }
+};
+// Worker threads that run the jobs of ONE caller at a time: run(n, job) calls job(0 .. n-1) once each, spread over the workers and the
+// calling thread, and returns when all have returned.  Started lazily (resize); the destructor joins the workers.
+// (a template over the job type, HIP-free, so that tests/native/gather_pool_threads.cpp can run it under ThreadSanitizer)
+template <class Job>
+struct WorkPoolT {
+    WorkPoolT() = default;
+    WorkPoolT(const WorkPoolT&) = delete;
+    WorkPoolT& operator=(const WorkPoolT&) = delete;
+    ~WorkPoolT() { stop(); }
+    int threads() const { return (int)th.size() + 1; }   // (the caller included)
+    // nthreads copying threads, the caller included; a worker that cannot be started leaves the pool smaller
+    void resize(int nthreads) {
+        if ((int)th.size() == nthreads - 1) return;
+        stop();
+        for (int i = 1; i < nthreads; ++i) {
+            try {
+                th.emplace_back([this] { loop(); });
+            } catch (...) {
+                break;
+            }
+        }
+    }
+    void run(size_t count, const Job& j) {
+        if (count == 0) return;
+        if (th.empty() || count == 1) {
+            for (size_t i = 0; i < count; ++i) j(i);
+            return;
+        }
+        {
+            std::lock_guard<std::mutex> g(mu);
+            job = &j;
+            n = count;
+            next.store(0);
+            ++gen;
+        }
+        wake.notify_all();
+        for (size_t i; (i = next.fetch_add(1)) < count;) j(i);
+        std::unique_lock<std::mutex> lk(mu);
+        idle.wait(lk, [&] { return inside == 0; });
+        job = nullptr;   // (a worker that wakes only now finds nothing to do)
+        n = 0;
+    }
+
+  private:
+    std::mutex mu;
+    std::condition_variable wake, idle;
+    std::vector<std::thread> th;
+    const Job* job = nullptr;
+    size_t n = 0;
+    std::atomic<size_t> next{0};
+    uint64_t gen = 0;
+    int inside = 0;   // workers between taking a job and giving it back
+    bool quit = false;
+    void stop() {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            quit = true;
+        }
+        wake.notify_all();
+        for (std::thread& t : th) t.join();
+        th.clear();
+        quit = false;
+    }
+    void loop() {
+        std::unique_lock<std::mutex> lk(mu);
+        uint64_t seen = gen;
+        for (;;) {
+            wake.wait(lk, [&] { return quit || gen != seen; });
+            if (quit) return;
+            seen = gen;
+            const Job* j = job;
+            const size_t cnt = n;
+            if (!j) continue;
+            ++inside;
+            lk.unlock();
+            for (size_t i; (i = next.fetch_add(1)) < cnt;) (*j)(i);
+            lk.lock();
+            if (--inside == 0) idle.notify_all();
+        }
+    }
+};
+using CopyPool = WorkPoolT<CopyJob>;
+static inline void run_pieces(CopyPool& pool, const std::vector<CopyPiece>& v) { pool.run(v.size(), CopyJob{v.data()}); }
+// copying threads of the list-fed calls, the caller included: min(8, hardware threads), SSP_HOST_THREADS overrides (1 .. 16)
+static inline int host_threads() {
+    int n = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+    if (const char* e = getenv("SSP_HOST_THREADS")) n = atoi(e);
+    return std::min(16, std::max(1, n));
+}
+
 #ifndef SSP_STAGING_NO_HIP
 using StagePool = StagePoolT<DevBuf>;
+// page-locked host buffer (hipHostMalloc): copies from / to it run asynchronously at the full PCIe rate
+struct PinBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    int alloc(size_t n) {
+        release();
+        if (n == 0) n = 16;
+        SSP_HIP(hipHostMalloc(&p, n, hipHostMallocDefault));
+        bytes = n;
+        return SSP_OK;
+    }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
+};
 // Ring of device slots that large SSP_HOST calls stream through, on two copy streams beside the ctx stream: run_sliced (mfcc_plan.hip)
 // copies slice i + 1 in while slice i computes and slice i - 1's features go back; feed_rows (below) copies rows in ahead of the scorers.
 // The ctx makes it on first use and keeps it (slots grow-only: pipe_reserve); ssp_ctx_destroy drains and frees it.
@@ -52,6 +209,10 @@ struct HostPipe {
     static constexpr int RING = 3;
     hipStream_t h2d = nullptr, d2h = nullptr;
     DevBuf in[RING], raw[RING], out[RING];          // fp32 samples | int16 samples as copied in (widened into `in`) | features
+    // list-fed calls: pinned copies of the slices' samples and features (the slot's last copy is waited for before the host writes it
+    // again: in_ready / out_done), and whole-batch pinned bounces of the one-piece paths; grow-only like the device slots
+    PinBuf pin_in[RING], pin_out[RING], bounce_in, bounce_out;
+    CopyPool pool;   // their copying threads (started on first use: pipe_pool)
     hipEvent_t in_ready[RING] = {}, computed[RING] = {}, out_done[RING] = {};
     // a call's prologue: the copy streams start behind whatever the ctx stream holds (the slots' last readers of an earlier call included)
     int start(hipStream_t cs) {
@@ -156,7 +317,7 @@ struct DrainIfFailed {
 };
 // The ctx's ring for one call, slots of at least in / raw / out bytes (0: unused).  Made on first use, all or nothing (a half-made pipe
 // is freed, the next call starts afresh).  A slot about to grow may still be read by an earlier call's work: all streams drain first.
-static inline int pipe_reserve(ssp_ctx* ctx, size_t in, size_t raw, size_t out) {
+static inline int pipe_reserve(ssp_ctx* ctx, size_t in, size_t raw, size_t out, size_t pin_in = 0, size_t pin_out = 0) {
     if (!ctx->pipe) {
         std::unique_ptr<HostPipe> p(new (std::nothrow) HostPipe);
         if (!p) SSP_FAIL(SSP_ERR_NOMEM, "host alloc (pipeline)");
@@ -171,15 +332,34 @@ static inline int pipe_reserve(ssp_ctx* ctx, size_t in, size_t raw, size_t out) 
     }
     HostPipe& hp = *ctx->pipe;
     bool grow = false;
-    for (int k = 0; k < HostPipe::RING; ++k) grow = grow || hp.in[k].bytes < in || hp.raw[k].bytes < raw || hp.out[k].bytes < out;
+    for (int k = 0; k < HostPipe::RING; ++k)
+        grow = grow || hp.in[k].bytes < in || hp.raw[k].bytes < raw || hp.out[k].bytes < out || hp.pin_in[k].bytes < pin_in ||
+               hp.pin_out[k].bytes < pin_out;
     if (!grow) return SSP_OK;
     if (!drain_pipe(ctx)) SSP_FAIL(SSP_ERR_HIP, "host pipeline: draining the streams before its slots grow failed");
     for (int k = 0; k < HostPipe::RING; ++k) {
         if (hp.in[k].bytes < in) SSP_TRY(hp.in[k].alloc(in));
         if (hp.raw[k].bytes < raw) SSP_TRY(hp.raw[k].alloc(raw));
         if (hp.out[k].bytes < out) SSP_TRY(hp.out[k].alloc(out));
+        if (hp.pin_in[k].bytes < pin_in) SSP_TRY(hp.pin_in[k].alloc(pin_in));
+        if (hp.pin_out[k].bytes < pin_out) SSP_TRY(hp.pin_out[k].alloc(pin_out));
     }
     return SSP_OK;
+}
+// The ctx's whole-batch pinned bounces (list-fed one-piece paths), at least in / out bytes; grown as the ring's slots are
+static inline int pipe_bounce(ssp_ctx* ctx, size_t in, size_t out) {
+    SSP_TRY(pipe_reserve(ctx, 0, 0, 0));
+    HostPipe& hp = *ctx->pipe;
+    if (hp.bounce_in.bytes >= in && hp.bounce_out.bytes >= out) return SSP_OK;
+    if (!drain_pipe(ctx)) SSP_FAIL(SSP_ERR_HIP, "host pipeline: draining the streams before its bounce buffers grow failed");
+    if (hp.bounce_in.bytes < in) SSP_TRY(hp.bounce_in.alloc(in));
+    if (hp.bounce_out.bytes < out) SSP_TRY(hp.bounce_out.alloc(out));
+    return SSP_OK;
+}
+// The ctx's copying threads, sized for this call (SSP_HOST_THREADS is read on every call)
+static inline CopyPool& pipe_pool(ssp_ctx* ctx) {
+    ctx->pipe->pool.resize(host_threads());
+    return ctx->pipe->pool;
 }
 struct EventSet {  // hipEvents that live as long as the holder (every return path destroys them)
     std::vector<hipEvent_t> ev;
