@@ -215,6 +215,39 @@ int ssp_cmvn(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, in
 int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segments* frame_seg, int32_t n_bands, float fmax_hz,
                  int32_t plp_order, int32_t rasta, float lift, float* ceps_out, int where, float* kernel_ms);
 
+/* ---- voice activity detection: replaces VAD.py's per-frame Python loops (enframe VAD.py:28-50, energy :67-76, ZCR :53-64,
+ *      spectrum_entropy :79-105, feature :108-119, the peak normalisation of wavdata :131) and its two detectors (VAD_detection
+ *      :136-182, VAD_frequency :185-186) for a ragged batch of utterances ---- */
+/* math.ceil(wlen / step) (VAD.py:37): the last frames run past the utterance's end and are zero padded.  No GPU. */
+int ssp_vad_num_frames(int64_t n_samples, int32_t step, int64_t* n_frames);
+/* frame segments (starting at frame 0) derived from sample segments with that rule */
+int ssp_vad_frame_segments(ssp_ctx* ctx, const ssp_segments* sample_seg, int32_t step, ssp_segments** frame_seg_out);
+/* feature (VAD.py:108-119) of every frame of every utterance in one pass: zcr_out = crossings * (power > 0.1), power_out = sum of squares,
+ * entropy_out = spectral entropy of bins 0..127 in 10 blocks of 12 (VAD.py:79-92); float[total frames] each, laid out by frame_seg.
+ * samples: sample_type 0 float32 | 1 int16 (taken at their integer value), laid out by sample_seg as ssp_mfcc_run takes them.  No window,
+ * no pre-emphasis.  normalize != 0: every utterance is divided by its peak max|x| first (wavdata, VAD.py:131; int16 widened before the
+ * abs: |-32768| = 32768); a digitally silent utterance (peak 0) gives NaN power and entropy and zcr 0, as the reference's 0 / 0 does.
+ * normalize == 0: the samples are taken as they are (the caller's frames are already in [-1, 1]).  flags: SSP_VAD_ZCR_UNGATED makes
+ * zcr_out the bare count of ZCR (VAD.py:53-64), without the power gate; other bits answer SSP_ERR_INVALID.  frame_size 256 with step 128 (the reference's frameSize / overlap) or step 256
+ * (the columns of an enframe matrix handed over as one utterance); anything else answers SSP_ERR_UNSUPPORTED.  frame_seg must hold
+ * ceil(n / step) frames per utterance.  where = SSP_HOST stages the batch whole.  One host wait per call, before the kernels are
+ * queued (the upload of the call's chunk table). */
+#define SSP_VAD_ZCR_UNGATED 1u
+int ssp_vad_features(ssp_ctx* ctx, const void* samples, int sample_type, const ssp_segments* sample_seg, const ssp_segments* frame_seg,
+                     int32_t frame_size, int32_t step, int32_t normalize, uint32_t flags, float* zcr_out, float* power_out, float* entropy_out, int where,
+                     float* kernel_ms);
+/* mode 0: VAD_detection(zcr, power, zcr_gate, ampl, amph) (VAD.py:136-182) per utterance of frame_seg, min_len = 16 in the reference
+ * (>= 1): a frame with power > amph extends the current run and opens one if none is open; any other frame flushes a run longer than
+ * min_len — start walks back and end forward while power > ampl or zcr > zcr_gate, [start, end] is marked — and leaves a shorter one
+ * OPEN (a later loud frame extends it across the gap); a run open at the last frame is never flushed.  The reference's last_end /
+ * min_distance merge can never be taken and is not implemented.  The backward walk stops at frame 0 (Python's index -1 would go on with
+ * the last frame: the same result whenever the last frame is not active).
+ * mode 1: VAD_frequency (VAD.py:185-186) on the entropy plane: 0 where entropy > ampl (0.4 in the reference), else 1; zcr, zcr_gate, amph
+ * and min_len are not read.
+ * mask_out: uint8[total frames]; n_speech_out (nullable): int32[n utterances] = marked frames per utterance. */
+int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy, const ssp_segments* frame_seg, int32_t mode, float zcr_gate,
+                   float ampl, float amph, int32_t min_len, uint8_t* mask_out, int32_t* n_speech_out, int where, float* kernel_ms);
+
 /* ---- GMM-UBM scoring: replaces the GMM[i].score(x_j) - UBM.score(x_j) double loop
  *      (GMM_UBM.py:181-197) and sklearn GaussianMixture.score_samples/score for diag models ---- */
 /* weights: HOST double[n_models x K]; means, covars: HOST double[n_models x K x D].

@@ -11,6 +11,7 @@ SSP_OK, SSP_ERR_INVALID, SSP_ERR_UNSUPPORTED, SSP_ERR_HIP, SSP_ERR_NOMEM, SSP_ER
 HOST, DEVICE = 0, 1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
+VAD_ZCR_UNGATED = 1
 
 
 class SspError(RuntimeError):
@@ -64,6 +65,10 @@ SIGNATURES = {
     "ssp_mfcc_run": (C.c_int, [_P, _P, _P, _F32P, _F32P, C.c_int, C.c_int, _MSP]),
     "ssp_mfcc_run_i16": (C.c_int, [_P, _P, _P, _F32P, _F32P, C.c_int, C.c_int, _MSP]),
     "ssp_mfcc_run_list": (C.c_int, [_P, _P, _P, _P, C.c_int, _F32P, C.c_int, C.c_int, _MSP]),
+    "ssp_vad_num_frames": (C.c_int, [C.c_int64, C.c_int32, _I64P]),
+    "ssp_vad_frame_segments": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),
+    "ssp_vad_features": (C.c_int, [_P, _F32P, C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _F32P, _F32P, _F32P, C.c_int, _MSP]),
+    "ssp_vad_detect": (C.c_int, [_P, _F32P, _F32P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, C.c_int, _MSP]),
     "ssp_enframe": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int, _MSP]),
     "ssp_cepstrum": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, C.c_int32, _F32P, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, _F32P, C.c_int, _MSP]),

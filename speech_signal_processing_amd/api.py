@@ -452,6 +452,69 @@ def plp_post(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_ord
     return (out, ms.value) if timing else out
 
 
+def vad_num_frames(n_samples: int, step: int = 128) -> int:
+    """math.ceil(n / step) — VAD.py:37 (no GPU)."""
+    out = C.c_int64()
+    _lib.check(_lib.load().ssp_vad_num_frames(int(n_samples), int(step), C.byref(out)))
+    return out.value
+
+
+def vad_frame_segments(ctx: Context, sample_seg: Segments, step: int = 128) -> Segments:
+    h = C.c_void_p()
+    _lib.check(ctx._lib.ssp_vad_frame_segments(ctx._h, sample_seg._h, int(step), C.byref(h)))
+    return Segments(ctx, _handle=h)
+
+
+def _raw_ptr(x, where):
+    return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
+
+
+def vad_features(ctx: Context, samples, sample_seg: Segments, frame_seg: Optional[Segments] = None, frame_size: int = 256, step: int = 128,
+                 normalize: bool = True, gate_zcr: bool = True, timing: bool = False):
+    """VAD.py's feature() for every frame of a ragged batch in one pass (ssp_vad_features): samples float32 or int16 PCM, flat, laid out
+    by sample_seg (numpy -> host path, torch cuda -> device path).  normalize: divide every utterance by its peak first (False: the samples are taken as
+    they are); gate_zcr=False leaves the zero-crossing count ungated (VAD.py's bare ZCR).  Returns (zcr, power, entropy, frame_seg),
+    float32[total frames] each
+    [and kernel milliseconds when timing=True]."""
+    if frame_seg is None:
+        frame_seg = vad_frame_segments(ctx, sample_seg, step)
+    keep, ptr, where, is_i16 = _as_samples(samples, "samples")
+    if int(np.prod(keep.shape)) < sample_seg.total:
+        raise ValueError("samples shorter than the segment table")
+    zcr, power, ent = (ctx._empty((frame_seg.total,), where) for _ in range(3))
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_vad_features(ctx._h, ptr, 1 if is_i16 else 0, sample_seg._h, frame_seg._h, int(frame_size), int(step),
+                                             1 if normalize else 0, 0 if gate_zcr else _lib.VAD_ZCR_UNGATED, _raw_ptr(zcr, where), _raw_ptr(power, where), _raw_ptr(ent, where),
+                                             where, C.byref(ms) if timing else None))
+    return (zcr, power, ent, frame_seg, ms.value) if timing else (zcr, power, ent, frame_seg)
+
+
+def vad_detect(ctx: Context, zcr, power_or_entropy, frame_seg: Segments, mode: int = 0, zcr_gate: float = 35.0, ampl: float = 0.3,
+               amph: float = 12.0, min_len: int = 16, timing: bool = False):
+    """mode 0: VAD_detection (VAD.py:136-182) per utterance on (zcr, power); mode 1: VAD_frequency (VAD.py:185-186) on the entropy with
+    threshold ``ampl`` (ssp_vad_detect).  Returns (mask uint8[total frames], speech frames per utterance int32[n])
+    [and kernel milliseconds when timing=True]."""
+    pk, pptr, where = _as_f32(power_or_entropy, "power_or_entropy")
+    if mode == 0:
+        zk, zptr, zwhere = _as_f32(zcr, "zcr")
+        if zwhere != where or int(np.prod(zk.shape)) < frame_seg.total:
+            raise ValueError("zcr and power must be arrays of the same kind holding every frame of frame_seg")
+    else:
+        zk, zptr = None, None
+    if int(np.prod(pk.shape)) < frame_seg.total:
+        raise ValueError("fewer values than frame_seg has frames")
+    mask = ctx._empty((frame_seg.total,), where, "uint8")
+    count = ctx._empty((frame_seg.n,), where, "int32")
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_vad_detect(ctx._h, zptr, pptr, frame_seg._h, int(mode), float(zcr_gate), float(ampl), float(amph),
+                                           int(min_len), _raw_ptr(mask, where), _raw_ptr(count, where), where,
+                                           C.byref(ms) if timing else None))
+    del zk, pk
+    return (mask, count, ms.value) if timing else (mask, count)
+
+
 def gmm_em_stats(ctx: "Context", weights, means, covars, feats, timing: bool = False) -> dict:
     """E step + M-step sums of ONE EM iteration of a diagonal GMM on the GPU (ssp_gmm_em_stats).
     weights (K,), means (K,D), covars (K,D) float64; feats (n, D) float32 (numpy or device tensor).
