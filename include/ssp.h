@@ -51,6 +51,7 @@ typedef struct ssp_segments ssp_segments;
 typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
+typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 
 /* MFCC dialect knobs.  Three presets are built by the host side:
  *   in-repo  utils/processing.py:19-144  (Hamming, |X|/L, 40 talkbox filters folded, log10(.+1e-8), c0..c12)
@@ -357,6 +358,31 @@ int ssp_dnn_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const fl
                    const int32_t* relu, ssp_dnn** out);
 int ssp_dnn_destroy(ssp_dnn* dnn);
 int ssp_dnn_forward(ssp_dnn* dnn, const float* X, int64_t N, float* Y, int where, float* kernel_ms);
+
+/* ---- d-vector recurrent network forward: the LSTM(128) whose last hidden state is the embedding (d_vector.py:271-294 inference_lstm;
+ *      spkModel.predict with the default model_name 'lstm' at d_vector.py:297-299, 330-331, 347-348).  Keras' cell, return_sequences
+ *      False, zero initial state, no mask; gate blocks in the order i | f | c | o:
+ *        z = x_t W + h_{t-1} U + b;  i = s(z_i), f = s(z_f), g = tanh(z_c), o = s(z_o);  c_t = f c_{t-1} + i g;  h_t = o tanh(c_t)
+ *      recurrent_activation names s: 0 hard_sigmoid = clip(0.2 z + 0.5, 0, 1) (stand-alone Keras <= 2.2's default) | 1 logistic sigmoid
+ *      (Keras >= 2.3, tf.keras).  The caller chooses; there is no default. ---- */
+/* W: HOST float[d_in x 4 units], U: HOST float[units x 4 units], bias: HOST float[4 units] or NULL — layer.get_weights() as it is.
+ * units: a multiple of 16 up to 128; d_in up to 64; anything else answers SSP_ERR_UNSUPPORTED (no other path exists). */
+int ssp_lstm_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, const float* U, const float* bias,
+                    int32_t recurrent_activation, ssp_lstm** out);
+int ssp_lstm_destroy(ssp_lstm* lstm);
+/* feats: float[total frames x d_in] row-major laid out by frame_seg — what ssp_mfcc_run writes; sequence s is rows
+ * [offsets[s], offsets[s + 1]) and runs for its own length (a sequence without frames gives the zero vector).  h_out: float[n_seq x units]
+ * = h_T of every sequence.  A sequence's output bits do not depend on the batch it is in.  One kernel: 16 sequences per wave on exact
+ * fp32 MFMA, h and c in registers for the whole sequence, the weights streamed per time step through LDS. */
+int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* frame_seg, float* h_out, int where, float* kernel_ms);
+/* The operand-order image ssp_lstm_create uploads, built on the host (no device, no ctx).  With HT = 1, 2, 4 or 8 tiles of 16 hidden
+ * units covering `units`, dT = ceil(d_in / 16) and G = dT + HT input groups of 16:
+ *   image[(((j G + g) 4 + q) 64 + lane) 4 + r] = row k, column q units + u of W (g < dT: k = 16 g + 4 (lane >> 4) + r) or of U
+ *   (g >= dT: k = 16 (g - dT) + 4 (lane >> 4) + r), u = 16 j + (lane & 15); zero where k or u lies beyond the matrix;
+ *   then bias as [4 gates][16 HT], zero padded.
+ * n_floats_out (nullable) receives the image's length, HT G 1024 + 64 HT; image_out == NULL only asks for that length. */
+int ssp_lstm_pack_weights(int32_t d_in, int32_t units, const float* W, const float* U, const float* bias, float* image_out,
+                          int64_t* n_floats_out);
 
 /* ---- d-vector cosine scoring: replaces the scipy cosine double loop + argmin
  *      (d_vector.py:315-319, 346-361) ---- */

@@ -88,6 +88,10 @@ SIGNATURES = {
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),
     "ssp_dnn_destroy": (C.c_int, [_P]),
     "ssp_dnn_forward": (C.c_int, [_P, _F32P, C.c_int64, _F32P, C.c_int, _MSP]),
+    "ssp_lstm_create": (C.c_int, [_P, C.c_int32, C.c_int32, _F32P, _F32P, _F32P, C.c_int32, C.POINTER(_P)]),
+    "ssp_lstm_destroy": (C.c_int, [_P]),
+    "ssp_lstm_forward": (C.c_int, [_P, _F32P, _P, _F32P, C.c_int, _MSP]),
+    "ssp_lstm_pack_weights": (C.c_int, [C.c_int32, C.c_int32, _F32P, _F32P, _F32P, _F32P, _I64P]),
     "ssp_dtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_fastdtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_void_p, _MSP]),
     "ssp_dtw_path": (C.c_int, [_P, _F32P, C.c_int64, _F32P, C.c_int64, C.c_int32, _P, _P, _P, _P]),

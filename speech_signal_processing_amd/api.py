@@ -849,6 +849,89 @@ class DnnForward:
             pass
 
 
+LSTM_ACTIVATIONS = {"hard_sigmoid": 0, "sigmoid": 1}
+
+
+def _lstm_arrays(W, U, b):
+    """contiguous float32 (W (d_in, 4 units), U (units, 4 units), b (4 units,) or None) in Keras' layout, shapes checked"""
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    U = np.ascontiguousarray(U, dtype=np.float32)
+    if W.ndim != 2 or U.ndim != 2 or U.shape[1] != 4 * U.shape[0] or W.shape[1] != U.shape[1]:
+        raise ValueError("W must be (d_in, 4 units) and U (units, 4 units)")
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+    if b is not None and b.shape[0] != U.shape[1]:
+        raise ValueError("b must have 4 units entries")
+    return W, U, b
+
+
+def lstm_pack_weights(W, U, b=None):
+    """The operand-order weight image LstmForward uploads, built on the host by ssp_lstm_pack_weights (no device, no context): float32
+    vector laid out as include/ssp.h documents.  W (d_in, 4 units), U (units, 4 units), b (4 units,) or None — Keras' layout."""
+    W, U, b = _lstm_arrays(W, U, b)
+    lib = _lib.load()
+    n = C.c_int64()
+    d_in, units = int(W.shape[0]), int(U.shape[0])
+    _lib.check(lib.ssp_lstm_pack_weights(d_in, units, None, None, None, None, C.byref(n)))
+    img = np.empty(n.value, dtype=np.float32)
+    _lib.check(lib.ssp_lstm_pack_weights(d_in, units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data, img.ctypes.data, None))
+    return img
+
+
+class LstmForward:
+    """One Keras LSTM layer packed once for the GPU forward pass (ssp_lstm; d_vector.py:271-294): W (d_in, 4 units), U (units, 4 units),
+    b (4 units,) or None in Keras' layout (gate blocks i | f | c | o), ``recurrent_activation`` 'hard_sigmoid' or 'sigmoid' — named by
+    the caller, there is no default.  ``forward`` returns the last hidden state of every sequence.  units: a multiple of 16 up to 128,
+    d_in up to 64 (NotImplementedError otherwise)."""
+
+    def __init__(self, ctx: Context, W, U, b, recurrent_activation):
+        if recurrent_activation not in LSTM_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        self.ctx = ctx
+        self._lib = ctx._lib
+        W, U, b = _lstm_arrays(W, U, b)
+        self.d_in, self.units = int(W.shape[0]), int(U.shape[0])
+        self.recurrent_activation = recurrent_activation
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_lstm_create(ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data,
+                                             LSTM_ACTIVATIONS[recurrent_activation], C.byref(h)))
+        self._h = h
+
+    def forward(self, feats, frame_seg: Optional[Segments] = None, timing: bool = False):
+        """feats (N, T, d_in) — equal lengths, no segments needed — or (frames, d_in) laid out by ``frame_seg`` (what MfccPlan.run
+        returns); numpy (host) or torch CUDA tensor.  Returns (n sequences, units) of the same kind [and kernel milliseconds]."""
+        keep, ptr, where = _as_f32(feats, "feats")
+        if keep.ndim == 3:
+            if frame_seg is not None:
+                raise ValueError("(N, T, d_in) input takes no frame_seg")
+            if int(keep.shape[2]) != self.d_in:
+                raise ValueError("feats must be (N, T, %d)" % self.d_in)
+            if int(keep.shape[0]) == 0:
+                out = self.ctx._empty((0, self.units), where)
+                return (out, 0.0) if timing else out
+            frame_seg = Segments(self.ctx, np.arange(int(keep.shape[0]) + 1, dtype=np.int64) * int(keep.shape[1]))
+        elif keep.ndim != 2 or int(keep.shape[1]) != self.d_in or frame_seg is None:
+            raise ValueError("feats must be (N, T, %d), or (frames, %d) with frame_seg" % (self.d_in, self.d_in))
+        elif int(keep.shape[0]) < int(frame_seg.offsets[-1]):
+            raise ValueError("fewer rows than frame_seg has frames")
+        out = self.ctx._empty((frame_seg.n, self.units), where)
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_lstm_forward(self._h, ptr, frame_seg._h, _raw_ptr(out, where), where, C.byref(ms) if timing else None))
+        del keep
+        return (out, ms.value) if timing else out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_lstm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def cosine_identify(ctx: Context, X, Cn, dist: bool = False, argmin: bool = True, minval: bool = True,
                     timing: bool = False, precision: int = 0, counts: bool = True) -> dict:
     """dist[i,j] = clip(1 - cos(X[i], C[j]), 0, 2); argmin over j (first index on ties) — d_vector.py:315-319.

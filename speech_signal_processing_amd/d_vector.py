@@ -1,7 +1,8 @@
 """GPU-backed mirror of the inference half of the reference's ``d_vector.py``: Data_gen's feature front end
 (d_vector.py:80-98), the forward pass of the fully connected speaker network (``DenseNet.predict`` = spkModel.predict of
-the Sequential built at d_vector.py:171-189) and nn_model.test / enroll / eval (d_vector.py:296-361).  Training the
-Keras networks (and the GRU / LSTM variants) is out of scope: weights are inputs."""
+the Sequential built at d_vector.py:171-189), the forward pass of the recurrent one (``LstmNet.predict``: the LSTM(128) of
+d_vector.py:271-294, the network nn_model.enroll / eval load by default) and nn_model.test / enroll / eval (d_vector.py:296-361).
+Training the Keras networks, and the conv + GRU variant (d_vector.py:212-269), are out of scope: weights are inputs."""
 from __future__ import annotations
 
 import functools
@@ -66,6 +67,50 @@ class DenseNet:
         return h if is_t else h.cpu().numpy()
 
 
+class LstmNet:
+    """Forward pass of the reference's recurrent d-vector network (d_vector.py:271-294): one LSTM(units) over the (T, D) feature matrix
+    of a chunk, the last hidden state is the embedding — what ``load_model('feature/d_vector/d_vector_lstm.h5').predict`` computes up
+    to the layer the reference cuts the model at.  W (D, 4 units), U (units, 4 units), b (4 units,) or None are ``layer.get_weights()``
+    as Keras stores them (gate blocks i | f | c | o).  ``recurrent_activation`` must be named: 'hard_sigmoid' (stand-alone Keras up to
+    2.2, current when the reference was written) or 'sigmoid' (Keras 2.3 on, tf.keras) — the two give different embeddings and the
+    weights file does not say which one trained them.  Weights go to the GPU once (api.LstmForward)."""
+
+    def __init__(self, W, U, b=None, *, recurrent_activation, device: int = 0):
+        self._ctx = api.default_context(device, torch_stream=True)
+        self.W = np.ascontiguousarray(W, dtype=np.float32)
+        self.U = np.ascontiguousarray(U, dtype=np.float32)
+        self.b = None if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+        self.recurrent_activation = recurrent_activation
+        self._net = api.LstmForward(self._ctx, self.W, self.U, self.b, recurrent_activation)
+        self.input_dim = self._net.d_in
+        self.output_dim = self._net.units
+
+    @classmethod
+    def from_keras(cls, layer, device: int = 0):
+        """From a Keras LSTM layer (or anything with its ``get_weights()`` and ``recurrent_activation`` function)."""
+        w = layer.get_weights()
+        if len(w) not in (2, 3):
+            raise ValueError("an LSTM layer holds [kernel, recurrent_kernel] or [kernel, recurrent_kernel, bias]")
+        return cls(w[0], w[1], w[2] if len(w) == 3 else None, recurrent_activation=layer.recurrent_activation.__name__, device=device)
+
+    def predict(self, X, batch_size=None):
+        """X (N, T, D), or (N, T * D) — what nn_model.eval's reshape(1, -1) and load_data(reshape=True) hand over —, numpy or torch CUDA
+        tensor -> (N, units) of the same kind (numpy in: float32 out)."""
+        if not api._is_torch(X):
+            X = np.asarray(X)
+        if X.ndim == 2:
+            if X.shape[1] == 0 or X.shape[1] % self.input_dim:
+                raise ValueError("X must be (N, T, %d) or (N, T * %d)" % (self.input_dim, self.input_dim))
+            X = X.reshape(X.shape[0], X.shape[1] // self.input_dim, self.input_dim)
+        if X.ndim != 3 or X.shape[2] != self.input_dim:
+            raise ValueError("X must be (N, T, %d) or (N, T * %d)" % (self.input_dim, self.input_dim))
+        return self._net.forward(X)
+
+    def predict_ragged(self, feats, fseg):
+        """feats (frames, D) laid out by the frame segments ``fseg`` (MfccPlan.run's output, as it is) -> (n sequences, units)."""
+        return self._net.forward(feats, fseg)
+
+
 # ---- model registry: the reference addresses its networks by name — load_model('feature/d_vector/d_vector_{}.h5'.format(model_name)),
 # d_vector.py:297,329,347.  Keras / h5py are not part of this path: a DenseNet is registered under the name (or saved next to where
 # the .h5 would be, as d_vector_{name}.npz) and `model_name=` resolves to it.
@@ -74,14 +119,19 @@ MODEL_DIR = os.path.join('feature', 'd_vector')
 
 
 def register_model(name, net):
-    """Make ``net`` (a DenseNet, or any object with .predict) the model that ``model_name=name`` refers to."""
+    """Make ``net`` (a DenseNet, an LstmNet, or any object with .predict) the model that ``model_name=name`` refers to."""
     _MODELS[str(name)] = net
 
 
-def save_model(net: "DenseNet", name, model_dir=None):
-    """Store a DenseNet's weights as {model_dir}/d_vector_{name}.npz (the .h5's place, d_vector.py:297)."""
+def save_model(net, name, model_dir=None):
+    """Store a DenseNet's or an LstmNet's weights as {model_dir}/d_vector_{name}.npz (the .h5's place, d_vector.py:297).  An LstmNet's
+    file carries kind = 'lstm' and its recurrent activation; a file without ``kind`` is a DenseNet."""
     model_dir = MODEL_DIR if model_dir is None else model_dir
     os.makedirs(model_dir, exist_ok=True)
+    if isinstance(net, LstmNet):
+        np.savez(os.path.join(model_dir, "d_vector_%s.npz" % name), kind=np.array("lstm"), W=net.W, U=net.U,
+                 b=np.zeros(0, np.float32) if net.b is None else net.b, recurrent_activation=np.array(net.recurrent_activation))
+        return
     arrs = {}
     for i, (Wt, bt, relu) in enumerate(net.layers):
         arrs["W%d" % i] = Wt.cpu().numpy().T
@@ -100,6 +150,12 @@ def load_model(name, model_dir=None):
     if not os.path.exists(path):
         raise OSError("no d-vector model %r: register_model(%r, net) or save one as %s" % (name, name, path))
     z = np.load(path)
+    if "kind" in z.files:
+        if str(z["kind"]) != "lstm":
+            raise ValueError("%s: unknown model kind %r" % (path, str(z["kind"])))
+        net = LstmNet(z["W"], z["U"], z["b"] if z["b"].size else None, recurrent_activation=str(z["recurrent_activation"]))
+        _MODELS[name] = net
+        return net
     n = len([k for k in z.files if k.startswith("W")])
     net = DenseNet([(z["W%d" % i], z["b%d" % i] if z["b%d" % i].size else None, 'relu' if int(z["a%d" % i]) else 'linear') for i in range(n)])
     _MODELS[name] = net
