@@ -52,6 +52,7 @@ typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
+typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
 
 /* MFCC dialect knobs.  Three presets are built by the host side:
  *   in-repo  utils/processing.py:19-144  (Hamming, |X|/L, 40 talkbox filters folded, log10(.+1e-8), c0..c12)
@@ -383,6 +384,45 @@ int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* fra
  * n_floats_out (nullable) receives the image's length, HT G 1024 + 64 HT; image_out == NULL only asks for that length. */
 int ssp_lstm_pack_weights(int32_t d_in, int32_t units, const float* W, const float* U, const float* bias, float* image_out,
                           int64_t* n_floats_out);
+
+/* ---- d-vector conv + GRU network forward (since without a version step, like the LSTM entries): the pieces of inference_gru
+ *      (d_vector.py:213-269) — Conv2D(64, 5x5, strides 2, padding 'same') :216-221, TimeDistributed(Flatten) :226, 3 x GRU(1024,
+ *      return_sequences=True) :229-231, the mean over time :234-237, Dense(512) :240 (ssp_dense_forward) and K.l2_normalize :243-246 — the
+ *      network d_vector.py:389 evaluates as model_name 'lstm_conv'.  Unpinned: the reference tree holds no GRU weights or outputs.
+ *      One GRU layer, Keras' cell at inference, gate blocks z | r | h, zero initial state, return_sequences:
+ *        reset_after 0 (stand-alone Keras), bias [3 units] or NULL:
+ *          z = s(x W_z + b_z + h U_z);  r = s(x W_r + b_r + h U_r);  hh = tanh(x W_h + b_h + (r . h) U_h)
+ *        reset_after 1 (tf.keras 2), bias [2 x 3 units] = input row, recurrent row, or NULL:
+ *          z = s(x W_z + b_iz + h U_z + b_rz);  r likewise;  hh = tanh(x W_h + b_ih + r . (h U_h + b_rh))
+ *        h_t = z . h_{t-1} + (1 - z) . hh
+ *      recurrent_activation names s: 0 hard_sigmoid = clip(0.2 z + 0.5, 0, 1) | 1 logistic sigmoid.  The weights file records neither
+ *      switch: the caller names both, there is no default. ---- */
+/* W: HOST float[d_in x 3 units], U: HOST float[units x 3 units], bias as above — layer.get_weights() as it is.  units: a multiple of
+ * 16 up to 1024; d_in up to 4096; anything else answers SSP_ERR_UNSUPPORTED, a bad switch or a null kernel SSP_ERR_INVALID, both
+ * before any GPU work. */
+int ssp_gru_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, const float* U, const float* bias,
+                   int32_t recurrent_activation, int32_t reset_after, ssp_gru** out);
+int ssp_gru_destroy(ssp_gru* gru);
+/* X: float[N x T x d_in]; seq_out (nullable): float[N x T x units] = h_t of every step; mean_out (nullable): float[N x units] = the mean
+ * of h_t over t, summed with t ascending (d_vector.py:234-237).  The input projection of all rows is one GEMM, the recurrence one launch
+ * per time step (two with reset_after 0) of an exact-fp32 MFMA GEMM against the packed U with the gate arithmetic in its epilogue, on
+ * the ctx stream.  A large batch runs in slabs of whole chunks under the workspace cap (projection buffer, kept on the ctx and shared
+ * by the layers of a network; the output sequence when seq_out is NULL, on the host or not 16-byte aligned; z and r . h with
+ * reset_after 0); one chunk always runs.  A chunk's output bits do not depend on N, on the slab size or on its place in the batch. */
+int ssp_gru_forward(ssp_gru* gru, const float* X, int64_t N, int32_t T, float* seq_out, float* mean_out, int where, float* kernel_ms);
+/* the workspace cap of one forward call in bytes (default 2 GiB) and the chunks per slab the last call used */
+int ssp_gru_set_workspace(ssp_gru* gru, size_t bytes);
+int ssp_gru_last_slab(const ssp_gru* gru, int64_t* chunks_out);
+/* Conv2D with one input channel, channels last, linear activation, TensorFlow's `same` padding (d_vector.py:216-221): out = ceil(in / s),
+ * pad = max((out - 1) s + k - in, 0), pad / 2 in front and the rest behind; a cross-correlation.  X: float[N x T x D]; K: float[kh x kw x 1 x F]
+ * (the Keras kernel as it is); bias: float[F] (nullable); Y: float[N x To x Do F], element (f_out F + c) of a time step — the
+ * TimeDistributed(Flatten) of d_vector.py:226 is this layout.  kh, kw up to 7, F up to 256, strides 1 or 2 (SSP_ERR_UNSUPPORTED beyond).
+ * All arrays live on the side `where` names. */
+int ssp_conv2d_same_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t T, int32_t D, const float* K, const float* bias, int32_t kh,
+                            int32_t kw, int32_t F, int32_t sh, int32_t sw, float* Y, int where, float* kernel_ms);
+/* K.l2_normalize(x, axis=1) (d_vector.py:243-246): Y = X / sqrt(max(sum_k X_k^2, eps)) per row (Keras' eps: 1e-12; an all-zero row stays
+ * zero).  X, Y: float[N x d]; Y may be X. */
+int ssp_l2_normalize(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, float eps, float* Y, int where, float* kernel_ms);
 
 /* ---- d-vector cosine scoring: replaces the scipy cosine double loop + argmin
  *      (d_vector.py:315-319, 346-361) ---- */

@@ -92,6 +92,14 @@ SIGNATURES = {
     "ssp_lstm_destroy": (C.c_int, [_P]),
     "ssp_lstm_forward": (C.c_int, [_P, _F32P, _P, _F32P, C.c_int, _MSP]),
     "ssp_lstm_pack_weights": (C.c_int, [C.c_int32, C.c_int32, _F32P, _F32P, _F32P, _F32P, _I64P]),
+    "ssp_gru_create": (C.c_int, [_P, C.c_int32, C.c_int32, _F32P, _F32P, _F32P, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ssp_gru_destroy": (C.c_int, [_P]),
+    "ssp_gru_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int, _MSP]),
+    "ssp_gru_set_workspace": (C.c_int, [_P, C.c_size_t]),
+    "ssp_gru_last_slab": (C.c_int, [_P, _I64P]),
+    "ssp_conv2d_same_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, _F32P, C.c_int, _MSP]),
+    "ssp_l2_normalize": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_float, _F32P, C.c_int, _MSP]),
     "ssp_dtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_fastdtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_void_p, _MSP]),
     "ssp_dtw_path": (C.c_int, [_P, _F32P, C.c_int64, _F32P, C.c_int64, C.c_int32, _P, _P, _P, _P]),

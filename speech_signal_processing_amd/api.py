@@ -932,6 +932,137 @@ class LstmForward:
             pass
 
 
+GRU_ACTIVATIONS = LSTM_ACTIVATIONS
+
+
+def _gru_arrays(W, U, b, reset_after):
+    """contiguous float32 (W (d_in, 3 units), U (units, 3 units), b (3 units,) / (2, 3 units) or None) in Keras' layout, shapes checked"""
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    U = np.ascontiguousarray(U, dtype=np.float32)
+    if W.ndim != 2 or U.ndim != 2 or U.shape[1] != 3 * U.shape[0] or W.shape[1] != U.shape[1]:
+        raise ValueError("W must be (d_in, 3 units) and U (units, 3 units)")
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        want = (2, U.shape[1]) if reset_after else (U.shape[1],)
+        if b.shape != want:
+            raise ValueError("b must be %s with reset_after=%s" % (want, bool(reset_after)))
+    return W, U, b
+
+
+class GruForward:
+    """One Keras GRU layer packed once for the GPU forward pass (ssp_gru; the GRU(1024, return_sequences=True) layers of d_vector.py:229-231):
+    W (d_in, 3 units), U (units, 3 units), b in Keras' layout (gate blocks z | r | h).  Both switches are named by the caller, there is no
+    default: ``recurrent_activation`` 'hard_sigmoid' or 'sigmoid', ``reset_after`` False (stand-alone Keras; b (3 units,) or None) or True
+    (tf.keras 2; b (2, 3 units) or None).  units: a multiple of 16 up to 1024, d_in up to 4096 (NotImplementedError otherwise)."""
+
+    def __init__(self, ctx: Context, W, U, b, recurrent_activation, reset_after):
+        if recurrent_activation not in GRU_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        if not isinstance(reset_after, (bool, np.bool_)):
+            raise ValueError("reset_after must be True or False")
+        self.ctx = ctx
+        self._lib = ctx._lib
+        W, U, b = _gru_arrays(W, U, b, reset_after)
+        self.d_in, self.units = int(W.shape[0]), int(U.shape[0])
+        self.recurrent_activation, self.reset_after = recurrent_activation, bool(reset_after)
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_gru_create(ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data,
+                                            GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, C.byref(h)))
+        self._h = h
+
+    def set_workspace(self, nbytes: int) -> "GruForward":
+        """cap of the workspace one forward call may hold; larger batches run in slabs of whole chunks (same bits)"""
+        _lib.check(self._lib.ssp_gru_set_workspace(self._h, C.c_size_t(int(nbytes))))
+        return self
+
+    @property
+    def last_slab(self) -> int:
+        n = C.c_int64(0)
+        _lib.check(self._lib.ssp_gru_last_slab(self._h, C.byref(n)))
+        return n.value
+
+    def forward(self, X, mean: bool = False, timing: bool = False):
+        """X (N, T, d_in), numpy (host) or torch CUDA tensor -> the output sequence (N, T, units) of the same kind, or with ``mean=True``
+        its mean over time (N, units) [and kernel milliseconds]."""
+        keep, ptr, where = _as_f32(X, "X")
+        if keep.ndim != 3 or int(keep.shape[2]) != self.d_in or int(keep.shape[1]) < 1:
+            raise ValueError("X must be (N, T >= 1, %d)" % self.d_in)
+        N, T = int(keep.shape[0]), int(keep.shape[1])
+        out = self.ctx._empty((N, self.units) if mean else (N, T, self.units), where)
+        ms = C.c_float(0.0)
+        if N:
+            with self.ctx._ordered(where):
+                _lib.check(self._lib.ssp_gru_forward(self._h, ptr, N, T, None if mean else _raw_ptr(out, where), _raw_ptr(out, where) if mean else None,
+                                                     where, C.byref(ms) if timing else None))
+        del keep
+        return (out, ms.value) if timing else out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_gru_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def conv2d_same_out_shape(T: int, D: int, strides):
+    """(To, Do) of a `same` convolution: ceil(in / stride)"""
+    return -(-int(T) // int(strides[0])), -(-int(D) // int(strides[1]))
+
+
+def conv2d_same(ctx: Context, X, K, bias=None, strides=(1, 1), timing: bool = False):
+    """Conv2D(F, (kh, kw), strides, padding='same') with one input channel, channels last, linear activation (ssp_conv2d_same_forward;
+    d_vector.py:216-221) followed by TimeDistributed(Flatten) (:226).  X (N, T, D); K (kh, kw, 1, F) or (kh, kw, F) — the Keras kernel;
+    bias (F,) or None; all numpy (host) or all torch CUDA tensors.  Returns (N, To, Do * F) of the same kind, element f_out * F + c."""
+    xk, xp, where = _as_f32(X, "X")
+    kk, kp, kwhere = _as_f32(K, "K")
+    if kwhere != where:
+        raise ValueError("X and K must both be numpy arrays or both be torch CUDA tensors")
+    if kk.ndim == 4 and int(kk.shape[2]) == 1:
+        kk = kk.reshape(kk.shape[0], kk.shape[1], kk.shape[3])
+    if xk.ndim != 3 or kk.ndim != 3:
+        raise ValueError("X must be (N, T, D) and K (kh, kw, 1, F)")
+    N, T, D = (int(v) for v in xk.shape)
+    kh, kw, F = (int(v) for v in kk.shape)
+    if T < 1 or D < 1:
+        raise ValueError("X must be (N, T >= 1, D >= 1)")
+    bk, bp = None, None
+    if bias is not None:
+        bk, bp, bwhere = _as_f32(bias, "bias")
+        if bwhere != where or int(np.prod(bk.shape)) != F:
+            raise ValueError("bias must have F entries and live where X lives")
+    sh, sw = int(strides[0]), int(strides[1])
+    if sh < 1 or sw < 1:
+        raise ValueError("strides must be >= 1")
+    To, Do = conv2d_same_out_shape(T, D, (sh, sw))
+    Y = ctx._empty((N, To, Do * F), where)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_conv2d_same_forward(ctx._h, xp, N, T, D, kp, bp, kh, kw, F, sh, sw, _raw_ptr(Y, where), where,
+                                                     C.byref(ms) if timing else None))
+    del xk, kk, bk
+    return (Y, ms.value) if timing else Y
+
+
+def l2_normalize(ctx: Context, X, eps: float = 1e-12, timing: bool = False):
+    """K.l2_normalize(X, axis=-1) on rows (ssp_l2_normalize; d_vector.py:243-246): X / sqrt(max(sum X^2, eps)).  X (N, d) numpy or torch
+    CUDA tensor -> the same kind."""
+    xk, xp, where = _as_f32(X, "X")
+    if xk.ndim != 2 or int(xk.shape[1]) < 1:
+        raise ValueError("X must be (N, d >= 1)")
+    N, d = int(xk.shape[0]), int(xk.shape[1])
+    Y = ctx._empty((N, d), where)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_l2_normalize(ctx._h, xp, N, d, float(eps), _raw_ptr(Y, where), where, C.byref(ms) if timing else None))
+    del xk
+    return (Y, ms.value) if timing else Y
+
+
 def cosine_identify(ctx: Context, X, Cn, dist: bool = False, argmin: bool = True, minval: bool = True,
                     timing: bool = False, precision: int = 0, counts: bool = True) -> dict:
     """dist[i,j] = clip(1 - cos(X[i], C[j]), 0, 2); argmin over j (first index on ties) — d_vector.py:315-319.

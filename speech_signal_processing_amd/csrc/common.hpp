@@ -142,6 +142,9 @@ struct ssp_ctx {
     mutable bool cos_counts_pending = false;  // the two counts still sit in cos_count on the device (a device-pointer call does not wait for them)
     // cosine scorer's scratch, kept between calls (the reference calls it in a loop): packed centroid images, the lists of close calls, counts
     ssp::DevBuf cos_img16, cos_img, cos_list1, cos_list2, cos_count, cos_inc;
+    // input projection of the GRU layer that is running (gru.hip): grow-only, shared by the layers of a network, which run one after
+    // the other on the ctx stream
+    ssp::DevBuf gru_proj;
     mutable ssp::StagePool stage;  // staging buffers of SSP_HOST calls
     int32_t* pinned_words = nullptr;  // 64 bytes of pinned host memory for small read-backs (precision-auto pilots)
     ssp::HostPipe* pipe = nullptr;  // slots / streams of the sliced host-fed MFCC path (staging.hpp; made on first use)

@@ -1,8 +1,11 @@
 """GPU-backed mirror of the inference half of the reference's ``d_vector.py``: Data_gen's feature front end
 (d_vector.py:80-98), the forward pass of the fully connected speaker network (``DenseNet.predict`` = spkModel.predict of
 the Sequential built at d_vector.py:171-189), the forward pass of the recurrent one (``LstmNet.predict``: the LSTM(128) of
-d_vector.py:271-294, the network nn_model.enroll / eval load by default) and nn_model.test / enroll / eval (d_vector.py:296-361).
-Training the Keras networks, and the conv + GRU variant (d_vector.py:212-269), are out of scope: weights are inputs."""
+d_vector.py:271-294, the network nn_model.enroll / eval load by default), the forward pass of the conv + GRU one (``ConvGruNet.predict``:
+Conv2D -> 3 x GRU(1024) -> mean over time -> Dense(512) -> L2 normalisation, d_vector.py:213-269, the network d_vector.py:389 evaluates)
+and nn_model.test / enroll / eval (d_vector.py:296-361).  Training the Keras networks is out of scope: weights are inputs.
+The recurrent networks are UNPINNED: the reference tree holds no weights or outputs for them and Keras is not a dependency; their
+arithmetic is restated from Keras' documentation and corroborated against torch's cells only."""
 from __future__ import annotations
 
 import functools
@@ -111,6 +114,142 @@ class LstmNet:
         return self._net.forward(feats, fseg)
 
 
+class ConvGruNet:
+    """Forward pass of the reference's conv + GRU d-vector network (d_vector.py:213-269 inference_gru; 'feature/d_vector/d_vector_gru.h5'):
+    Conv2D(F, (kh, kw), strides, padding='same') on the (T, D, 1) feature matrix of a chunk, TimeDistributed(Flatten), n GRU layers with
+    return_sequences, the mean over time, Dense and K.l2_normalize.  ``conv`` = (K (kh, kw, 1, F), b (F,) or None, strides (sh, sw));
+    ``grus`` = [(W (d_in, 3 units), U (units, 3 units), b or None), ...]; ``dense`` = (Wd (units, E), bd (E,) or None) — all as
+    ``layer.get_weights()`` returns them.  Both GRU switches must be named, the weights do not record them: ``recurrent_activation``
+    'hard_sigmoid' (stand-alone Keras up to 2.2) or 'sigmoid', ``reset_after`` False (stand-alone Keras, bias (3 units,)) or True (tf.keras 2,
+    bias (2, 3 units)).  ``input_shape`` = (T, D) lets predict take flattened (N, T * D) rows.  A batch runs in slabs of chunks whose
+    intermediate activations fit ``workspace_bytes`` (default 4 GiB); a chunk's embedding does not depend on the slab it is in.  Layers
+    chain on the device.  Unpinned against Keras (no GRU fixture in the reference, no Keras here): corroborated against torch only."""
+
+    DEFAULT_WORKSPACE = 4 << 30
+
+    def __init__(self, conv, grus, dense, *, recurrent_activation, reset_after, input_shape=None, workspace_bytes=None, device: int = 0):
+        if recurrent_activation not in api.GRU_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        if not isinstance(reset_after, (bool, np.bool_)):
+            raise ValueError("reset_after must be True or False")
+        K, bc, strides = conv
+        self.K = np.ascontiguousarray(K, dtype=np.float32)
+        if self.K.ndim == 3:
+            self.K = self.K[:, :, None, :]
+        if self.K.ndim != 4 or self.K.shape[2] != 1:
+            raise ValueError("the convolution kernel must be (kh, kw, 1, F)")
+        self.bc = None if bc is None else np.ascontiguousarray(bc, dtype=np.float32).reshape(-1)
+        self.strides = (int(strides[0]), int(strides[1]))
+        if len(grus) < 1:
+            raise ValueError("at least one GRU layer")
+        self.grus = [api._gru_arrays(W, U, b, reset_after) for W, U, b in grus]
+        Wd, bd = dense
+        self.Wd = np.ascontiguousarray(Wd, dtype=np.float32)
+        self.bd = None if bd is None else np.ascontiguousarray(bd, dtype=np.float32).reshape(-1)
+        F = int(self.K.shape[3])
+        for i, (W, U, _) in enumerate(self.grus):
+            if i and W.shape[0] != self.grus[i - 1][1].shape[0]:
+                raise ValueError("GRU layer %d does not take layer %d's width" % (i, i - 1))
+        if self.grus[0][0].shape[0] % F:
+            raise ValueError("the first GRU's input width must be a multiple of the %d filters" % F)
+        if self.Wd.ndim != 2 or self.Wd.shape[0] != self.grus[-1][1].shape[0]:
+            raise ValueError("the Dense kernel must be (units, E)")
+        self.recurrent_activation, self.reset_after = recurrent_activation, bool(reset_after)
+        self.input_shape = None if input_shape is None else (int(input_shape[0]), int(input_shape[1]))
+        self.workspace_bytes = int(self.DEFAULT_WORKSPACE if workspace_bytes is None else workspace_bytes)
+        if self.workspace_bytes < 1:
+            raise ValueError("workspace_bytes must be positive")
+        self.output_dim = int(self.Wd.shape[1])
+        import torch
+        self._ctx = api.default_context(device, torch_stream=True)
+        self._dev = "cuda:%d" % device
+        self._K = torch.from_numpy(self.K).to(self._dev)
+        self._bc = None if self.bc is None else torch.from_numpy(self.bc).to(self._dev)
+        self._layers = [api.GruForward(self._ctx, W, U, b, recurrent_activation, bool(reset_after)) for W, U, b in self.grus]
+        self._Wdt = torch.from_numpy(np.ascontiguousarray(self.Wd.T)).to(self._dev)
+        self._bd = None if self.bd is None else torch.from_numpy(self.bd).to(self._dev)
+        self.last_slab = 0
+
+    @classmethod
+    def from_keras(cls, model, *, recurrent_activation, reset_after, input_shape=None, workspace_bytes=None, device: int = 0):
+        """From a Keras model (or anything whose ``layers`` have ``get_weights()``): the layers that hold weights are taken in order — one
+        Conv2D (4-D kernel; ``strides`` read from the layer), the GRUs (two 2-D kernels) and the Dense (one 2-D kernel)."""
+        conv, grus, dense = None, [], None
+        for layer in model.layers:
+            w = layer.get_weights()
+            if not w:
+                continue
+            if np.ndim(w[0]) == 4:
+                conv = (w[0], w[1] if len(w) > 1 else None, tuple(getattr(layer, "strides", (1, 1))))
+            elif len(w) >= 2 and np.ndim(w[1]) == 2:
+                grus.append((w[0], w[1], w[2] if len(w) > 2 else None))
+            else:
+                dense = (w[0], w[1] if len(w) > 1 else None)
+        if conv is None or not grus or dense is None:
+            raise ValueError("expected a Conv2D, GRU layers and a Dense among the model's layers")
+        return cls(conv, grus, dense, recurrent_activation=recurrent_activation, reset_after=reset_after, input_shape=input_shape,
+                   workspace_bytes=workspace_bytes, device=device)
+
+    def _slab(self, T, D):
+        To, Do = api.conv2d_same_out_shape(T, D, self.strides)
+        F = int(self.K.shape[3])
+        if Do * F != self.grus[0][0].shape[0]:
+            raise ValueError("a (%d, %d) input gives %d features per step, the first GRU takes %d" % (T, D, Do * F, self.grus[0][0].shape[0]))
+        widths = [U.shape[0] for _, U, _ in self.grus]
+        seq = sorted(widths, reverse=True)[:2]     # two sequences are alive at a time (a layer's input and its output)
+        per = 4 * To * (Do * F + sum(seq) + 3 * max(widths)) + 4 * 2 * max(widths)
+        return max(1, self.workspace_bytes // per), per, To
+
+    def predict(self, X, batch_size=None, parts=None):
+        """X (N, T, D, 1) or (N, T, D) — or (N, T * D) when ``input_shape`` was given —, numpy or torch CUDA tensor -> (N, E) unit-length
+        embeddings of the same kind (numpy in: float32 out).  ``parts``: a dict that receives 'mean' (the last GRU's mean over time) and,
+        with a 'ms' key present, the kernel milliseconds of each stage summed over the slabs (each reading synchronises)."""
+        import torch
+        is_t = api._is_torch(X)
+        if not is_t:
+            X = np.asarray(X)
+        if X.ndim == 2 and self.input_shape is not None and X.shape[1] == self.input_shape[0] * self.input_shape[1]:
+            X = X.reshape(X.shape[0], self.input_shape[0], self.input_shape[1])
+        if X.ndim == 4 and X.shape[3] == 1:
+            X = X.reshape(X.shape[0], X.shape[1], X.shape[2])
+        if X.ndim != 3 or X.shape[1] < 1 or X.shape[2] < 1:
+            raise ValueError("X must be (N, T, D, 1) or (N, T, D)" + ("" if self.input_shape is None else " or (N, %d)" % (self.input_shape[0] * self.input_shape[1])))
+        N, T, D = (int(v) for v in X.shape)
+        slab, _, _ = self._slab(T, D)
+        self.last_slab = min(slab, N)
+        out = torch.empty((N, self.output_dim), dtype=torch.float32, device=self._dev)
+        H = int(self.grus[-1][1].shape[0])
+        mean_all = torch.empty((N, H), dtype=torch.float32, device=self._dev) if parts is not None else None
+        timing = parts is not None and "ms" in parts
+        ms = {"conv": 0.0, "gru": [0.0] * len(self._layers), "tail": 0.0}
+        for c0 in range(0, N, slab):
+            x = X[c0:c0 + slab]
+            if not is_t:
+                x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self._dev)
+            r = api.conv2d_same(self._ctx, x, self._K, self._bc, self.strides, timing=timing)
+            h, t_ms = r if timing else (r, 0.0)
+            ms["conv"] += t_ms
+            for i, g in enumerate(self._layers):
+                g.set_workspace(self.workspace_bytes)
+                r = g.forward(h, mean=i == len(self._layers) - 1, timing=timing)
+                h, t_ms = r if timing else (r, 0.0)
+                ms["gru"][i] += t_ms
+            if mean_all is not None:
+                mean_all[c0:c0 + slab] = h
+            r = api.dense_forward(self._ctx, h, self._Wdt, self._bd, relu=False, timing=timing)
+            y, t_ms = r if timing else (r, 0.0)
+            ms["tail"] += t_ms
+            r = api.l2_normalize(self._ctx, y, timing=timing)
+            y, t_ms = r if timing else (r, 0.0)
+            ms["tail"] += t_ms
+            out[c0:c0 + slab] = y
+        if parts is not None:
+            parts["mean"] = mean_all if is_t else mean_all.cpu().numpy()
+            if timing:
+                parts["ms"] = ms
+        return out if is_t else out.cpu().numpy()
+
+
 # ---- model registry: the reference addresses its networks by name — load_model('feature/d_vector/d_vector_{}.h5'.format(model_name)),
 # d_vector.py:297,329,347.  Keras / h5py are not part of this path: a DenseNet is registered under the name (or saved next to where
 # the .h5 would be, as d_vector_{name}.npz) and `model_name=` resolves to it.
@@ -119,15 +258,26 @@ MODEL_DIR = os.path.join('feature', 'd_vector')
 
 
 def register_model(name, net):
-    """Make ``net`` (a DenseNet, an LstmNet, or any object with .predict) the model that ``model_name=name`` refers to."""
+    """Make ``net`` (a DenseNet, an LstmNet, a ConvGruNet, or any object with .predict) the model that ``model_name=name`` refers to."""
     _MODELS[str(name)] = net
 
 
 def save_model(net, name, model_dir=None):
-    """Store a DenseNet's or an LstmNet's weights as {model_dir}/d_vector_{name}.npz (the .h5's place, d_vector.py:297).  An LstmNet's
-    file carries kind = 'lstm' and its recurrent activation; a file without ``kind`` is a DenseNet."""
+    """Store a DenseNet's, an LstmNet's or a ConvGruNet's weights as {model_dir}/d_vector_{name}.npz (the .h5's place, d_vector.py:297).
+    An LstmNet's file carries kind = 'lstm' and its recurrent activation, a ConvGruNet's kind = 'conv_gru' with both GRU switches, the
+    strides and the input shape; a file without ``kind`` is a DenseNet."""
     model_dir = MODEL_DIR if model_dir is None else model_dir
     os.makedirs(model_dir, exist_ok=True)
+    if isinstance(net, ConvGruNet):
+        arrs = {"kind": np.array("conv_gru"), "recurrent_activation": np.array(net.recurrent_activation), "reset_after": np.array(int(net.reset_after)),
+                "strides": np.array(net.strides, np.int64), "n_gru": np.array(len(net.grus)), "conv_K": net.K,
+                "conv_b": np.zeros(0, np.float32) if net.bc is None else net.bc, "dense_W": net.Wd,
+                "dense_b": np.zeros(0, np.float32) if net.bd is None else net.bd,
+                "input_shape": np.array(net.input_shape if net.input_shape is not None else (), np.int64)}
+        for i, (W, U, b) in enumerate(net.grus):
+            arrs["gru%d_W" % i], arrs["gru%d_U" % i], arrs["gru%d_b" % i] = W, U, np.zeros(0, np.float32) if b is None else b
+        np.savez(os.path.join(model_dir, "d_vector_%s.npz" % name), **arrs)
+        return
     if isinstance(net, LstmNet):
         np.savez(os.path.join(model_dir, "d_vector_%s.npz" % name), kind=np.array("lstm"), W=net.W, U=net.U,
                  b=np.zeros(0, np.float32) if net.b is None else net.b, recurrent_activation=np.array(net.recurrent_activation))
@@ -151,6 +301,14 @@ def load_model(name, model_dir=None):
         raise OSError("no d-vector model %r: register_model(%r, net) or save one as %s" % (name, name, path))
     z = np.load(path)
     if "kind" in z.files:
+        if str(z["kind"]) == "conv_gru":
+            opt = lambda a: a if a.size else None  # noqa: E731
+            net = ConvGruNet((z["conv_K"], opt(z["conv_b"]), tuple(int(v) for v in z["strides"])),
+                             [(z["gru%d_W" % i], z["gru%d_U" % i], opt(z["gru%d_b" % i])) for i in range(int(z["n_gru"]))],
+                             (z["dense_W"], opt(z["dense_b"])), recurrent_activation=str(z["recurrent_activation"]),
+                             reset_after=bool(int(z["reset_after"])), input_shape=tuple(int(v) for v in z["input_shape"]) if z["input_shape"].size else None)
+            _MODELS[name] = net
+            return net
         if str(z["kind"]) != "lstm":
             raise ValueError("%s: unknown model kind %r" % (path, str(z["kind"])))
         net = LstmNet(z["W"], z["U"], z["b"] if z["b"].size else None, recurrent_activation=str(z["recurrent_activation"]))
