@@ -16,6 +16,14 @@
  *     above two slices (SSP_HOST_SLICE_MB, 64 MiB): those go through a ring of three slice-sized
  *     slots, copied in ahead of the kernels that consume them);  SSP_DEVICE (1): bulk arrays are
  *     device pointers on the ctx's device.
+ *   - alignment: a device array needs only the natural alignment of its element type (4 bytes
+ *     for float / int32, 2 for int16, 1 for uint8) — a slice `big[1:1 + n]` of a larger array is
+ *     a valid argument, and an int16 batch may start on an odd sample.  16-byte alignment is a
+ *     matter of speed only: several kernels move 16 bytes per lane from or to an aligned base and
+ *     fall back to element-wise moves otherwise (ssp_gru_forward writes an aligned seq_out in
+ *     place and copies any other out of its workspace), with bit-identical results.  No entry
+ *     point refuses an alignment (tests/test_gpu_alignment.py).  Host arrays are only ever read
+ *     and written with memcpy.
  *   - segment offsets (per-utterance sample / frame offsets) are small host-side metadata:
  *     they are always HOST int64 arrays and are uploaded once into an ssp_segments handle.
  *   - one ssp_ctx = one HIP device + one stream.  A ctx is not thread-safe; distinct ctxs are.

@@ -945,8 +945,9 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the table is written (LDS operations of a wave execute in order)
-            // the utterance's rows once more: 16 loads in flight per lane (through L2: glc), 8 bytes per lane when rows are 8-byte
-            // aligned (an even number of columns)
+            // the utterance's rows once more: 16 loads in flight per lane (through L2: glc), 8 bytes per lane when the number of columns
+            // is even.  A row is then a multiple of 8 bytes from the output base, which itself needs dword alignment only: on a base 4
+            // or 12 bytes past a 16-byte line the 8-byte buffer accesses run at 4-byte aligned addresses, with the same bits
             const int tot = T * Dd;
             auto rewrite = [&](auto wtag) {
                 constexpr int W = decltype(wtag)::value, B = 16;
