@@ -49,9 +49,20 @@ def _as_samples(x, name):
     return _as_f32(x, name) + (False,)
 
 
+def _current_raw_stream(device: int) -> int:
+    """torch's current hipStream_t on ``device`` as an integer (0 = the default stream).  Every device-pointer call asks, so the short
+    way is taken where torch has it: no Stream object is built."""
+    import torch
+    try:
+        return int(torch._C._cuda_getCurrentRawStream(device))
+    except AttributeError:
+        return int(torch.cuda.current_stream(device).cuda_stream)
+
+
 class Context:
     """One HIP device + one stream (ssp_ctx).  stream=None: the library owns a stream; an int is a borrowed
-    hipStream_t (e.g. torch.cuda.current_stream().cuda_stream; 0 = the HIP default stream)."""
+    hipStream_t (e.g. torch.cuda.current_stream().cuda_stream; 0 = the HIP default stream).  Device-pointer calls are ordered
+    against torch's current stream whichever stream the context runs on (_ordered)."""
 
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self._lib = _lib.load()
@@ -79,25 +90,30 @@ class Context:
 
     @contextlib.contextmanager
     def _ordered(self, where):
-        """Stream ordering around a call that takes device pointers.  A context that BORROWS torch's stream needs none (the kernels
-        are queued behind the producers of their inputs and ahead of the consumers of their outputs).  A context that owns its
-        stream is ordered against nothing torch does, so around a device-pointer call its stream first waits for torch's current
-        stream and torch's current stream then waits for it — two events, no host wait (ssp_ctx_wait_stream / _signal_stream): calls
-        on different owned-stream contexts overlap, and the host runs ahead as it does with torch's own kernels."""
-        own = where == _lib.DEVICE and self.stream is None
-        ts = None
-        host_sync = own and bool(os.environ.get("SSP_ORDER_SYNC"))  # (diagnostic: host waits on both sides, as before round 3)
-        if own:
-            import torch
+        """Stream ordering around a call that takes device pointers.  The contract: the call sees everything queued on torch's CURRENT
+        stream (of this device) at the time of the call, and work queued on that stream after the call returns sees the call's results.
+        A context whose stream IS torch's current stream needs nothing for that (the kernels are queued behind the producers of their
+        inputs and ahead of the consumers of their outputs): no event, no host wait.  Any other context — one that owns its stream, or
+        one that borrowed a torch stream which is not the current one any more (a cached default_context(torch_stream=True) called
+        under ``with torch.cuda.stream(s)``) — is ordered against nothing torch does now, so around the call its stream first waits
+        for torch's current stream and torch's current stream then waits for it: two events, no host wait (ssp_ctx_wait_stream /
+        _signal_stream).  Calls on different owned-stream contexts overlap, and the host runs ahead as it does with torch's own kernels."""
+        order, ts = False, None
+        if where == _lib.DEVICE:
+            cur = _current_raw_stream(self.device)
+            order = self.stream is None or int(self.stream) != cur
+        host_sync = order and bool(os.environ.get("SSP_ORDER_SYNC"))  # (diagnostic: host waits on both sides, as before round 3)
+        if order:
             if host_sync:
+                import torch
                 torch.cuda.current_stream(self.device).synchronize()
             else:
-                ts = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                ts = C.c_void_p(cur)
                 _lib.check(self._lib.ssp_ctx_wait_stream(self._h, ts))
         try:
             yield
         finally:
-            if own:
+            if order:
                 if host_sync:
                     self.sync()
                 else:

@@ -60,7 +60,9 @@ class DenseNet:
                                                 None if b is None else np.asarray(b, dtype=np.float32), act == 'relu') for W, b, act in layers])
 
     def predict(self, X, batch_size=None):
-        """X (N, input_dim) numpy or torch CUDA tensor -> (N, output_dim) of the same kind (numpy in: float32 out)."""
+        """X (N, input_dim) numpy or torch CUDA tensor -> (N, output_dim) of the same kind (numpy in: float32 out).  Under
+        ``with torch.cuda.stream(s)`` the copies of the numpy route run on s and the kernels on the cached context's stream:
+        api.Context._ordered orders the two, here and in the other networks."""
         import torch
         is_t = api._is_torch(X)
         h = X if is_t else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda(self.layers[0][0].device)
