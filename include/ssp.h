@@ -61,6 +61,7 @@ typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
+typedef struct ssp_dnn_trainer ssp_dnn_trainer; /* a fully connected network with its gradients and Adam state, for training */
 
 /* MFCC dialect knobs.  Three presets are built by the host side:
  *   in-repo  utils/processing.py:19-144  (Hamming, |X|/L, 40 talkbox filters folded, log10(.+1e-8), c0..c12)
@@ -431,6 +432,58 @@ int ssp_conv2d_same_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t T, 
 /* K.l2_normalize(x, axis=1) (d_vector.py:243-246): Y = X / sqrt(max(sum_k X_k^2, eps)) per row (Keras' eps: 1e-12; an all-zero row stays
  * zero).  X, Y: float[N x d]; Y may be X. */
 int ssp_l2_normalize(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, float eps, float* Y, int where, float* kernel_ms);
+
+/* ---- d-vector network training (since without a version step, like the LSTM and GRU entries): nn_model.inference, d_vector.py:168-206 —
+ *      the Sequential of Dense / ReLU / Dropout layers :171-194, categorical cross-entropy and Adam(lr=1e-4) :198-203, spk.fit(batch_size
+ *      128, epochs 50, shuffled) :205-206.  ReduceLROnPlateau :200, CSVLogger :201 and spkModel.save :210 stay with the host side
+ *      (d_vector.nn_model.inference).  Unpinned: the reference tree holds no weights, logs or outputs of this network and Keras is not a
+ *      dependency; the arithmetic below is restated from Keras 2's sources and corroborated against torch.autograd only.  All fp32, the
+ *      products on the exact-fp32 MFMA; no floating-point atomics: the same seed, data and order give the same bits.
+ *        Dense    layer l: y = act(x W_l + b_l), W_l in Keras' (d_in, units) layout; the caller initialises (Keras' Dense defaults are
+ *                 glorot_uniform kernels and zero biases; d_vector.nn_model.inference draws them from a seeded numpy generator).
+ *        Dropout  after layer l's activation, inverted as in Keras: a kept unit is scaled by 1 / (1 - rate), the others are zero, rate 0
+ *                 is the identity.  The decision is counter-based and stateless — a pure function of (seed, step, layer, row inside the
+ *                 batch, column), step = the number of steps the trainer had taken before this one:
+ *                   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16           (32-bit, wrapping)
+ *                   key = mix(mix(mix(mix(mix(0x9e3779b9 ^ seed_lo) ^ seed_hi) ^ step_lo) ^ step_hi) ^ layer)
+ *                   keep(row, col) = (mix(key ^ (row * 4096 + col)) >> 8) >= floor(rate * 2^24)
+ *                 It is recomputed in the backward pass, never stored.
+ *        Loss     softmax and cross-entropy together on the logits: row maximum subtracted, log-sum-exp.  Keras' clipping of the
+ *                 probabilities to [1e-7, 1 - 1e-7] is NOT reproduced (it only matters when a probability underflows 1e-7).  The
+ *                 gradient at the logits is (softmax - onehot) / B with B the actual size of that batch: the last batch of an epoch has
+ *                 N % batch_size rows, as Keras runs it.  Accuracy counts rows whose arg-max (first index on ties) is the label.
+ *        Adam     Keras 2's form, beta1 0.9, beta2 0.999, eps 1e-7 (K.epsilon()) OUTSIDE the root, t counted from 1 over the whole fit:
+ *                   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t);  p -= lr_t m / (sqrt(v) + eps)
+ *                 (not torch's placement of eps).  One launch over all parameters: they, the gradients, m and v are one flat buffer each. ---- */
+/* dims: HOST int32[n_layers + 1]; relu[l] != 0: ReLU after layer l; dropout_rate[l] in [0, 1): dropout after layer l's activation;
+ * W[l]: HOST float[dims[l] x dims[l + 1]]; bias: NULL, or bias[l]: HOST float[dims[l + 1]] or NULL (a layer without bias).  The last
+ * width is n_class (>= 2).  Widths up to 4096 and max_batch up to 1024, else SSP_ERR_UNSUPPORTED; a null kernel or a rate outside [0, 1)
+ * answers SSP_ERR_INVALID; both before any GPU work. */
+int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const int32_t* relu, const float* dropout_rate,
+                           const float* const* W, const float* const* bias, int32_t max_batch, ssp_dnn_trainer** out);
+int ssp_dnn_trainer_destroy(ssp_dnn_trainer* trainer);
+/* One pass of spk.fit over the data (d_vector.py:205-206): ceil(N / batch_size) steps of forward with dropout, loss, backward and Adam at
+ * learning rate lr.  X: float[N x dims[0]], labels: int32[N], on the side `where` names; order: HOST int64[N] (step s takes rows
+ * order[s batch_size ..]) or NULL for 0..N-1.  The steps are queued on the ctx stream without a host wait; every step leaves its loss
+ * sum and its count of correct rows in a slot of a device array, which is read back ONCE at the end and added on the host in float64 in
+ * step order: loss_sum = sum over rows of the loss as the steps ran (dropout on, weights moving), n_correct likewise (both nullable).
+ * The step counter t continues across calls: an epoch equals its steps issued one batch per call, bit for bit.  SSP_ERR_INVALID before
+ * any GPU work: batch_size outside [1, max_batch], an order entry outside [0, N), a label outside [0, n_class) in a HOST array (on the
+ * device a label out of range is not read as an index: its row counts as wrong and its loss is the log-sum-exp of its logits).
+ * t advances with every step queued: a call that fails half way leaves t in step with the weights it has moved. */
+int ssp_dnn_trainer_epoch(ssp_dnn_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
+                          float lr, uint64_t seed, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms);
+/* the validation pass of spk.fit (d_vector.py:205): dropout off, nothing updated (weights, gradients, m, v and t keep their values) */
+int ssp_dnn_trainer_evaluate(ssp_dnn_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
+                             int where, float* kernel_ms);
+/* layer's kernel (dims[l] x dims[l + 1]) or bias (dims[l + 1]) of: the parameters, the LAST step's gradients, Adam's m and v.
+ * out: HOST.  Waits for the ctx stream.  A bias of a layer created without one answers SSP_ERR_INVALID. */
+enum { SSP_DNN_W = 0, SSP_DNN_B = 1, SSP_DNN_DW = 2, SSP_DNN_DB = 3, SSP_DNN_M_W = 4, SSP_DNN_M_B = 5, SSP_DNN_V_W = 6, SSP_DNN_V_B = 7 };
+int ssp_dnn_trainer_read(ssp_dnn_trainer* trainer, int32_t what, int32_t layer, float* out);
+int ssp_dnn_trainer_steps(const ssp_dnn_trainer* trainer, int64_t* t); /* steps taken so far (Adam's t) */
+/* the dropout generator itself, on the host (no device, no ctx; like ssp_lstm_pack_weights): keep_out HOST uint8[rows x width] = 1 where
+ * the unit is kept.  rows up to 1024, width up to 4096. */
+int ssp_dropout_keep(uint64_t seed, int64_t step, int32_t layer, int32_t rows, int32_t width, float rate, uint8_t* keep_out);
 
 /* ---- d-vector cosine scoring: replaces the scipy cosine double loop + argmin
  *      (d_vector.py:315-319, 346-361) ---- */

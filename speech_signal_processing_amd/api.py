@@ -865,6 +865,114 @@ class DnnForward:
             pass
 
 
+class DnnTrainer:
+    """A fully connected network with its gradients and Adam state on the GPU (ssp_dnn_trainer): nn_model.inference's spk.fit,
+    d_vector.py:168-206.  ``layers`` = list of (W (d_in, units) float32 in Keras' layout, bias (units,) or None, relu bool, dropout rate
+    after the activation).  X and labels are numpy arrays (host) or torch CUDA tensors (X float32, labels int32)."""
+
+    WHAT = {"W": 0, "b": 1, "dW": 2, "db": 3, "mW": 4, "mb": 5, "vW": 6, "vb": 7}
+
+    def __init__(self, ctx: Context, layers, max_batch: int = 128):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        n = len(layers)
+        if n < 1:
+            raise ValueError("at least one layer")
+        ws = [np.ascontiguousarray(w, dtype=np.float32) for w, _, _, _ in layers]
+        bs = [None if b is None else np.ascontiguousarray(b, dtype=np.float32).reshape(-1) for _, b, _, _ in layers]
+        if any(w.ndim != 2 for w in ws):
+            raise ValueError("kernels must be (d_in, units)")
+        dims = [int(ws[0].shape[0])] + [int(w.shape[1]) for w in ws]
+        for i, w in enumerate(ws):
+            if w.shape[0] != dims[i] or (bs[i] is not None and bs[i].shape[0] != dims[i + 1]):
+                raise ValueError("layer %d: kernel (d_in, units) / bias (units,) do not chain" % i)
+        self.dims, self.has_bias, self.max_batch = dims, [b is not None for b in bs], int(max_batch)
+        c_dims = (C.c_int32 * (n + 1))(*dims)
+        c_r = (C.c_int32 * n)(*[1 if r else 0 for _, _, r, _ in layers])
+        c_p = (C.c_float * n)(*[float(p) for _, _, _, p in layers])
+        c_w = (C.c_void_p * n)(*[w.ctypes.data for w in ws])
+        c_b = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in bs])
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_dnn_trainer_create(ctx._h, n, c_dims, c_r, c_p, c_w, c_b, int(max_batch), C.byref(h)))
+        self._h = h
+
+    def _data(self, X, labels):
+        xk, xp, where = _as_f32(X, "X")
+        if xk.ndim != 2 or int(xk.shape[1]) != self.dims[0]:
+            raise ValueError("X must be (N, %d)" % self.dims[0])
+        if where == _lib.DEVICE:
+            import torch
+            if not (_is_torch(labels) and labels.is_cuda):
+                raise ValueError("labels must live where X lives")
+            lk = labels.to(torch.int32).contiguous()
+            lp = lk.data_ptr()
+        else:
+            lk = np.ascontiguousarray(labels, dtype=np.int32)
+            lp = lk.ctypes.data
+        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
+            raise ValueError("one label per row of X")
+        return (xk, lk), xp, lp, int(xk.shape[0]), where
+
+    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, seed: int = 0, timing: bool = False):
+        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
+        as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        ok, op = None, None
+        if order is not None:
+            ok = np.ascontiguousarray(order, dtype=np.int64)
+            if ok.shape != (N,):
+                raise ValueError("order must hold N row indices")
+            op = ok.ctypes.data
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_dnn_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), int(seed) & (2 ** 64 - 1),
+                                                       C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def evaluate(self, X, labels, timing: bool = False):
+        """loss sum and correct rows over (X, labels) with dropout off; nothing is updated"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_dnn_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def read(self, what: str, layer: int):
+        """'W', 'b' (parameters), 'dW', 'db' (the last step's gradients), 'mW', 'mb', 'vW', 'vb' (Adam's moments) of ``layer`` -> numpy"""
+        layer = int(layer)
+        if not 0 <= layer < len(self.dims) - 1:
+            raise ValueError("layer %d of %d" % (layer, len(self.dims) - 1))
+        code = self.WHAT[what]
+        out = np.empty((self.dims[layer + 1],) if code & 1 else (self.dims[layer], self.dims[layer + 1]), dtype=np.float32)
+        _lib.check(self._lib.ssp_dnn_trainer_read(self._h, code, layer, out.ctypes.data))
+        return out
+
+    @property
+    def steps(self) -> int:
+        t = C.c_int64(0)
+        _lib.check(self._lib.ssp_dnn_trainer_steps(self._h, C.byref(t)))
+        return t.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_dnn_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dropout_keep(seed: int, step: int, layer: int, rows: int, width: int, rate: float):
+    """the trainer's dropout decision (ssp_dropout_keep; computed on the host, no device): bool (rows, width), True = kept"""
+    out = np.empty((int(rows), int(width)), dtype=np.uint8)
+    lib = _lib.load()
+    _lib.check(lib.ssp_dropout_keep(int(seed) & (2 ** 64 - 1), int(step), int(layer), int(rows), int(width), float(rate), out.ctypes.data))
+    return out.astype(bool)
+
+
 LSTM_ACTIVATIONS = {"hard_sigmoid": 0, "sigmoid": 1}
 
 

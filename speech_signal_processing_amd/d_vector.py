@@ -3,7 +3,9 @@
 the Sequential built at d_vector.py:171-189), the forward pass of the recurrent one (``LstmNet.predict``: the LSTM(128) of
 d_vector.py:271-294, the network nn_model.enroll / eval load by default), the forward pass of the conv + GRU one (``ConvGruNet.predict``:
 Conv2D -> 3 x GRU(1024) -> mean over time -> Dense(512) -> L2 normalisation, d_vector.py:213-269, the network d_vector.py:389 evaluates)
-and nn_model.test / enroll / eval (d_vector.py:296-361).  Training the Keras networks is out of scope: weights are inputs.
+and nn_model.test / enroll / eval (d_vector.py:296-361), and the training of the fully connected network (``nn_model.inference``,
+d_vector.py:168-210: forward with dropout, softmax cross-entropy, backward and Adam on the GPU, api.DnnTrainer).  Training the two
+recurrent networks is out of scope: their weights are inputs.
 The recurrent networks are UNPINNED: the reference tree holds no weights or outputs for them and Keras is not a dependency; their
 arithmetic is restated from Keras' documentation and corroborated against torch's cells only."""
 from __future__ import annotations
@@ -447,7 +449,7 @@ class Data_gen:
 
 
 class nn_model:
-    """Inference half of d_vector.nn_model.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
+    """d_vector.nn_model: ``inference`` trains the fully connected network; test / enroll / eval score.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
     stand-in for load_model('feature/d_vector/d_vector_{}.h5')) is given.  ``store``: path of the enrolment dictionary pickle
     (the reference always uses 'feature/d_vector/d_vector.pkl', d_vector.py:333-344,350-351); None keeps it in memory."""
 
@@ -475,6 +477,69 @@ class nn_model:
                 os.makedirs(d)
             with open(self.store, 'wb') as f:
                 pkl.dump(self.d_vector, f)
+
+    #: dropout after each of the five Dense layers (d_vector.py:175, 179, 183, 192; none behind the softmax layer)
+    DROPOUT = (0.0, 0.0, 0.5, 0.5, 0.0)
+    LOG_HEADER = "epoch,acc,loss,lr,val_acc,val_loss"  # Keras 2.2's CSVLogger columns, in its sorted order
+
+    def inference(self, X_train, Y_train, X_val, Y_val, *, epochs=50, batch_size=128, lr=1e-4, seed=0, model_dir=None):
+        """d_vector.py:168-210, same positional signature: train Dense(256) ReLU x 3, Dense(256) | ReLU Dropout(0.5) Dense(n_class)
+        softmax with categorical cross-entropy and Adam on the GPU (api.DnnTrainer), ReduceLROnPlateau(val_loss, factor 0.5, patience 2,
+        min_lr 1e-7, Keras 2's min_delta 1e-4) on the host, one row per epoch in {model_dir}/nn_training.log, and the first four layers
+        (spkModel) saved as {model_dir}/d_vector_nn.npz and registered under 'nn'.  One numpy generator seeded with ``seed`` draws the
+        glorot_uniform kernels (zero biases: Keras' Dense defaults) layer by layer and then one permutation of the rows per epoch; the
+        same ``seed`` keys the dropout.  One-hot Y is decoded with argmax.  The defaults are the reference's.  Returns the history as a
+        dict of lists (acc, loss, lr, val_acc, val_loss; ``loss`` / ``acc`` are the means over the epoch's steps as they ran,
+        ``val_*`` a pass without dropout after it, ``lr`` what the epoch ran with)."""
+        print("Training model")
+        model_dir = MODEL_DIR if model_dir is None else model_dir
+        X_train, X_val = np.ascontiguousarray(X_train, dtype=np.float32), np.ascontiguousarray(X_val, dtype=np.float32)
+        y_train, y_val = (np.argmax(np.asarray(Y), axis=1).astype(np.int32) for Y in (Y_train, Y_val))
+        if X_train.ndim != 2 or X_val.ndim != 2 or X_val.shape[1] != X_train.shape[1] or len(y_train) != len(X_train) or len(y_val) != len(X_val):
+            raise ValueError("X (N, d) and one-hot Y (N, n_class) must agree")
+        if max(int(y_train.max(initial=0)), int(y_val.max(initial=0))) >= int(self.n_class):
+            raise ValueError("a label lies outside n_class = %d" % self.n_class)
+        dims = [int(X_train.shape[1]), 256, 256, 256, 256, int(self.n_class)]
+        rng = np.random.default_rng(seed)
+        layers = []
+        for l, (d_in, units) in enumerate(zip(dims[:-1], dims[1:])):
+            lim = np.sqrt(6.0 / (d_in + units))
+            layers.append((rng.uniform(-lim, lim, (d_in, units)).astype(np.float32), np.zeros(units, np.float32), l < len(dims) - 2, self.DROPOUT[l]))
+        import torch
+        ctx = api.default_context()
+        net = api.DnnTrainer(ctx, layers, max_batch=max(1, min(1024, max(int(batch_size), 256))))
+        dev = "cuda:%d" % ctx.device
+        xt, yt = torch.from_numpy(X_train).to(dev), torch.from_numpy(y_train).to(dev)   # the data stays on the device over the epochs
+        xv, yv = torch.from_numpy(X_val).to(dev), torch.from_numpy(y_val).to(dev)
+        hist = {k: [] for k in ("acc", "loss", "lr", "val_acc", "val_loss")}
+        lr = float(np.float32(lr))   # (Keras keeps lr in a float32 variable)
+        best, wait, factor, patience, min_lr, min_delta = np.inf, 0, 0.5, 2, 1e-7, 1e-4
+        os.makedirs(model_dir, exist_ok=True)
+        with open(os.path.join(model_dir, "nn_training.log"), "w") as log:
+            log.write(self.LOG_HEADER + "\n")
+            for epoch in range(int(epochs)):
+                order = rng.permutation(len(y_train))
+                loss, correct = net.epoch(xt, yt, order, batch_size=batch_size, lr=lr, seed=seed)
+                vloss, vcorrect = net.evaluate(xv, yv) if len(y_val) else (float("nan"), 0)
+                row = {"acc": correct / max(len(y_train), 1), "loss": loss / max(len(y_train), 1), "lr": lr,
+                       "val_acc": vcorrect / max(len(y_val), 1), "val_loss": vloss / max(len(y_val), 1)}
+                for k, v in row.items():
+                    hist[k].append(v)
+                log.write(",".join([str(epoch)] + [repr(float(row[k])) for k in ("acc", "loss", "lr", "val_acc", "val_loss")]) + "\n")
+                log.flush()
+                # ReduceLROnPlateau.on_epoch_end (Keras 2, mode min, cooldown 0)
+                if row["val_loss"] < best - min_delta:
+                    best, wait = row["val_loss"], 0
+                else:
+                    wait += 1
+                    if wait >= patience and lr > min_lr:
+                        lr = float(np.float32(max(lr * factor, min_lr)))
+                        wait = 0
+        spk = DenseNet([(net.read("W", l), net.read("b", l), 'relu' if l < 3 else 'linear') for l in range(4)], device=ctx.device)
+        save_model(spk, 'nn', model_dir)
+        register_model('nn', spk)
+        self.trainer_ = net
+        return hist
 
     def test(self, X_train, Y_train, X_val, Y_val, model_name=_UNSET, spk_model=None):
         """d_vector.py:296-320, same positional signature: X = spkModel.predict(X) with the network ``model_name`` names (default
