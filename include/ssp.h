@@ -485,6 +485,65 @@ int ssp_dnn_trainer_steps(const ssp_dnn_trainer* trainer, int64_t* t); /* steps 
  * the unit is kept.  rows up to 1024, width up to 4096. */
 int ssp_dropout_keep(uint64_t seed, int64_t step, int32_t layer, int32_t rows, int32_t width, float rate, uint8_t* keep_out);
 
+/* ---- recurrent d-vector network training (since without a version step, like the entries above): nn_model.inference_lstm,
+ *      d_vector.py:271-294 — LSTM(128) over the (T, d_in) chunk :274, Dense(n_class) softmax on the last hidden state :278, categorical
+ *      cross-entropy and Adam(lr=1e-4) :281-284, spk.fit(batch_size 128, epochs 50, shuffled) :289-290.  ReduceLROnPlateau :286, CSVLogger
+ *      :287 and spkModel.save :294 stay with the host side (d_vector.nn_model.inference_lstm).  Unpinned: the reference tree holds no
+ *      weights, logs or outputs of this network and Keras is not a dependency; the arithmetic is restated and corroborated against
+ *      torch.autograd only.  All fp32, the products on the exact-fp32 MFMA.
+ *        Network  one LSTM(units) over a fixed-length chunk; Keras' cell exactly as stated for ssp_lstm_forward above (gate blocks
+ *                 i | f | c | o, zero initial state, no mask; recurrent_activation 0 hard_sigmoid | 1 sigmoid); the last hidden state
+ *                 feeds Dense(n_class) and a softmax.  No dropout, no recurrent dropout, no gradient clipping.
+ *        Loss, accuracy, Adam: the dense trainer's, in the words of the section above — softmax and cross-entropy together on the
+ *                 logits, the gradient at the logits (softmax - onehot) / B with B the actual batch (the tail batch included), Keras 2's
+ *                 Adam with eps 1e-7 outside the root and t counted over the whole fit, one Adam launch over flat parameter, gradient, m
+ *                 and v buffers (W | U | b | Wd | bd).
+ *        Backward through time, for t = T-1 .. 0, dh starting as dlogits Wd^T and dc at 0:
+ *                   do = dh tanh(c_t);  dc += dh o (1 - tanh^2(c_t))
+ *                   dz = [dc g s'(i) | dc c_{t-1} s'(f) | dc i (1 - g^2) | do s'(o)]
+ *                   dW += x_t^T dz;  dU += h_{t-1}^T dz;  db += sum over rows of dz;  dh = dz U^T;  dc = dc f
+ *                 sigmoid: s'(s) = s (1 - s).  hard_sigmoid: s' = 0.2 where the fp32 activation lies strictly inside (0, 1) and 0
+ *                 elsewhere (Keras' clip passes no gradient at or beyond the bounds).
+ *        Determinism: no floating-point atomic anywhere.  A sequence is one MFMA column in both recurrent kernels; the sums over the
+ *                 B T rows in dW / dU / db, the split of K over waves and the loss have a fixed partition and a fixed order: the same
+ *                 seed, data and order give the same bits.
+ *      The forward kernel gives a workgroup 16 sequences and each of its units / 16 waves one hidden tile whose slice of [W; U] stays in
+ *      registers over the T steps, x_t and h_{t-1} in LDS, one barrier per step; it stashes x_t, h_t, c_t and the gate activations per
+ *      (row, t) in a workspace allocated at create (T max_batch (d_in + 6 units) floats).  The backward kernel runs the same
+ *      decomposition in reverse and leaves dz in the stash; the weight gradients are GEMMs over it. ---- */
+/* W: HOST float[d_in x 4 units], U: HOST float[units x 4 units], bias: HOST float[4 units] or NULL (Keras layout, as ssp_lstm_create);
+ * Wd: HOST float[units x n_class], bd: HOST float[n_class] or NULL.  units: a multiple of 16 up to 128, d_in up to 64 (as for the forward
+ * pass), T in [1, 1024], n_class in [2, 4096], max_batch in [1, 1024], else SSP_ERR_UNSUPPORTED; a null W / U / Wd or a bad activation
+ * code answers SSP_ERR_INVALID; both before any GPU work. */
+typedef struct ssp_lstm_trainer ssp_lstm_trainer;
+int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n_class, int32_t T, int32_t recurrent_activation, const float* W,
+                            const float* U, const float* bias, const float* Wd, const float* bd, int32_t max_batch, ssp_lstm_trainer** out);
+int ssp_lstm_trainer_destroy(ssp_lstm_trainer* trainer);
+/* One pass of spk.fit over the data (d_vector.py:289-290): ceil(N / batch_size) steps of forward, loss, backward and Adam at learning rate
+ * lr.  X: float[N x T x d_in], labels: int32[N], on the side `where` names; order: HOST int64[N] (step s takes rows order[s batch_size ..],
+ * gathered inside the kernel's loads) or NULL for 0..N-1.  The steps are queued on the ctx stream without a host wait; every step leaves
+ * its loss sum and its count of correct rows in a slot of a device array, which is read back ONCE at the end and added on the host in
+ * float64 in step order (both nullable).  The step counter t continues across calls: an epoch equals its steps issued one batch per call,
+ * bit for bit.  SSP_ERR_INVALID before any GPU work: batch_size outside [1, max_batch], an order entry outside [0, N), a label outside
+ * [0, n_class) in a HOST array (on the device a label out of range is not read as an index: its row counts as wrong and its loss is the
+ * log-sum-exp of its logits).  t advances with every step queued. */
+int ssp_lstm_trainer_epoch(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
+                           float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms);
+/* the validation pass of spk.fit (d_vector.py:289): the forward kernel without the stash; nothing is updated (weights, gradients, m, v and t
+ * keep their values) */
+int ssp_lstm_trainer_evaluate(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
+                              int where, float* kernel_ms);
+/* `tensor` (W: d_in x 4 units, U: units x 4 units, B: 4 units, WD: units x n_class, BD: n_class) of: the parameters, the LAST step's
+ * gradients, Adam's m and v.  out: HOST.  Waits for the ctx stream.  A bias the network was created without answers SSP_ERR_INVALID. */
+enum { SSP_LSTM_PARAM = 0, SSP_LSTM_GRAD = 1, SSP_LSTM_M = 2, SSP_LSTM_V = 3 };
+enum { SSP_LSTM_W = 0, SSP_LSTM_U = 1, SSP_LSTM_B = 2, SSP_LSTM_WD = 3, SSP_LSTM_BD = 4 };
+int ssp_lstm_trainer_read(ssp_lstm_trainer* trainer, int32_t what, int32_t tensor, float* out);
+int ssp_lstm_trainer_steps(const ssp_lstm_trainer* trainer, int64_t* t); /* steps taken so far (Adam's t) */
+/* measurement aid (tools/bench_lstm_train.py): ONE training step on the first batch_size rows of DEVICE arrays with a hipEvent between its
+ * nine launches, then a host wait.  ms_out: HOST float[9] — forward with stash, Dense head, loss, dWd, dh_T, backward through time, dW + db,
+ * dU, Adam.  The step counts: weights, m, v and t move as in ssp_lstm_trainer_epoch. */
+int ssp_lstm_trainer_step_times(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int32_t batch_size, float lr, float* ms_out);
+
 /* ---- d-vector cosine scoring: replaces the scipy cosine double loop + argmin
  *      (d_vector.py:315-319, 346-361) ---- */
 /* X: float[N x d]; C: float[S x d]; dist_out (nullable): float[N x S] = clip(1 - cos, 0, 2);

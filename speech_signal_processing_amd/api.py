@@ -1056,6 +1056,125 @@ class LstmForward:
             pass
 
 
+class LstmTrainer:
+    """The recurrent d-vector network with its gradients and Adam state on the GPU (ssp_lstm_trainer): nn_model.inference_lstm's spk.fit,
+    d_vector.py:271-294 — one LSTM(units) over a (T, d_in) chunk, Dense(n_class) and a softmax on the last hidden state.  W (d_in, 4 units),
+    U (units, 4 units), b (4 units,) or None, Wd (units, n_class), bd (n_class,) or None in Keras' layout; ``recurrent_activation``
+    'hard_sigmoid' or 'sigmoid', named by the caller.  X (N, T, d_in) and labels are numpy arrays (host) or torch CUDA tensors (X float32,
+    labels int32).  units: a multiple of 16 up to 128, d_in up to 64, T up to 1024 (NotImplementedError otherwise)."""
+
+    WHAT = {"": 0, "d": 1, "m": 2, "v": 3}
+    TENSOR = {"W": 0, "U": 1, "b": 2, "Wd": 3, "bd": 4}
+
+    def __init__(self, ctx: Context, W, U, b, Wd, bd, *, T, recurrent_activation, max_batch: int = 128):
+        if recurrent_activation not in LSTM_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        self.ctx = ctx
+        self._lib = ctx._lib
+        W, U, b = _lstm_arrays(W, U, b)
+        Wd = np.ascontiguousarray(Wd, dtype=np.float32)
+        bd = None if bd is None else np.ascontiguousarray(bd, dtype=np.float32).reshape(-1)
+        if Wd.ndim != 2 or Wd.shape[0] != U.shape[0] or (bd is not None and bd.shape[0] != Wd.shape[1]):
+            raise ValueError("Wd must be (units, n_class) and bd (n_class,)")
+        self.d_in, self.units, self.n_class, self.T = int(W.shape[0]), int(U.shape[0]), int(Wd.shape[1]), int(T)
+        self.recurrent_activation, self.max_batch = recurrent_activation, int(max_batch)
+        self.has_bias = {"b": b is not None, "bd": bd is not None}
+        self.shapes = {"W": (self.d_in, 4 * self.units), "U": (self.units, 4 * self.units), "b": (4 * self.units,),
+                       "Wd": (self.units, self.n_class), "bd": (self.n_class,)}
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_lstm_trainer_create(ctx._h, self.d_in, self.units, self.n_class, self.T, LSTM_ACTIVATIONS[recurrent_activation],
+                                                     W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data, Wd.ctypes.data,
+                                                     None if bd is None else bd.ctypes.data, int(max_batch), C.byref(h)))
+        self._h = h
+
+    def _data(self, X, labels):
+        xk, xp, where = _as_f32(X, "X")
+        if xk.ndim != 3 or int(xk.shape[1]) != self.T or int(xk.shape[2]) != self.d_in:
+            raise ValueError("X must be (N, %d, %d)" % (self.T, self.d_in))
+        if where == _lib.DEVICE:
+            import torch
+            if not (_is_torch(labels) and labels.is_cuda):
+                raise ValueError("labels must live where X lives")
+            lk = labels.to(torch.int32).contiguous()
+            lp = lk.data_ptr()
+        else:
+            lk = np.ascontiguousarray(labels, dtype=np.int32)
+            lp = lk.ctypes.data
+        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
+            raise ValueError("one label per row of X")
+        return (xk, lk), xp, lp, int(xk.shape[0]), where
+
+    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
+        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
+        as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        ok, op = None, None
+        if order is not None:
+            ok = np.ascontiguousarray(order, dtype=np.int64)
+            if ok.shape != (N,):
+                raise ValueError("order must hold N row indices")
+            op = ok.ctypes.data
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_lstm_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), C.byref(loss), C.byref(corr), where,
+                                                        C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def evaluate(self, X, labels, timing: bool = False):
+        """loss sum and correct rows over (X, labels); nothing is updated"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_lstm_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    STEP_LAUNCHES = ("forward+stash", "dense head", "loss", "dWd", "dh_T", "backward through time", "dW+db", "dU", "adam")
+
+    def step_times(self, X, labels, batch_size: int = 128, lr: float = 1e-4):
+        """ONE training step on the first ``batch_size`` rows of torch CUDA tensors with a hipEvent between its nine launches ->
+        {launch name: milliseconds} (a measurement aid: the step counts like any other)"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        if where != _lib.DEVICE or N < int(batch_size):
+            raise ValueError("step_times takes torch CUDA tensors of at least batch_size rows")
+        ms = (C.c_float * len(self.STEP_LAUNCHES))()
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_lstm_trainer_step_times(self._h, xp, lp, int(batch_size), float(lr), ms))
+        return dict(zip(self.STEP_LAUNCHES, (float(v) for v in ms)))
+
+    def read(self, what: str, out=None):
+        """'W', 'U', 'b', 'Wd', 'bd' (parameters), with a prefix 'd' (the last step's gradients), 'm' or 'v' (Adam's moments), e.g. 'dU',
+        'mWd' -> numpy; ``out``: a float32 array of the tensor's size to fill instead (it needs 4-byte alignment only)"""
+        for prefix in ("", "d", "m", "v"):
+            if what.startswith(prefix) and what[len(prefix):] in self.TENSOR and (prefix or what in self.TENSOR):
+                name = what[len(prefix):]
+                break
+        else:
+            raise ValueError("unknown tensor %r" % (what,))
+        if out is None:
+            out = np.empty(self.shapes[name], dtype=np.float32)
+        elif out.dtype != np.float32 or out.size != int(np.prod(self.shapes[name])) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float32 array of %d entries" % int(np.prod(self.shapes[name])))
+        _lib.check(self._lib.ssp_lstm_trainer_read(self._h, self.WHAT[prefix], self.TENSOR[name], out.ctypes.data))
+        return out
+
+    @property
+    def steps(self) -> int:
+        t = C.c_int64(0)
+        _lib.check(self._lib.ssp_lstm_trainer_steps(self._h, C.byref(t)))
+        return t.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_lstm_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 GRU_ACTIVATIONS = LSTM_ACTIVATIONS
 
 

@@ -615,3 +615,44 @@ int ssp_dnn_trainer_steps(const ssp_dnn_trainer* trainer, int64_t* t) {
 }
 
 }  // extern "C"
+
+// ---- the step kernels as plain launches for the other trainers (dnn_train.hpp)
+#include "dnn_train.hpp"
+
+namespace ssp {
+
+int dt_launch_gemm(int mode, const float* A, const float* B, float* C, const int64_t* idx, int32_t M, int32_t N, int32_t K, int64_t lda,
+                   const float* bias, float* db, hipStream_t s) {
+    GemmArgs a{};
+    a.A = A, a.B = B, a.C = C, a.idx = idx;
+    a.M = M, a.N = N, a.K = K, a.lda = lda;
+    a.bias = bias, a.db = db;
+    a.scale = 1.f;
+    if (mode == 0) return dt_gemm<0>(a, s);
+    if (mode == 1) return dt_gemm<1>(a, s);
+    if (mode == 2) return dt_gemm<2>(a, s);
+    SSP_FAIL(SSP_ERR_INVALID, "dt_launch_gemm: mode");
+}
+
+int dt_launch_loss(float* Z, const int32_t* labels, const int64_t* idx, int32_t B, int32_t C, int write_grad, float* rowloss, int32_t* rowcorr,
+                   uint32_t* ticket, float* loss_slot, int32_t* corr_slot, hipStream_t s) {
+    LossArgs a{};
+    a.Z = Z, a.labels = labels, a.idx = idx;
+    a.B = B, a.C = C, a.write_grad = write_grad ? 1 : 0;
+    a.inv_B = 1.f / (float)B;
+    a.rowloss = rowloss, a.rowcorr = rowcorr, a.ticket = ticket, a.loss_slot = loss_slot, a.corr_slot = corr_slot;
+    hipLaunchKernelGGL(dt_loss_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, a);
+    SSP_HIP(hipGetLastError());
+    return SSP_OK;
+}
+
+int dt_launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, int64_t t1, hipStream_t s) {
+    const double b1 = 0.9, b2 = 0.999;
+    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t1)) / (1.0 - std::pow(b1, (double)t1)));
+    hipLaunchKernelGGL(dt_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr_t, (float)b1, (float)(1.0 - b1),
+                       (float)b2, (float)(1.0 - b2), 1e-7f);
+    SSP_HIP(hipGetLastError());
+    return SSP_OK;
+}
+
+}  // namespace ssp

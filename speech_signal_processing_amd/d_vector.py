@@ -4,8 +4,10 @@ the Sequential built at d_vector.py:171-189), the forward pass of the recurrent 
 d_vector.py:271-294, the network nn_model.enroll / eval load by default), the forward pass of the conv + GRU one (``ConvGruNet.predict``:
 Conv2D -> 3 x GRU(1024) -> mean over time -> Dense(512) -> L2 normalisation, d_vector.py:213-269, the network d_vector.py:389 evaluates)
 and nn_model.test / enroll / eval (d_vector.py:296-361), and the training of the fully connected network (``nn_model.inference``,
-d_vector.py:168-210: forward with dropout, softmax cross-entropy, backward and Adam on the GPU, api.DnnTrainer).  Training the two
-recurrent networks is out of scope: their weights are inputs.
+d_vector.py:168-210: forward with dropout, softmax cross-entropy, backward and Adam on the GPU, api.DnnTrainer) and of the recurrent one
+(``nn_model.inference_lstm``, d_vector.py:271-294: recurrent forward with a stash, backward through time and Adam on the GPU,
+api.LstmTrainer; it writes d_vector_lstm.npz, which enroll / eval pick up).  Training the conv + GRU network is out of scope: its weights
+are inputs.
 The recurrent networks are UNPINNED: the reference tree holds no weights or outputs for them and Keras is not a dependency; their
 arithmetic is restated from Keras' documentation and corroborated against torch's cells only."""
 from __future__ import annotations
@@ -449,7 +451,8 @@ class Data_gen:
 
 
 class nn_model:
-    """d_vector.nn_model: ``inference`` trains the fully connected network; test / enroll / eval score.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
+    """d_vector.nn_model: ``inference`` trains the fully connected network, ``inference_lstm`` the recurrent one (the conv + GRU network is
+    not trained here); test / enroll / eval score.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
     stand-in for load_model('feature/d_vector/d_vector_{}.h5')) is given.  ``store``: path of the enrolment dictionary pickle
     (the reference always uses 'feature/d_vector/d_vector.pkl', d_vector.py:333-344,350-351); None keeps it in memory."""
 
@@ -482,6 +485,37 @@ class nn_model:
     DROPOUT = (0.0, 0.0, 0.5, 0.5, 0.0)
     LOG_HEADER = "epoch,acc,loss,lr,val_acc,val_loss"  # Keras 2.2's CSVLogger columns, in its sorted order
 
+    def _fit(self, net, xt, yt, xv, yv, rng, epochs, batch_size, lr, log_path, **epoch_args):
+        """spk.fit's loop around a trainer (api.DnnTrainer / api.LstmTrainer): one permutation of the rows from ``rng`` and one
+        ``net.epoch`` per epoch, the validation pass, one CSVLogger row in ``log_path`` and Keras 2's ReduceLROnPlateau(val_loss, factor
+        0.5, patience 2, min_lr 1e-7, min_delta 1e-4, mode min, cooldown 0) on the host -> the history as a dict of lists"""
+        n_train, n_val = int(yt.shape[0]), int(yv.shape[0])
+        hist = {k: [] for k in ("acc", "loss", "lr", "val_acc", "val_loss")}
+        lr = float(np.float32(lr))   # (Keras keeps lr in a float32 variable)
+        best, wait, factor, patience, min_lr, min_delta = np.inf, 0, 0.5, 2, 1e-7, 1e-4
+        os.makedirs(os.path.dirname(log_path) or ".", exist_ok=True)
+        with open(log_path, "w") as log:
+            log.write(self.LOG_HEADER + "\n")
+            for epoch in range(int(epochs)):
+                order = rng.permutation(n_train)
+                loss, correct = net.epoch(xt, yt, order, batch_size=batch_size, lr=lr, **epoch_args)
+                vloss, vcorrect = net.evaluate(xv, yv) if n_val else (float("nan"), 0)
+                row = {"acc": correct / max(n_train, 1), "loss": loss / max(n_train, 1), "lr": lr,
+                       "val_acc": vcorrect / max(n_val, 1), "val_loss": vloss / max(n_val, 1)}
+                for k, v in row.items():
+                    hist[k].append(v)
+                log.write(",".join([str(epoch)] + [repr(float(row[k])) for k in ("acc", "loss", "lr", "val_acc", "val_loss")]) + "\n")
+                log.flush()
+                # ReduceLROnPlateau.on_epoch_end (Keras 2, mode min, cooldown 0)
+                if row["val_loss"] < best - min_delta:
+                    best, wait = row["val_loss"], 0
+                else:
+                    wait += 1
+                    if wait >= patience and lr > min_lr:
+                        lr = float(np.float32(max(lr * factor, min_lr)))
+                        wait = 0
+        return hist
+
     def inference(self, X_train, Y_train, X_val, Y_val, *, epochs=50, batch_size=128, lr=1e-4, seed=0, model_dir=None):
         """d_vector.py:168-210, same positional signature: train Dense(256) ReLU x 3, Dense(256) | ReLU Dropout(0.5) Dense(n_class)
         softmax with categorical cross-entropy and Adam on the GPU (api.DnnTrainer), ReduceLROnPlateau(val_loss, factor 0.5, patience 2,
@@ -511,33 +545,65 @@ class nn_model:
         dev = "cuda:%d" % ctx.device
         xt, yt = torch.from_numpy(X_train).to(dev), torch.from_numpy(y_train).to(dev)   # the data stays on the device over the epochs
         xv, yv = torch.from_numpy(X_val).to(dev), torch.from_numpy(y_val).to(dev)
-        hist = {k: [] for k in ("acc", "loss", "lr", "val_acc", "val_loss")}
-        lr = float(np.float32(lr))   # (Keras keeps lr in a float32 variable)
-        best, wait, factor, patience, min_lr, min_delta = np.inf, 0, 0.5, 2, 1e-7, 1e-4
-        os.makedirs(model_dir, exist_ok=True)
-        with open(os.path.join(model_dir, "nn_training.log"), "w") as log:
-            log.write(self.LOG_HEADER + "\n")
-            for epoch in range(int(epochs)):
-                order = rng.permutation(len(y_train))
-                loss, correct = net.epoch(xt, yt, order, batch_size=batch_size, lr=lr, seed=seed)
-                vloss, vcorrect = net.evaluate(xv, yv) if len(y_val) else (float("nan"), 0)
-                row = {"acc": correct / max(len(y_train), 1), "loss": loss / max(len(y_train), 1), "lr": lr,
-                       "val_acc": vcorrect / max(len(y_val), 1), "val_loss": vloss / max(len(y_val), 1)}
-                for k, v in row.items():
-                    hist[k].append(v)
-                log.write(",".join([str(epoch)] + [repr(float(row[k])) for k in ("acc", "loss", "lr", "val_acc", "val_loss")]) + "\n")
-                log.flush()
-                # ReduceLROnPlateau.on_epoch_end (Keras 2, mode min, cooldown 0)
-                if row["val_loss"] < best - min_delta:
-                    best, wait = row["val_loss"], 0
-                else:
-                    wait += 1
-                    if wait >= patience and lr > min_lr:
-                        lr = float(np.float32(max(lr * factor, min_lr)))
-                        wait = 0
+        hist = self._fit(net, xt, yt, xv, yv, rng, epochs, batch_size, lr, os.path.join(model_dir, "nn_training.log"), seed=seed)
         spk = DenseNet([(net.read("W", l), net.read("b", l), 'relu' if l < 3 else 'linear') for l in range(4)], device=ctx.device)
         save_model(spk, 'nn', model_dir)
         register_model('nn', spk)
+        self.trainer_ = net
+        return hist
+
+    def inference_lstm(self, X_train, Y_train, X_val, Y_val, *, epochs=50, batch_size=128, lr=1e-4, seed=0, recurrent_activation='hard_sigmoid',
+                       D=None, model_dir=None):
+        """d_vector.py:271-294, same positional signature: train LSTM(128) -> Dense(n_class) softmax with categorical cross-entropy and Adam
+        on the GPU (api.LstmTrainer: recurrent forward with a stash, backward through time, weight gradients and Adam as kernels), the
+        plateau schedule and one row per epoch in {model_dir}/lstm_training.log (d_vector.py:286-287) on the host, and the LSTM alone
+        (spkModel, d_vector.py:277) saved as {model_dir}/d_vector_lstm.npz and registered under 'lstm' — the model ``enroll`` and ``eval``
+        load by default.  X is (N, T, D), or (N, T * D) with ``D`` given, as LstmNet.predict accepts.  ``recurrent_activation`` defaults to
+        Keras <= 2.2's 'hard_sigmoid' (the Keras whose Adam(lr=) and CSVLogger columns ``inference`` follows); the saved file records it, so
+        training and prediction agree.  Initialisation is Keras' own, drawn from one ``np.random.default_rng(seed)`` in this order: the LSTM
+        kernel glorot_uniform over (D, 512); the recurrent kernel Orthogonal over the shape (128, 512) — a standard normal matrix of that
+        shape, its thin SVD, the factor of that shape: orthonormal rows —; zero bias with the forget block at one (unit_forget_bias); the
+        Dense kernel glorot_uniform with zero bias; then one permutation of the rows per epoch.  Returns the history as ``inference``
+        does and keeps ``self.trainer_``.  Unpinned against Keras (no Keras here, no fixture in the reference)."""
+        print("Training model")
+        if recurrent_activation not in api.LSTM_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        model_dir = MODEL_DIR if model_dir is None else model_dir
+        X_train, X_val = np.ascontiguousarray(X_train, dtype=np.float32), np.ascontiguousarray(X_val, dtype=np.float32)
+        if X_train.ndim == 2 and D is not None and X_train.shape[1] % int(D) == 0 and X_train.shape[1] > 0:
+            X_train = X_train.reshape(X_train.shape[0], -1, int(D))
+        if X_train.ndim != 3:
+            raise ValueError("X must be (N, T, D), or (N, T * D) with D given")
+        T, d_in = int(X_train.shape[1]), int(X_train.shape[2])
+        if X_val.ndim == 2 and X_val.shape[1] == T * d_in:
+            X_val = X_val.reshape(X_val.shape[0], T, d_in)
+        y_train, y_val = (np.argmax(np.asarray(Y), axis=1).astype(np.int32) for Y in (Y_train, Y_val))
+        if X_val.shape[1:] != X_train.shape[1:] or len(y_train) != len(X_train) or len(y_val) != len(X_val):
+            raise ValueError("X (N, T, D) and one-hot Y (N, n_class) must agree")
+        if max(int(y_train.max(initial=0)), int(y_val.max(initial=0))) >= int(self.n_class):
+            raise ValueError("a label lies outside n_class = %d" % self.n_class)
+        units, n_class = 128, int(self.n_class)
+        rng = np.random.default_rng(seed)
+        lim = np.sqrt(6.0 / (d_in + 4 * units))
+        W = rng.uniform(-lim, lim, (d_in, 4 * units)).astype(np.float32)
+        _, _, vt = np.linalg.svd(rng.standard_normal((units, 4 * units)), full_matrices=False)
+        U = vt.astype(np.float32)
+        b = np.zeros(4 * units, np.float32)
+        b[units:2 * units] = 1.0
+        lim = np.sqrt(6.0 / (units + n_class))
+        Wd = rng.uniform(-lim, lim, (units, n_class)).astype(np.float32)
+        bd = np.zeros(n_class, np.float32)
+        import torch
+        ctx = api.default_context()
+        net = api.LstmTrainer(ctx, W, U, b, Wd, bd, T=T, recurrent_activation=recurrent_activation,
+                              max_batch=max(1, min(1024, max(int(batch_size), 128))))
+        dev = "cuda:%d" % ctx.device
+        xt, yt = torch.from_numpy(X_train).to(dev), torch.from_numpy(y_train).to(dev)   # the data stays on the device over the epochs
+        xv, yv = torch.from_numpy(X_val).to(dev), torch.from_numpy(y_val).to(dev)
+        hist = self._fit(net, xt, yt, xv, yv, rng, epochs, batch_size, lr, os.path.join(model_dir, "lstm_training.log"))
+        spk = LstmNet(net.read("W"), net.read("U"), net.read("b"), recurrent_activation=recurrent_activation, device=ctx.device)
+        save_model(spk, 'lstm', model_dir)
+        register_model('lstm', spk)
         self.trainer_ = net
         return hist
 
