@@ -544,6 +544,80 @@ int ssp_lstm_trainer_steps(const ssp_lstm_trainer* trainer, int64_t* t); /* step
  * dU, Adam.  The step counts: weights, m, v and t move as in ssp_lstm_trainer_epoch. */
 int ssp_lstm_trainer_step_times(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int32_t batch_size, float lr, float* ms_out);
 
+/* ---- conv + GRU d-vector network training (since without a version step, like the entries above): nn_model.inference_gru,
+ *      d_vector.py:213-269 — the network the reference's __main__ evaluates (:389).  ReduceLROnPlateau, CSVLogger and spkModel.save stay with
+ *      the host side (d_vector.nn_model.inference_gru).  Unpinned: the reference tree holds no weights, logs or outputs of this network and
+ *      Keras is not a dependency; the arithmetic is restated from Keras 2's sources and corroborated against torch.autograd only.  All
+ *      fp32, the products on the exact-fp32 MFMA, no floating-point atomic anywhere.
+ *        Network  Conv2D(F, (kh, kw), strides, `same`, linear, one input channel) on the (T, D) chunk (ssp_conv2d_same_forward's
+ *                 arithmetic; To = ceil(T / sh) steps of Do F features, Do = ceil(D / sw)) -> TimeDistributed(Flatten) -> n_gru x
+ *                 GRU(units, return_sequences) -> mean over time (t ascending) -> Dense(E), linear -> K.l2_normalize (eps 1e-12) ->
+ *                 Dense(n_class) softmax.  Reference values: F 64, 5 x 5, strides 2, T 98, D 13 (49 steps of 448 features), 3 x 1024,
+ *                 E 512, batch 128, Adam lr 1e-4.
+ *        Regulariser  the convolution kernel carries regularizers.l2() with Keras' default factor lambda = 0.01: a step's loss is the
+ *                 batch's mean cross-entropy + lambda sum K^2, dK gains 2 lambda K, and both the training and the validation loss sums
+ *                 contain the term as Keras reports them: a batch of B rows adds B lambda sum K^2, K as it was before that step's
+ *                 update.  Biases are not regularised.
+ *        GRU cell the forward pass's, as stated for ssp_gru_forward above, with reset_after = 0 (what the reference's stand-alone Keras
+ *                 runs); recurrent_activation 0 hard_sigmoid | 1 sigmoid.  reset_after = 1 is NOT trained: create answers
+ *                 SSP_ERR_UNSUPPORTED for it before any GPU work.
+ *        Backward through time, for t = To-1 .. 0; dh_t = the gradient from above (dmean / To for the top layer, the upper layer's dx_t
+ *                 otherwise) + the recurrent part carried from step t + 1:
+ *                   dhh = dh_t (1 - z);   da_h = dhh (1 - hh^2);   da_z = dh_t (h_{t-1} - hh) s'(z)
+ *                   G   = da_h U_h^T;     da_r = (G . h_{t-1}) s'(r)
+ *                   dh_{t-1} = dh_t z + G . r + [da_z | da_r] [U_z | U_r]^T
+ *                   dW += x_t^T [da_z | da_r | da_h];   db += column sums of the same
+ *                   dU_z,r += h_{t-1}^T [da_z | da_r];  dU_h += (r . h_{t-1})^T da_h
+ *                   dx_t = [da_z | da_r | da_h] W^T
+ *                 sigmoid: s'(s) = s (1 - s).  hard_sigmoid: s' = 0.2 where the fp32 activation lies strictly inside (0, 1) and 0
+ *                 elsewhere (the LSTM trainer's rule).
+ *        Around the GRUs  mean over time and Dense backward; l2_normalize backward with n = sqrt(max(sum x^2, eps)): dx = (dy - y (y . dy))
+ *                 / n where sum x^2 >= eps, dx = dy / n below it; conv backward: dK and db only (the input needs no gradient), the sum
+ *                 over the B To Do output positions in 64 fixed chunks added in order.
+ *        Loss, accuracy, Adam: the dense trainer's, in the words of its section — the gradient at the logits is (softmax - onehot) / B
+ *                 with B the actual batch (the tail batch included), Keras 2's Adam with eps 1e-7 outside the root and t counted over
+ *                 the whole fit, one Adam launch over flat parameter, gradient, m and v buffers.
+ *        Determinism: the same seed, data and order give the same bits.  A sequence is one MFMA column in the recurrent kernels; every
+ *                 sum over rows has a fixed partition and order.
+ *      Time steps are ordered by the stream: two launches per step, layer and direction (16 units x 16 sequences per wave, 64 units per
+ *      workgroup).  The stash (h, z, r, hh, r . h_{t-1} per layer), the projection, the gate gradients and the gradient at a layer's
+ *      input are time-major in a workspace allocated at create: To max_batch (d0 + 6 Hmax + max(Hmax, d0) + 5 sum units) floats, 0.58 GB
+ *      at the reference shape.  Above 4 GiB create answers SSP_ERR_UNSUPPORTED. ---- */
+/* conv_K: HOST float[kh x kw x F] (Keras' (kh, kw, 1, F)), conv_b: HOST float[F] or NULL; kh, kw <= 7, F <= 256, strides 1 or 2.
+ * units: HOST int32[n_gru], n_gru in [1, 4]; W[l]: HOST float[d_in x 3 units[l]] with d_in = Do F for l = 0 and units[l - 1] above;
+ * U[l]: HOST float[units[l] x 3 units[l]]; bias: NULL, or bias[l]: HOST float[3 units[l]] or NULL; units a multiple of 16 up to 1024,
+ * d_in up to 4096.  dense_W: HOST float[units[n_gru - 1] x E], dense_b: HOST float[E] or NULL, E <= 4096; head_W: HOST float[E x n_class],
+ * head_b: HOST float[n_class] or NULL, n_class in [2, 4096].  T in [1, 1024], D in [1, 4096], max_batch in [1, 1024], To max_batch up to 2^19 rows.  A limit exceeded,
+ * reset_after = 1 or a workspace above the cap answers SSP_ERR_UNSUPPORTED; a null kernel, a bad switch or a shape below 1 answers
+ * SSP_ERR_INVALID; both before any GPU work. */
+typedef struct ssp_gru_trainer ssp_gru_trainer;
+int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32_t kw, int32_t F, int32_t sh, int32_t sw, const float* conv_K,
+                           const float* conv_b, int32_t n_gru, const int32_t* units, const float* const* W, const float* const* U,
+                           const float* const* bias, int32_t E, const float* dense_W, const float* dense_b, int32_t n_class, const float* head_W,
+                           const float* head_b, int32_t recurrent_activation, int32_t reset_after, int32_t max_batch, ssp_gru_trainer** out);
+int ssp_gru_trainer_destroy(ssp_gru_trainer* trainer);
+/* One pass of spk.fit over the data (d_vector.py:264-265).  X: float[N x T x D], labels: int32[N], on the side `where` names; order,
+ * batch_size, lr, the queued steps without a host wait, the per-step loss / correct slots read back ONCE, the refusals and t: as for
+ * ssp_lstm_trainer_epoch.  loss_sum contains the regulariser's term. */
+int ssp_gru_trainer_epoch(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
+                          float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms);
+/* the validation pass, in chunks of max_batch rows: nothing is updated (weights, gradients, m, v and t keep their values) */
+int ssp_gru_trainer_evaluate(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
+                             int where, float* kernel_ms);
+/* `tensor` of: the parameters, the LAST step's gradients, Adam's m and v, in Keras' layout.  out: HOST.  Waits for the ctx stream.  A bias
+ * the network was created without, or a layer it does not have, answers SSP_ERR_INVALID. */
+enum { SSP_GRUT_PARAM = 0, SSP_GRUT_GRAD = 1, SSP_GRUT_M = 2, SSP_GRUT_V = 3 };
+enum { SSP_GRUT_CONV_K = 0, SSP_GRUT_CONV_B = 1, SSP_GRUT_GRU0_W = 2, SSP_GRUT_GRU0_U = 3, SSP_GRUT_GRU0_B = 4, /* layer i: 2 + 3 i .. */
+       SSP_GRUT_DENSE_W = 14, SSP_GRUT_DENSE_B = 15, SSP_GRUT_HEAD_W = 16, SSP_GRUT_HEAD_B = 17 };
+int ssp_gru_trainer_read(ssp_gru_trainer* trainer, int32_t what, int32_t tensor, float* out);
+int ssp_gru_trainer_steps(const ssp_gru_trainer* trainer, int64_t* t); /* steps taken so far (Adam's t) */
+/* measurement aid (tools/bench_gru_train.py): ONE training step on the first batch_size rows of DEVICE arrays with a hipEvent between its
+ * launch kinds, then a host wait.  ms_out: HOST float[30] — [0] conv forward, [1] mean + Dense + l2_normalize + head, [2] loss +
+ * regulariser, [3] their backward, [4] conv backward, [5] Adam + re-pack of U; then for GRU layer i at [6 + 6 i ..]: input projection, the
+ * 2 To forward step launches, the 2 To backward step launches, dW + db, dU, dx (zero for absent layers).  The step counts. */
+enum { SSP_GRUT_TIMES = 30 };
+int ssp_gru_trainer_step_times(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int32_t batch_size, float lr, float* ms_out);
+
 /* ---- d-vector cosine scoring: replaces the scipy cosine double loop + argmin
  *      (d_vector.py:315-319, 346-361) ---- */
 /* X: float[N x d]; C: float[S x d]; dist_out (nullable): float[N x S] = clip(1 - cos, 0, 2);

@@ -115,6 +115,15 @@ SIGNATURES = {
     "ssp_lstm_trainer_read": (C.c_int, [_P, C.c_int32, C.c_int32, _F32P]),
     "ssp_lstm_trainer_steps": (C.c_int, [_P, _I64P]),
     "ssp_lstm_trainer_step_times": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, _MSP]),
+    "ssp_gru_trainer_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int32,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, _F32P,
+                                         _F32P, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "ssp_gru_trainer_destroy": (C.c_int, [_P]),
+    "ssp_gru_trainer_epoch": (C.c_int, [_P, _F32P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.POINTER(C.c_double), _I64P, C.c_int, _MSP]),
+    "ssp_gru_trainer_evaluate": (C.c_int, [_P, _F32P, _P, C.c_int64, C.POINTER(C.c_double), _I64P, C.c_int, _MSP]),
+    "ssp_gru_trainer_read": (C.c_int, [_P, C.c_int32, C.c_int32, _F32P]),
+    "ssp_gru_trainer_steps": (C.c_int, [_P, _I64P]),
+    "ssp_gru_trainer_step_times": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, _MSP]),
     "ssp_dropout_keep": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     "ssp_dtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_fastdtw_distances": (C.c_int, [_P, _F32P, _P, _F32P, _P, C.c_int32, C.c_void_p, _MSP]),

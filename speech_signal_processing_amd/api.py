@@ -1306,6 +1306,192 @@ def l2_normalize(ctx: Context, X, eps: float = 1e-12, timing: bool = False):
     return (Y, ms.value) if timing else Y
 
 
+class GruTrainer:
+    """The conv + GRU d-vector network with its gradients and Adam state on the GPU (ssp_gru_trainer): nn_model.inference_gru's spk.fit,
+    d_vector.py:213-269 — Conv2D (l2-regularised kernel, lambda 0.01) -> n GRU layers -> mean over time -> Dense(E) -> l2_normalize ->
+    Dense(n_class) softmax.  ``conv`` = (K (kh, kw, 1, F), b (F,) or None, strides), ``grus`` = [(W (d_in, 3 units), U (units, 3 units),
+    b (3 units,) or None), ...], ``dense`` = (W (units, E), b or None), ``head`` = (W (E, n_class), b or None), all in Keras' layout.
+    Both GRU switches are named by the caller; ``reset_after=True`` is not trained (NotImplementedError).  X (N, T, D) and labels are
+    numpy arrays (host) or torch CUDA tensors (X float32, labels int32).  Limits (NotImplementedError otherwise): kernels up to 7 x 7, 256
+    filters, strides 1 or 2, 1 to 4 GRU layers of units a multiple of 16 up to 1024, d_in up to 4096, n_class in [2, 4096], max_batch
+    up to 1024 and a workspace of one step within 4 GiB.  Tensor names for ``read``: conv_K, conv_b, gru{i}_W, gru{i}_U, gru{i}_b,
+    dense_W, dense_b, head_W, head_b.  Unpinned against Keras."""
+
+    WHAT = {"": 0, "d": 1, "m": 2, "v": 3}
+    MAX_LAYERS = 4
+
+    def __init__(self, ctx: Context, conv, grus, dense, head, *, T, D, recurrent_activation, reset_after, max_batch: int = 128):
+        if recurrent_activation not in GRU_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        if not isinstance(reset_after, (bool, np.bool_)):
+            raise ValueError("reset_after must be True or False")
+        self.ctx = ctx
+        self._lib = ctx._lib
+        K, bc, strides = conv
+        K = np.ascontiguousarray(K, dtype=np.float32)
+        if K.ndim == 4 and K.shape[2] == 1:
+            K = K.reshape(K.shape[0], K.shape[1], K.shape[3])
+        if K.ndim != 3:
+            raise ValueError("the convolution kernel must be (kh, kw, 1, F)")
+        kh, kw, F = (int(v) for v in K.shape)
+        vec = lambda b, n, what: None if b is None else _gru_vec(b, n, what)  # noqa: E731
+        bc = vec(bc, F, "conv bias")
+        sh, sw = int(strides[0]), int(strides[1])
+        self.T, self.D, self.strides = int(T), int(D), (sh, sw)
+        if sh < 1 or sw < 1 or self.D < 1:
+            raise ValueError("strides and D must be >= 1")
+        To, Do = conv2d_same_out_shape(max(self.T, 1), self.D, (sh, sw))
+        if len(grus) < 1:
+            raise ValueError("at least one GRU layer")
+        layers, d_in = [], Do * F
+        for i, (W, U, b) in enumerate(grus):
+            W, U, _ = _gru_arrays(W, U, None, False)
+            if W.shape[0] != d_in:
+                raise ValueError("GRU layer %d must take %d features" % (i, d_in))
+            # reset_after=True is refused by create before it reads anything, whichever of the two bias layouts came with it
+            if b is not None:
+                b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1) if reset_after else _gru_vec(b, U.shape[1], "GRU bias")
+            layers.append((W, U, b))
+            d_in = int(U.shape[0])
+        Wd, bd = np.ascontiguousarray(dense[0], dtype=np.float32), dense[1]
+        if Wd.ndim != 2 or Wd.shape[0] != d_in:
+            raise ValueError("the Dense kernel must be (units, E)")
+        E = int(Wd.shape[1])
+        bd = vec(bd, E, "Dense bias")
+        Wh, bh = np.ascontiguousarray(head[0], dtype=np.float32), head[1]
+        if Wh.ndim != 2 or Wh.shape[0] != E:
+            raise ValueError("the head's kernel must be (E, n_class)")
+        self.n_class = int(Wh.shape[1])
+        bh = vec(bh, self.n_class, "head bias")
+        self.units = [int(U.shape[0]) for _, U, _ in layers]
+        self.n_gru, self.embedding, self.filters = len(layers), E, F
+        self.recurrent_activation, self.reset_after, self.max_batch = recurrent_activation, bool(reset_after), int(max_batch)
+        self.TENSOR = {"conv_K": 0, "conv_b": 1, "dense_W": 14, "dense_b": 15, "head_W": 16, "head_b": 17}
+        self.shapes = {"conv_K": (kh, kw, 1, F), "conv_b": (F,), "dense_W": tuple(Wd.shape), "dense_b": (E,), "head_W": tuple(Wh.shape),
+                       "head_b": (self.n_class,)}
+        self.has_bias = {"conv_b": bc is not None, "dense_b": bd is not None, "head_b": bh is not None}
+        for i, (W, U, b) in enumerate(layers[:self.MAX_LAYERS]):
+            for j, (n, a) in enumerate((("W", W), ("U", U), ("b", b))):
+                self.TENSOR["gru%d_%s" % (i, n)] = 2 + 3 * i + j
+                self.shapes["gru%d_%s" % (i, n)] = (3 * self.units[i],) if n == "b" else tuple(a.shape)
+            self.has_bias["gru%d_b" % i] = b is not None
+        n = len(layers)
+        c_units = (C.c_int32 * n)(*self.units)
+        c_w = (C.c_void_p * n)(*[W.ctypes.data for W, _, _ in layers])
+        c_u = (C.c_void_p * n)(*[U.ctypes.data for _, U, _ in layers])
+        c_b = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for _, _, b in layers])
+        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_gru_trainer_create(ctx._h, self.T, self.D, kh, kw, F, sh, sw, K.ctypes.data, p(bc), n, c_units, c_w, c_u, c_b, E,
+                                                    Wd.ctypes.data, p(bd), self.n_class, Wh.ctypes.data, p(bh),
+                                                    GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, int(max_batch), C.byref(h)))
+        self._h = h
+
+    def _data(self, X, labels):
+        xk, xp, where = _as_f32(X, "X")
+        if xk.ndim == 4 and int(xk.shape[3]) == 1:
+            xk = xk.reshape(xk.shape[0], xk.shape[1], xk.shape[2])
+        if xk.ndim != 3 or int(xk.shape[1]) != self.T or int(xk.shape[2]) != self.D:
+            raise ValueError("X must be (N, %d, %d)" % (self.T, self.D))
+        if where == _lib.DEVICE:
+            import torch
+            if not (_is_torch(labels) and labels.is_cuda):
+                raise ValueError("labels must live where X lives")
+            lk = labels.to(torch.int32).contiguous()
+            lp = lk.data_ptr()
+        else:
+            lk = np.ascontiguousarray(labels, dtype=np.int32)
+            lp = lk.ctypes.data
+        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
+            raise ValueError("one label per row of X")
+        return (xk, lk), xp, lp, int(xk.shape[0]), where
+
+    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
+        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum with the regulariser's
+        term, correct rows) as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        ok, op = None, None
+        if order is not None:
+            ok = np.ascontiguousarray(order, dtype=np.int64)
+            if ok.shape != (N,):
+                raise ValueError("order must hold N row indices")
+            op = ok.ctypes.data
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_gru_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), C.byref(loss), C.byref(corr), where,
+                                                       C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def evaluate(self, X, labels, timing: bool = False):
+        """loss sum and correct rows over (X, labels); nothing is updated"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_gru_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    STEP_KINDS = ("conv forward", "mean+dense+l2+head", "loss+regulariser", "head+l2+dense+mean backward", "conv backward", "adam+repack")
+    LAYER_KINDS = ("projection", "forward steps", "backward steps", "dW+db", "dU", "dx")
+
+    def step_times(self, X, labels, batch_size: int = 128, lr: float = 1e-4):
+        """ONE training step on the first ``batch_size`` rows of torch CUDA tensors with a hipEvent between its launch kinds ->
+        {kind: milliseconds}; the 2 To step launches of a layer and direction are one figure, 'gru{i} forward steps' / 'backward steps'
+        (a measurement aid: the step counts like any other)"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        if where != _lib.DEVICE or N < int(batch_size):
+            raise ValueError("step_times takes torch CUDA tensors of at least batch_size rows")
+        ms = (C.c_float * 30)()
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_gru_trainer_step_times(self._h, xp, lp, int(batch_size), float(lr), ms))
+        out = dict(zip(self.STEP_KINDS, (float(v) for v in ms[:6])))
+        for i in range(self.n_gru):
+            for j, k in enumerate(self.LAYER_KINDS):
+                out["gru%d %s" % (i, k)] = float(ms[6 + 6 * i + j])
+        return out
+
+    def _name(self, what):
+        if what in self.TENSOR:
+            return "", what
+        if what[:1] in ("d", "m", "v") and what[1:] in self.TENSOR:
+            return what[:1], what[1:]
+        raise ValueError("unknown tensor %r" % (what,))
+
+    def read(self, what: str, out=None):
+        """a tensor name (parameters), or one with a prefix 'd' (the last step's gradients), 'm' or 'v' (Adam's moments), e.g. 'dgru0_U',
+        'mhead_W' -> numpy; ``out``: a float32 array of the tensor's size to fill instead (it needs 4-byte alignment only)"""
+        prefix, name = self._name(what)
+        if out is None:
+            out = np.empty(self.shapes[name], dtype=np.float32)
+        elif out.dtype != np.float32 or out.size != int(np.prod(self.shapes[name])) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float32 array of %d entries" % int(np.prod(self.shapes[name])))
+        _lib.check(self._lib.ssp_gru_trainer_read(self._h, self.WHAT[prefix], self.TENSOR[name], out.ctypes.data))
+        return out
+
+    @property
+    def steps(self) -> int:
+        t = C.c_int64(0)
+        _lib.check(self._lib.ssp_gru_trainer_steps(self._h, C.byref(t)))
+        return t.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_gru_trainer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _gru_vec(b, n, what):
+    b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
+    if b.shape[0] != n:
+        raise ValueError("%s must have %d entries" % (what, n))
+    return b
+
+
 def cosine_identify(ctx: Context, X, Cn, dist: bool = False, argmin: bool = True, minval: bool = True,
                     timing: bool = False, precision: int = 0, counts: bool = True) -> dict:
     """dist[i,j] = clip(1 - cos(X[i], C[j]), 0, 2); argmin over j (first index on ties) — d_vector.py:315-319.

@@ -6,8 +6,8 @@ Conv2D -> 3 x GRU(1024) -> mean over time -> Dense(512) -> L2 normalisation, d_v
 and nn_model.test / enroll / eval (d_vector.py:296-361), and the training of the fully connected network (``nn_model.inference``,
 d_vector.py:168-210: forward with dropout, softmax cross-entropy, backward and Adam on the GPU, api.DnnTrainer) and of the recurrent one
 (``nn_model.inference_lstm``, d_vector.py:271-294: recurrent forward with a stash, backward through time and Adam on the GPU,
-api.LstmTrainer; it writes d_vector_lstm.npz, which enroll / eval pick up).  Training the conv + GRU network is out of scope: its weights
-are inputs.
+api.LstmTrainer; it writes d_vector_lstm.npz, which enroll / eval pick up) and of the conv + GRU one (``nn_model.inference_gru``,
+d_vector.py:213-269: api.GruTrainer; it writes d_vector_gru.npz, a ConvGruNet).
 The recurrent networks are UNPINNED: the reference tree holds no weights or outputs for them and Keras is not a dependency; their
 arithmetic is restated from Keras' documentation and corroborated against torch's cells only."""
 from __future__ import annotations
@@ -451,8 +451,8 @@ class Data_gen:
 
 
 class nn_model:
-    """d_vector.nn_model: ``inference`` trains the fully connected network, ``inference_lstm`` the recurrent one (the conv + GRU network is
-    not trained here); test / enroll / eval score.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
+    """d_vector.nn_model: ``inference`` trains the fully connected network, ``inference_lstm`` the recurrent one and ``inference_gru`` the conv +
+    GRU one (reset_after=False, stand-alone Keras' cell, only); test / enroll / eval score.  ``X_*`` are embeddings, or network inputs when ``spk_model`` (a DenseNet, the
     stand-in for load_model('feature/d_vector/d_vector_{}.h5')) is given.  ``store``: path of the enrolment dictionary pickle
     (the reference always uses 'feature/d_vector/d_vector.pkl', d_vector.py:333-344,350-351); None keeps it in memory."""
 
@@ -486,7 +486,7 @@ class nn_model:
     LOG_HEADER = "epoch,acc,loss,lr,val_acc,val_loss"  # Keras 2.2's CSVLogger columns, in its sorted order
 
     def _fit(self, net, xt, yt, xv, yv, rng, epochs, batch_size, lr, log_path, **epoch_args):
-        """spk.fit's loop around a trainer (api.DnnTrainer / api.LstmTrainer): one permutation of the rows from ``rng`` and one
+        """spk.fit's loop around a trainer (api.DnnTrainer / api.LstmTrainer / api.GruTrainer): one permutation of the rows from ``rng`` and one
         ``net.epoch`` per epoch, the validation pass, one CSVLogger row in ``log_path`` and Keras 2's ReduceLROnPlateau(val_loss, factor
         0.5, patience 2, min_lr 1e-7, min_delta 1e-4, mode min, cooldown 0) on the host -> the history as a dict of lists"""
         n_train, n_val = int(yt.shape[0]), int(yv.shape[0])
@@ -604,6 +604,70 @@ class nn_model:
         spk = LstmNet(net.read("W"), net.read("U"), net.read("b"), recurrent_activation=recurrent_activation, device=ctx.device)
         save_model(spk, 'lstm', model_dir)
         register_model('lstm', spk)
+        self.trainer_ = net
+        return hist
+
+    def inference_gru(self, X_train, Y_train, X_val, Y_val, *, epochs=50, batch_size=128, lr=1e-4, seed=0, recurrent_activation='hard_sigmoid',
+                      reset_after=False, filters=64, units=1024, n_gru=3, embedding=512, model_dir=None):
+        """d_vector.py:213-269, same positional signature: train Conv2D(filters, 5 x 5, strides 2, same, l2-regularised kernel) ->
+        TimeDistributed(Flatten) -> n_gru x GRU(units, return_sequences) -> mean over time -> Dense(embedding) -> l2_normalize ->
+        Dense(n_class) softmax with categorical cross-entropy and Adam on the GPU (api.GruTrainer), the plateau schedule and one row per
+        epoch in {model_dir}/gru_training.log on the host.  spkModel — everything up to the L2 normalisation, d_vector.py:250 — is saved as
+        a ConvGruNet in {model_dir}/d_vector_gru.npz and registered under 'gru'.  X is (N, T, D, 1) or (N, T, D).  ``loss`` / ``val_loss``
+        contain the regulariser's 0.01 sum K^2 as Keras reports them.  ``reset_after=True`` (tf.keras 2's cell) is not trained:
+        NotImplementedError.  Initialisation is Keras' own, drawn from one ``np.random.default_rng(seed)`` in this order: the conv kernel
+        glorot_uniform with fan_in kh kw and fan_out kh kw filters; then per GRU layer its kernel glorot_uniform over (d_in, 3 units) and
+        its recurrent kernel Orthogonal over the shape (units, 3 units) — a standard normal matrix of that shape, its thin SVD, the
+        factor of that shape: orthonormal rows, as inference_lstm draws its own —; the Dense(embedding) kernel and the head's kernel
+        glorot_uniform; every bias zero; then one permutation of the rows per epoch.  Returns the history as ``inference`` does and
+        keeps ``self.trainer_``.  Unpinned against Keras (no Keras here, no fixture in the reference)."""
+        print("Training model")
+        if recurrent_activation not in api.GRU_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
+        if reset_after:
+            raise NotImplementedError("inference_gru trains the reset_after=False cell only (ConvGruNet predicts with either)")
+        model_dir = MODEL_DIR if model_dir is None else model_dir
+        X_train, X_val = np.ascontiguousarray(X_train, dtype=np.float32), np.ascontiguousarray(X_val, dtype=np.float32)
+        if X_train.ndim == 4 and X_train.shape[3] == 1:
+            X_train = X_train.reshape(X_train.shape[:3])
+        if X_val.ndim == 4 and X_val.shape[3] == 1:
+            X_val = X_val.reshape(X_val.shape[:3])
+        y_train, y_val = (np.argmax(np.asarray(Y), axis=1).astype(np.int32) for Y in (Y_train, Y_val))
+        if X_train.ndim != 3 or X_val.shape[1:] != X_train.shape[1:] or len(y_train) != len(X_train) or len(y_val) != len(X_val):
+            raise ValueError("X (N, T, D[, 1]) and one-hot Y (N, n_class) must agree")
+        if max(int(y_train.max(initial=0)), int(y_val.max(initial=0))) >= int(self.n_class):
+            raise ValueError("a label lies outside n_class = %d" % self.n_class)
+        T, D = int(X_train.shape[1]), int(X_train.shape[2])
+        kh, kw, strides = 5, 5, (2, 2)
+        F, H, E, n_class = int(filters), int(units), int(embedding), int(self.n_class)
+        rng = np.random.default_rng(seed)
+
+        def glorot(shape, fan_in, fan_out):
+            lim = np.sqrt(6.0 / (fan_in + fan_out))
+            return rng.uniform(-lim, lim, shape).astype(np.float32)
+        K = glorot((kh, kw, 1, F), kh * kw, kh * kw * F)
+        grus, d_in = [], api.conv2d_same_out_shape(T, D, strides)[1] * F
+        for _ in range(int(n_gru)):
+            W = glorot((d_in, 3 * H), d_in, 3 * H)
+            _, _, vt = np.linalg.svd(rng.standard_normal((H, 3 * H)), full_matrices=False)
+            grus.append((W, vt.astype(np.float32), np.zeros(3 * H, np.float32)))
+            d_in = H
+        Wd, Wh = glorot((H, E), H, E), glorot((E, n_class), E, n_class)
+        import torch
+        ctx = api.default_context()
+        net = api.GruTrainer(ctx, (K, np.zeros(F, np.float32), strides), grus, (Wd, np.zeros(E, np.float32)), (Wh, np.zeros(n_class, np.float32)),
+                             T=T, D=D, recurrent_activation=recurrent_activation, reset_after=False,
+                             max_batch=max(1, min(1024, int(batch_size))))
+        dev = "cuda:%d" % ctx.device
+        xt, yt = torch.from_numpy(X_train).to(dev), torch.from_numpy(y_train).to(dev)   # the data stays on the device over the epochs
+        xv, yv = torch.from_numpy(X_val).to(dev), torch.from_numpy(y_val).to(dev)
+        hist = self._fit(net, xt, yt, xv, yv, rng, epochs, batch_size, lr, os.path.join(model_dir, "gru_training.log"))
+        spk = ConvGruNet((net.read("conv_K"), net.read("conv_b"), strides),
+                         [(net.read("gru%d_W" % i), net.read("gru%d_U" % i), net.read("gru%d_b" % i)) for i in range(int(n_gru))],
+                         (net.read("dense_W"), net.read("dense_b")), recurrent_activation=recurrent_activation, reset_after=False,
+                         input_shape=(T, D), device=ctx.device)
+        save_model(spk, 'gru', model_dir)
+        register_model('gru', spk)
         self.trainer_ = net
         return hist
 
