@@ -353,6 +353,24 @@ int ssp_fastdtw_distances(ssp_ctx* ctx, const float* xq, const ssp_segments* q_s
 int ssp_dtw_path(ssp_ctx* ctx, const float* x, int64_t r, const float* y, int64_t c, int32_t dim, double* dist_out,
                  int32_t* path_i_out, int32_t* path_j_out, int32_t* path_len_out);
 
+/* Every speaker's template in batched launches — the generate_template loop of load_train (MFCC_DTW.py:122-152, 187-217).
+ * x: HOST double[seq_off[n_seq] x dim], the sequences' rows back to back (seq_off: HOST int64[n_seq + 1], from 0, increasing); group g
+ * owns the sequences grp_off[g] .. grp_off[g + 1] - 1 (HOST int64[n_grp + 1], from 0 to n_seq, increasing).  A group's template is its
+ * first longest sequence, updated with the group's other sequences in index order: warp the sequence onto the template (the
+ * accelerated_dtw path), average the aligned values, keep the first path entry of every template index.  Round k of all groups is one
+ * launch of a forward kernel (float64 wavefront that stores one direction byte per cell instead of D1) and one of a traceback-and-update
+ * kernel; all rounds are enqueued on the context's stream without a host wait and the call returns after one.  As in ssp_dtw_path (which
+ * api.dtw_path feeds float32 arrays) the cost of a cell is taken from operands ROUNDED TO float32, accumulated in float64: a deviation
+ * of the existing single-pair path from the reference that is kept here, not changed, so that both give the same bits.
+ * tmpl_out: HOST double[sum of the groups' longest lengths x dim], templates back to back; tmpl_off_out: HOST int64[n_grp + 1], their
+ * row offsets.  A group of one sequence returns that sequence.  workspace_bytes caps the direction store of one round (0 = 1 GiB):
+ * consecutive groups share launches while they fit, a pair that exceeds the cap alone raises it to its need (rows x columns padded to
+ * a multiple of 4 bytes); the result does not depend on the cap.  Five device allocations per call, whatever the number of pairs.
+ * SSP_ERR_INVALID: null pointers, dim < 1, no group, an empty group or sequence, offsets that do not increase, a non-finite value in x
+ * (scanned before the first launch).  SSP_ERR_UNSUPPORTED: a pair beyond ssp_dtw_path's limits (r or c > 2^20, r x c > 5e8). */
+int ssp_dtw_templates(ssp_ctx* ctx, const double* x, const int64_t* seq_off, int64_t n_seq, const int64_t* grp_off, int64_t n_grp,
+                      int32_t dim, int64_t workspace_bytes, double* tmpl_out, int64_t* tmpl_off_out, float* kernel_ms);
+
 /* ---- d-vector network forward: one Dense layer Y = act(X W + b) of the speaker network the reference runs with
  *      spkModel.predict (d_vector.py:171-189 builds Dense(256) x 4 with ReLU between; predict at d_vector.py:298-299,327,348) ---- */
 /* X: float[N x d_in]; Wt: float[units x d_in] = the Keras kernel (d_in x units) TRANSPOSED; bias: float[units] (nullable);

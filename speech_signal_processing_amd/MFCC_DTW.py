@@ -3,7 +3,8 @@
 ``load_train`` / ``load_test`` (MFCC_DTW.py:122-184) walk ``<path>/<speaker>/*.wav`` like the reference's, with its ``mfcc_extract=`` plug
 point: with this module's own ``_MFCC`` / ``MFCC_lib`` / ``MFCC`` every file of the directory tree goes through ONE batched kernel launch,
 any other callable is applied per file as the reference applies it.  The matcher (distance_dtw / distance_train / distance_test, MFCC_DTW.py:57-108, and the
-arg-min classification of test(), MFCC_DTW.py:187-217) runs as one all-pairs DTW kernel (api.dtw_distances)."""
+arg-min classification of test(), MFCC_DTW.py:187-217) runs as one all-pairs DTW kernel (api.dtw_distances); load_train's templates
+are built for all speakers together (generate_templates)."""
 from __future__ import annotations
 
 import functools
@@ -89,10 +90,8 @@ def load_train(path='dataset/ASR/train', mfcc_extract=_MFCC):
             signals.append(_read_8k(os.path.join(path, _dir, _path)))
             owner.append(k)
     feats = _extract_all(signals, mfcc_extract)
-    x, y_label = [], []
-    for k, _dir in enumerate(wav_dir):
-        x.append(generate_template([f for f, o in zip(feats, owner) if o == k]))
-        y_label.append(_dir)
+    x = generate_templates([[f for f, o in zip(feats, owner) if o == k] for k in range(len(wav_dir))])  # every speaker's rounds in shared launches
+    y_label = list(wav_dir)
     print('Loading train data, extract mfcc feature and generate template spend {}s'.format(get_time(start_time)))
     return x, y_label
 
@@ -160,6 +159,13 @@ def generate_template(x):
         keep[1:] = p1[1:] != p1[:-1]
         template = template[keep]
     return template
+
+
+def generate_templates(groups, workspace_bytes=0):
+    """generate_template for every speaker at once (api.dtw_templates on the default context): ``groups[g]`` is one speaker's list of
+    samples, the result a list with ``generate_template(groups[g])`` at position g, bit for bit.  Speakers are independent, so sample k of
+    every speaker is warped onto that speaker's template in one launch; neither cost matrices nor paths leave the device."""
+    return api.dtw_templates(None, groups, workspace_bytes=workspace_bytes)
 
 
 def vote(label):

@@ -790,6 +790,64 @@ def dtw_path(ctx: Context, x, y):
     return d.value, pi[:n.value].astype(np.int64), pj[:n.value].astype(np.int64)
 
 
+def _dtw_direction_bytes(r: int, c: int) -> int:
+    """Bytes of the direction store ssp_dtw_templates keeps for one (sample of r rows, template of c rows) pair: one byte per cell,
+    rows padded to a multiple of four.  ``workspace_bytes`` of dtw_templates caps the sum over the pairs of one round."""
+    return int(r) * ((int(c) + 3) // 4 * 4)
+
+
+def _pack_template_groups(groups):
+    """The argument checks of dtw_templates (no context needed): (x float64 (rows, dim), seq_off, grp_off, dim, flat)."""
+    x, lens, grp_off, dims, flat = [], [], [0], set(), set()
+    for g, group in enumerate(groups):
+        group = list(group)
+        if not group:
+            raise ValueError("group %d is empty" % g)
+        for s in group:
+            a = np.asarray(s, dtype=np.float64)
+            if a.ndim not in (1, 2):
+                raise ValueError("samples must be (L,) or (L, dim) arrays")
+            if a.shape[0] < 1 or (a.ndim == 2 and a.shape[1] < 1):
+                raise ValueError("group %d has an empty sample" % g)
+            if not np.isfinite(a).all():
+                raise ValueError("group %d has a non-finite value" % g)
+            flat.add(a.ndim == 1)
+            dims.add(1 if a.ndim == 1 else a.shape[1])
+            x.append(a.reshape(a.shape[0], -1))
+            lens.append(a.shape[0])
+        grp_off.append(len(lens))
+    if len(flat) > 1 or len(dims) > 1:
+        raise ValueError("all samples must share the number of dimensions and the feature dimension")
+    seq_off = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(lens, out=seq_off[1:])
+    return np.ascontiguousarray(np.concatenate(x)), seq_off, np.asarray(grp_off, dtype=np.int64), dims.pop(), flat.pop()
+
+
+def dtw_templates(ctx, groups, workspace_bytes: int = 0, timing: bool = False):
+    """One DTW template per group of samples (ssp_dtw_templates): what MFCC_DTW.generate_template gives for each group, with round k of
+    ALL groups in one launch.  groups: a list of lists of arrays, every array (L,) (the reference's flattened MFCCs) or every array
+    (L, dim).  Returns a list of float64 arrays (L_g,) / (L_g, dim), L_g the length of group g's longest sample.  ``workspace_bytes``
+    caps the direction store of one round (0: 1 GiB; a pair of r x c cells takes r rows of c bytes, rows padded to a multiple of four); the result does not depend on it.  The arguments are
+    checked before a context is needed: ``ctx=None`` takes the default context after they passed."""
+    groups = list(groups)
+    if int(workspace_bytes) < 0:
+        raise ValueError("workspace_bytes must be >= 0")
+    if not groups:
+        return ([], 0.0) if timing else []
+    x, seq_off, grp_off, dim, flat = _pack_template_groups(groups)
+    if ctx is None:
+        ctx = default_context()
+    n_grp = len(grp_off) - 1
+    longest = [int(np.diff(seq_off[grp_off[g]:grp_off[g + 1] + 1]).max()) for g in range(n_grp)]
+    out = np.empty((sum(longest), dim), dtype=np.float64)
+    toff = np.empty(n_grp + 1, dtype=np.int64)
+    ms = C.c_float(0.0)
+    _lib.check(ctx._lib.ssp_dtw_templates(ctx._h, x.ctypes.data, seq_off.ctypes.data, len(seq_off) - 1, grp_off.ctypes.data, n_grp, dim,
+                                           int(workspace_bytes), out.ctypes.data, toff.ctypes.data, C.byref(ms) if timing else None))
+    res = [out[toff[g]:toff[g + 1]].reshape(-1).copy() if flat else out[toff[g]:toff[g + 1]].copy() for g in range(n_grp)]
+    return (res, ms.value) if timing else res
+
+
 def dense_forward(ctx: Context, X, Wt, bias=None, relu: bool = False, timing: bool = False):
     """Y = act(X @ Wt.T + bias) — one Keras Dense layer (ssp_dense_forward).  X (N, d_in); Wt (units, d_in) is the Keras
     kernel transposed; all arrays numpy (host) or all torch CUDA tensors.  Returns Y (N, units) of the same kind."""
