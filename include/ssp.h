@@ -258,6 +258,21 @@ int ssp_vad_features(ssp_ctx* ctx, const void* samples, int sample_type, const s
  * mask_out: uint8[total frames]; n_speech_out (nullable): int32[n utterances] = marked frames per utterance. */
 int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy, const ssp_segments* frame_seg, int32_t mode, float zcr_gate,
                    float ampl, float amph, int32_t min_len, uint8_t* mask_out, int32_t* n_speech_out, int where, float* kernel_ms);
+/* The objective of VAD.py's threshold search (optimize / cv, VAD.py:189-220) for n_par threshold sets in one launch: for every set j
+ * and utterance u of frame_seg, counts_out[j][u][0..2] = tp, fp, fn = |mark & label|, |mark & ~label|, |~mark & label| over the
+ * utterance's frames, where mark is exactly the mask ssp_vad_detect(mode, zcr_gate[j], ampl[j], amph[j], min_len) writes (same state
+ * machine, same semantics: min_len a parameter, no last_end merge, the backward walk stops at frame 0) and label = (labels != 0).
+ * F1 = 2 tp / (2 tp + fp + fn) (sklearn.metrics.f1_score, VAD.py:210); no mask leaves the device.
+ * labels: uint8[total frames] laid out by frame_seg.  zcr_gate / ampl / amph: HOST arrays of n_par floats each, whatever `where` says
+ * (NaN thresholds and NaN power are legal: their comparisons are false, as in the reference).  mode 1 (VAD_frequency with a list of
+ * entropy thresholds, mark = !(entropy > ampl[j])) reads ampl only: zcr, zcr_gate and amph may be null, min_len must still be >= 1.
+ * `where` applies to zcr / power_or_entropy / labels / counts_out.  Integer counts, no atomics: the result is deterministic.
+ * SSP_ERR_INVALID: a null pointer that is needed, n_par < 1, min_len < 1, a bad mode or where.  SSP_ERR_UNSUPPORTED, before any
+ * launch: an utterance longer than 131072 frames (the word planes of one utterance live in 64 KiB of LDS), or counts_out larger than
+ * 2^31 entries.  One host wait per call, before the kernel is queued (the upload of the threshold arrays). */
+int ssp_vad_sweep(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy, const uint8_t* labels, const ssp_segments* frame_seg,
+                  int32_t mode, int32_t n_par, const float* zcr_gate, const float* ampl, const float* amph, int32_t min_len,
+                  int32_t* counts_out /* [n_par][n_utt][3] tp, fp, fn */, int where, float* kernel_ms);
 
 /* ---- GMM-UBM scoring: replaces the GMM[i].score(x_j) - UBM.score(x_j) double loop
  *      (GMM_UBM.py:181-197) and sklearn GaussianMixture.score_samples/score for diag models ---- */

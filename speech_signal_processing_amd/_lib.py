@@ -69,6 +69,7 @@ SIGNATURES = {
     "ssp_vad_frame_segments": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),
     "ssp_vad_features": (C.c_int, [_P, _F32P, C.c_int, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _F32P, _F32P, _F32P, C.c_int, _MSP]),
     "ssp_vad_detect": (C.c_int, [_P, _F32P, _F32P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, _P, _P, C.c_int, _MSP]),
+    "ssp_vad_sweep": (C.c_int, [_P, _F32P, _F32P, _P, _P, C.c_int32, C.c_int32, _F32P, _F32P, _F32P, C.c_int32, _P, C.c_int, _MSP]),
     "ssp_enframe": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int, _MSP]),
     "ssp_cepstrum": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, C.c_int32, _F32P, C.c_int32, C.c_int32, C.c_int32,
                                C.c_float, _F32P, C.c_int, _MSP]),

@@ -531,6 +531,55 @@ def vad_detect(ctx: Context, zcr, power_or_entropy, frame_seg: Segments, mode: i
     return (mask, count, ms.value) if timing else (mask, count)
 
 
+def _as_u8(x, name):
+    """-> (array-like kept alive, raw address, where) of frame labels: nonzero = speech"""
+    if _is_torch(x):
+        import torch
+        if not x.is_cuda:
+            raise ValueError("%s: torch tensors must live on the GPU (pass numpy arrays for host data)" % name)
+        if x.dtype != torch.uint8:
+            x = (x != 0).to(torch.uint8)
+        x = x.contiguous()
+        return x, x.data_ptr(), _lib.DEVICE
+    a = np.asarray(x)
+    a = np.ascontiguousarray(a if a.dtype == np.uint8 else a != 0, dtype=np.uint8)
+    return a, a.ctypes.data, _lib.HOST
+
+
+def vad_sweep(ctx: Context, zcr, power_or_entropy, labels, frame_seg: Segments, zcr_gate=35.0, ampl=0.3, amph=12.0, mode: int = 0,
+              min_len: int = 16, timing: bool = False):
+    """The counts behind the F1 score of ``vad_detect`` against frame labels, for many threshold sets in one launch (ssp_vad_sweep; the
+    objective of VAD.py's optimize, :204-210).  ``zcr_gate`` / ``ampl`` / ``amph``: scalars or arrays that broadcast against each other
+    to ``n_par`` sets (mode 1 reads ``ampl`` only: the entropy thresholds).  ``labels``: nonzero = speech, one per frame of frame_seg.
+    Returns counts int32 ``(n_par, n_utt, 3)`` = tp, fp, fn per set and utterance — a torch tensor for device inputs, numpy otherwise
+    [and kernel milliseconds when timing=True]."""
+    pk, pptr, where = _as_f32(power_or_entropy, "power_or_entropy")
+    lk, lptr, lwhere = _as_u8(labels, "labels")
+    if lwhere != where:
+        raise ValueError("labels and power_or_entropy must be arrays of the same kind")
+    if mode == 0:
+        zk, zptr, zwhere = _as_f32(zcr, "zcr")
+        if zwhere != where or int(np.prod(zk.shape)) < frame_seg.total:
+            raise ValueError("zcr and power must be arrays of the same kind holding every frame of frame_seg")
+        g, lo, hi = np.broadcast_arrays(*(np.asarray(v, dtype=np.float32) for v in (zcr_gate, ampl, amph)))
+    else:
+        zk, zptr = None, None
+        lo = np.asarray(ampl, dtype=np.float32)
+        g = hi = lo
+    if int(np.prod(pk.shape)) < frame_seg.total or int(np.prod(lk.shape)) < frame_seg.total:
+        raise ValueError("fewer values than frame_seg has frames")
+    g, lo, hi = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (g, lo, hi))
+    n_par = int(lo.shape[0])
+    counts = ctx._empty((n_par, frame_seg.n, 3), where, "int32")
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_vad_sweep(ctx._h, zptr, pptr, lptr, frame_seg._h, int(mode), n_par, g.ctypes.data if mode == 0 else None,
+                                          lo.ctypes.data, hi.ctypes.data if mode == 0 else None, int(min_len), _raw_ptr(counts, where), where,
+                                          C.byref(ms) if timing else None))
+    del zk, pk, lk
+    return (counts, ms.value) if timing else counts
+
+
 def gmm_em_stats(ctx: "Context", weights, means, covars, feats, timing: bool = False) -> dict:
     """E step + M-step sums of ONE EM iteration of a diagonal GMM on the GPU (ssp_gmm_em_stats).
     weights (K,), means (K,D), covars (K,D) float64; feats (n, D) float32 (numpy or device tensor).

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "cplx.hpp"
+#include "vad_machine.hpp"
 
 namespace ssp {
 namespace {
@@ -272,35 +273,7 @@ __global__ __launch_bounds__(256) void vad_peak_kernel(const T* __restrict__ x, 
 }
 
 // ---- detectors -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t ldw(const uint64_t* p) {  // a word every lane reads from the same address, as a wave-uniform value
-    const uint64_t v = *p;
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-// first index >= i whose bit is set (FLIP: clear), n if none.  Bits at and above n are clear in every plane.
-template <bool FLIP>
-__device__ __forceinline__ int vad_next(const uint64_t* P, int i, int n) {
-    if (i >= n) return n;
-    const int nw = (n + 63) >> 6;
-    int w = i >> 6;
-    uint64_t x = (FLIP ? ~ldw(P + w) : ldw(P + w)) & (~0ull << (i & 63));
-    while (x == 0) {
-        if (++w >= nw) return n;
-        x = FLIP ? ~ldw(P + w) : ldw(P + w);
-    }
-    const int r = w * 64 + __builtin_ctzll(x);
-    return r < n ? r : n;
-}
-// last index <= i whose bit is clear, -1 if none
-__device__ __forceinline__ int vad_prev_clear(const uint64_t* P, int i) {
-    int w = i >> 6;
-    uint64_t x = ~ldw(P + w) & (~0ull >> (63 - (i & 63)));
-    while (x == 0) {
-        if (--w < 0) return -1;
-        x = ~ldw(P + w);
-    }
-    return w * 64 + 63 - __builtin_clzll(x);
-}
-
+// (ldw / vad_next / vad_prev_clear and the state machine itself, vad_mark_runs: vad_machine.hpp, shared with vad_sweep.hip)
 // mode 0: VAD_detection (VAD.py:136-182) on (zcr, power); mode 1: VAD_frequency (VAD.py:185-186) on the entropy with threshold `ampl`.
 // gwords: three planes of `plane` words for utterances longer than 64 VAD_LDS_WORDS frames (null when there is none).
 __global__ __launch_bounds__(64 * VAD_WAVES) void vad_detect_kernel(const float* __restrict__ zcr, const float* __restrict__ pw,
@@ -344,36 +317,7 @@ __global__ __launch_bounds__(64 * VAD_WAVES) void vad_detect_kernel(const float*
             }
         }
         __threadfence_block();
-        // The reference's loop, frame by frame: a loud frame extends the run (end = i) and opens one if none is open (start = i); any
-        // other frame flushes the run if it is longer than min_len: start walks back and end forward over active frames, [start, end] is
-        // marked, the run is closed.  A run that is too short stays OPEN with its start (a later loud frame extends it across the gap);
-        // a run still open at the last frame is never flushed.  Runs of loud frames and the two walks are bit searches here.
-        // Not implemented: the last_end / min_distance merge (VAD.py:172-174) — last_end starts at -1 and is only set inside the branch
-        // that needs it positive, so the branch is never taken.  Deviation: the backward walk stops at frame 0, where Python's index -1
-        // would go on with the LAST frame (the same result whenever the last frame is not active).
-        {
-            int i = 0, start = 0;
-            bool open = false;
-            for (;;) {
-                const int jn = vad_next<false>(L, i, T);
-                if (jn >= T) break;
-                if (!open) start = jn, open = true;
-                const int k = vad_next<true>(L, jn, T);  // first frame behind the loud streak
-                if (k >= T) break;
-                const int end = k - 1;
-                if (end - start + 1 > min_len) {
-                    const int st = vad_prev_clear(A, start) + 1;
-                    const int en = vad_next<true>(A, end, T) - 1;
-                    for (int w = (st >> 6) + lane; w <= (en >> 6) && st <= en; w += 64) {
-                        const int lo = w == (st >> 6) ? (st & 63) : 0, hi = w == (en >> 6) ? (en & 63) : 63;
-                        M[w] |= (~0ull << lo) & (~0ull >> (63 - hi));
-                    }
-                    __threadfence_block();
-                    open = false;
-                }
-                i = k + 1;
-            }
-        }
+        vad_mark_runs(L, A, M, T, min_len, lane);  // the reference's sequential loop as bit searches on the words
         for (int base = 0; base < T; base += 64) {
             const int i = base + lane;
             const uint64_t m = ldw(M + (base >> 6));
