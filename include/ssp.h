@@ -225,6 +225,25 @@ int ssp_cmvn(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, in
  * from the reference tree: the arithmetic follows the published rastamat algorithm it ports (parity unpinned). */
 int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segments* frame_seg, int32_t n_bands, float fmax_hz,
                  int32_t plp_order, int32_t rasta, float lift, float* ceps_out, int where, float* kernel_ms);
+/* ---- PLP feature recipes: everything the reference does to sidekit's PLP cepstra before a GMM sees them, in one call — GMM_UBM.py:94-99
+ * (plp -> hstack(c, delta c) -> scale), UI/tmp.py:309-324 (per 1 s chunk: scale(plp), scale(hstack(mfcc, plp))), UI/GMM_UBM_GUI.py:85-100.
+ * logspec, frame_seg, n_bands .. lift: as ssp_plp_post.  delta_order 0..2 appends the regression delta over +-2 frames (edge padded
+ * inside the utterance, GMM_UBM.py:53-69) and the delta of it; scale != 0 standardises every PLP column per utterance as
+ * sklearn.preprocessing.scale does (statistics over the entries that are not NaN, a deviation below 10 FLT_EPSILON counts as 1, NaN stays).
+ * left: float[F x left_dim] columns finished elsewhere (the MFCC plan's output with cmvn = scale and the same delta_order), copied
+ * unchanged; null / 0 for none; left_dim must be a multiple of 1 + delta_order.  feats_out: [F x (left_dim + (1 + delta_order) plp_order)]
+ * float32 (out_type 0) or float64 (1, widened exactly), rows laid out for b = 0 .. delta_order as [left block b | PLP block b] with
+ * left blocks of left_dim / (1 + delta_order) columns: scale(hstack(mfcc, plp, d mfcc, d plp)) at delta_order 1.
+ * logspec, left and feats_out are all host or all device arrays (where); device arrays need only their natural alignment.  All work
+ * is ordered on the ctx stream and a device-pointer call returns without a host wait (kernel_ms == NULL).  21 bands / order 13 and
+ * 17 bands / order 13 run as one kernel, an utterance per workgroup, when the call's longest utterance fits 64 KiB of LDS (464 frames
+ * at 21 bands, 336 with delta_order 2; 512 at most); any other size or a longer utterance chains the stand-alone kernels on the stream.  An empty
+ * utterance writes nothing.  Limits as ssp_plp_post (SSP_ERR_UNSUPPORTED); bad arguments answer SSP_ERR_INVALID before any GPU work. */
+int ssp_plp_features(ssp_ctx* ctx, const float* logspec, const ssp_segments* frame_seg, int32_t n_bands, float fmax_hz,
+                     int32_t plp_order, int32_t rasta, float lift,
+                     const float* left, int32_t left_dim,          /* may be null / 0 */
+                     int32_t delta_order /* 0..2 */, int32_t scale /* 0 | 1 */,
+                     void* feats_out, int out_type /* 0 float32 | 1 float64 */, int where, float* kernel_ms);
 
 /* ---- voice activity detection: replaces VAD.py's per-frame Python loops (enframe VAD.py:28-50, energy :67-76, ZCR :53-64,
  *      spectrum_entropy :79-105, feature :108-119, the peak normalisation of wavdata :131) and its two detectors (VAD_detection

@@ -1,7 +1,9 @@
 """GPU-backed mirror of the hot-path functions of the reference's ``GMM_UBM.py``.
 
 * ``delta``            GMM_UBM.py:53-69
-* ``extract_feature``  GMM_UBM.py:72-118  (sidekit mfcc -> [c, delta c] -> per-utterance scale; one fused kernel; 'PLP': plp back end)
+* ``extract_feature``  GMM_UBM.py:72-118  (sidekit mfcc -> [c, delta c] -> per-utterance scale; one fused kernel; 'PLP' and 'MFCC_PLP':
+                       the fused PLP tail, api.plp_features)
+* ``chunk_features`` / ``identify_language``  the language mode's read-out, UI/tmp.py:303-360
 * ``score_matrix``     the scoring loops GMM_UBM.py:181-197 as a function that returns what the reference prints
 * ``GMM``              GMM_UBM.py:134-199: trains one GMM per speaker + the UBM (EM on the GPU, gmm_train.GaussianMixture)
                        or takes pre-trained models, then scores
@@ -16,7 +18,7 @@ import numpy as np
 
 from . import api, frontend
 from .gmm_train import GaussianMixture, fit_many
-from .sidekit_features import mfcc, plp, plp_batch  # noqa: F401  (GMM_UBM.py:20 imports both names)
+from .sidekit_features import mfcc, mfcc_batch, plp, plp_batch, plp_features_batch  # noqa: F401  (GMM_UBM.py:20 imports both names)
 
 
 def delta(feat, N=2):
@@ -43,8 +45,8 @@ def extract_feature(x, y, is_train=False, feature_type='MFCC', fs=16000, delta_o
     """GMM_UBM.py:72-118.  x: list of 1-D audio arrays, y: list of labels.
     Returns (feature, y) or (train_data, feature, y); every feature is (T_i, 26) float64 = scale([c, delta c]).
     ``delta_order=2`` appends delta-delta (39-d) — an extension used by the benchmark configs."""
-    if feature_type == 'PLP':  # GMM_UBM.py:94-99: plp -> hstack(c, delta c) -> scale
-        feature = _extract_plp(x, int(fs), int(delta_order))
+    if feature_type in ('PLP', 'MFCC_PLP'):  # GMM_UBM.py:94-99: plp -> hstack(c, delta c) -> scale; UI/tmp.py:319-324: hstack(mfcc, plp)
+        feature = _extract_plp(x, int(fs), int(delta_order), with_mfcc=feature_type == 'MFCC_PLP')
         if not is_train:
             return feature, y
         train_data = {}
@@ -64,15 +66,49 @@ def extract_feature(x, y, is_train=False, feature_type='MFCC', fs=16000, delta_o
     return train_data, feature, y
 
 
-def _extract_plp(x, fs, delta_order):
-    """[c, delta c (, delta delta c)] of the PLP cepstra, per-utterance scaled; every stage on the GPU."""
-    ctx = api.default_context()
-    c, fseg = plp_batch(x, fs=fs)
-    blocks = [c]
-    for _ in range(delta_order):
-        blocks.append(api.delta_features(ctx, blocks[-1], fseg, 2))
-    feats = np.asarray(api.cmvn_features(ctx, np.ascontiguousarray(np.hstack(blocks)), fseg), dtype=np.float64)
+def _extract_plp(x, fs, delta_order, with_mfcc=False):
+    """[c, delta c (, delta delta c)] of the PLP cepstra, per-utterance scaled (with_mfcc: [mfcc | plp | d mfcc | d plp ...], 'MFCC_PLP');
+    one upload, the front end(s) and the fused tail on the device, one download."""
+    feats, fseg = plp_features_batch(x, fs=fs, with_mfcc=with_mfcc, delta_order=delta_order, scale=True, out_dtype=np.float64)
     return [feats[fseg.offsets[i]:fseg.offsets[i + 1]] for i in range(len(x))]
+
+
+def chunk_features(audio, feature_type='MFCC', fs=16000):
+    """UI/tmp.py:303-326: the audio cut into whole 1 s chunks, every chunk's scaled features without deltas — 'MFCC' scale(mfcc(x)[0]),
+    'PLP' scale(plp(x)[0]), 'MFCC_PLP' scale(hstack(mfcc(x)[0], plp(x)[0])) — all chunks in one batch.  Returns a list of
+    (98, 13 or 26) float64 arrays (at 16 kHz)."""
+    if feature_type not in ('MFCC', 'PLP', 'MFCC_PLP'):
+        raise NameError  # UI/tmp.py:325-326
+    audio = np.asarray(audio).reshape(-1)
+    fs = int(fs)
+    chunks = [audio[j * fs:(j + 1) * fs] for j in range(audio.shape[0] // fs)]
+    if not chunks:
+        return []
+    if feature_type == 'MFCC':
+        feats, fseg = mfcc_batch(chunks, fs=fs, scale=True, out_dtype=np.float64)
+    else:
+        feats, fseg = plp_features_batch(chunks, fs=fs, with_mfcc=feature_type == 'MFCC_PLP', scale=True, out_dtype=np.float64)
+    return [feats[fseg.offsets[i]:fseg.offsets[i + 1]] for i in range(len(chunks))]
+
+
+def language_readout(pred, names=('Chinese', 'English', 'Japanese')):
+    """The arithmetic of UI/tmp.py:345-360 on a (chunks, languages) matrix of score differences: per chunk the arg-max, its name (index 0,
+    index 1, anything else: the reference's if / elif / else) and exp(max) / sum exp of its row.  -> (names, probabilities)."""
+    pred = np.asarray(pred, dtype=np.float64)
+    if pred.ndim != 2 or pred.shape[1] < 1:
+        raise ValueError("pred must be (chunks, languages)")
+    am = pred.argmax(axis=1)
+    out = [names[0] if i == 0 else (names[1] if i == 1 else names[2]) for i in am]
+    prob = np.exp(pred.max(axis=1)) / np.exp(pred).sum(axis=1)
+    return out, prob
+
+
+def identify_language(models, ubm, features, names=('Chinese', 'English', 'Japanese')):
+    """UI/tmp.py:337-360: pred[j, i] = models[i].score(features[j]) - ubm.score(features[j]) for every chunk j (``score_matrix``), the
+    language of every chunk and its probability exp(max) / sum exp.  Returns (names, probabilities, pred)."""
+    pred, _ = score_matrix(models, ubm, features)
+    out, prob = language_readout(pred, names)
+    return out, prob, pred
 
 
 def score_matrix(models, ubm, feats):

@@ -468,6 +468,56 @@ def plp_post(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_ord
     return (out, ms.value) if timing else out
 
 
+def plp_feature_columns(plp_order: int, left_dim: int = 0, delta_order: int = 0):
+    """Column layout of ``plp_features``: -> (left columns, PLP columns), index arrays into an output row.  For b = 0 .. delta_order the
+    row holds [left block b | PLP block b], a left block being left_dim / (1 + delta_order) columns wide."""
+    nblk = 1 + int(delta_order)
+    if left_dim % nblk:
+        raise ValueError("left_dim=%d must be a multiple of 1 + delta_order = %d" % (left_dim, nblk))
+    lw = left_dim // nblk
+    bw = lw + int(plp_order)
+    col = np.arange(nblk * bw).reshape(nblk, bw)
+    return col[:, :lw].reshape(-1), col[:, lw:].reshape(-1)
+
+
+def plp_features(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_order: int = 13, rasta: bool = True, lift: float = 0.6,
+                 left=None, delta_order: int = 0, scale: bool = False, out_dtype=np.float32, timing: bool = False, out=None):
+    """The PLP feature recipes of the reference on the GPU (ssp_plp_features): (frames, bands) ln critical-band energies ->
+    RASTA, cepstra, delta (delta_order >= 1), delta of delta (2), per-utterance scale — one kernel per call for 21 / 17 bands at order 13.
+    ``left``: (frames, left_dim) finished columns (the MFCC plan's output with cmvn = scale and the same delta_order), interleaved
+    unchanged: rows are [left block b | PLP block b] for b = 0 .. delta_order (``plp_feature_columns``).  numpy arrays in, numpy array
+    out; torch cuda tensors in, torch cuda tensor out (no host wait).  Returns feats (frames, left_dim + (1 + delta_order) plp_order)
+    of ``out_dtype`` (float32 or float64) [and kernel milliseconds when timing=True]."""
+    out_dtype = np.dtype(out_dtype)
+    if out_dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError("out_dtype must be float32 or float64")
+    keep, ptr, where = _as_f32(logspec, "logspec")
+    if keep.ndim != 2:
+        raise ValueError("logspec must be (frames, bands)")
+    F = int(keep.shape[0])
+    lkeep, lptr, left_dim = None, None, 0
+    if left is not None:
+        lkeep, lptr, lwhere = _as_f32(left, "left")
+        if lwhere != where:
+            raise ValueError("left must be the same kind of array as logspec")
+        if lkeep.ndim != 2 or int(lkeep.shape[0]) != F:
+            raise ValueError("left must be (frames, left_dim)")
+        left_dim = int(lkeep.shape[1])
+    D = left_dim + (1 + int(delta_order)) * int(plp_order) if 0 <= int(delta_order) <= 2 else left_dim + int(plp_order)
+    if out is None:
+        out = ctx._empty((F, D), where, out_dtype.name)
+    elif tuple(out.shape) != (F, D) or _is_torch(out) != (where == _lib.DEVICE) or str(out.dtype).split(".")[-1] != out_dtype.name \
+            or not (out.is_contiguous() if _is_torch(out) else out.flags.c_contiguous):
+        raise ValueError("out must be a contiguous (%d, %d) %s array of the same kind as logspec" % (F, D, out_dtype.name))
+    ms = C.c_float(0.0)
+    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_plp_features(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), float(fmax_hz), int(plp_order), int(bool(rasta)),
+                                             float(lift), lptr, left_dim, int(delta_order), int(bool(scale)), optr,
+                                             1 if out_dtype == np.float64 else 0, where, C.byref(ms) if timing else None))
+    return (out, ms.value) if timing else out
+
+
 def vad_num_frames(n_samples: int, step: int = 128) -> int:
     """math.ceil(n / step) — VAD.py:37 (no GPU)."""
     out = C.c_int64()

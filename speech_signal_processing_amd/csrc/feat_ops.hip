@@ -162,6 +162,17 @@ int launch_cmvn(const float* in, float* out, const int64_t* frame_off_dev, int64
     return SSP_OK;
 }
 
+// delta_kernel<2> over a whole matrix whose segments start at row 0 (the composed path of ssp_plp_features, plp.hip)
+int launch_delta2(const float* in, float* out, const int64_t* frame_off_dev, int64_t n_utt, int dim, int64_t n_rows, hipStream_t stream) {
+    if (n_rows <= 0) return SSP_OK;
+    const int64_t n_blocks = ceil_div<int64_t>(n_rows, DELTA_RB);
+    if (n_blocks > INT32_MAX || n_utt > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "delta: matrix too large for one launch");
+    hipLaunchKernelGGL(delta_kernel<2>, dim3((unsigned)n_blocks), dim3(256), 0, stream, in, out, frame_off_dev, (int)n_utt, dim, 2, 1.0f / 10.0f,
+                       (int64_t)0, n_rows);
+    SSP_HIP(hipGetLastError());
+    return SSP_OK;
+}
+
 // utils/processing.py:19-38 — framing + window; out is row-major (frame_size, n_frames) like the reference ndarray
 __global__ __launch_bounds__(256) void enframe_kernel(const float* __restrict__ x, int64_t n, int frame_size, int step,
                                                       int64_t n_frames, const float* __restrict__ window,

@@ -424,7 +424,8 @@ class Data_gen:
         return feature, label
 
     def _extract(self, x, y, feature_type='MFCC'):
-        plan = self._plan(feature_type)
+        # ('MFCC_PLP', UI/tmp.py:319-324: hstack(mfcc, plp) per chunk, runs both front ends through sidekit_features.plp_features_batch)
+        plan = None if feature_type == 'MFCC_PLP' else self._plan(feature_type)
         sr = self.sample_rate
         chunks, labels = [], []
         for xi, yi in zip(x, y):
@@ -434,11 +435,15 @@ class Data_gen:
                 labels.append(yi)
         if not chunks:
             return [], []
-        seg = api.Segments.from_lengths(plan.ctx, [sr] * len(chunks))
-        fseg = plan.frame_segments(seg)
-        feats = plan.run(api.flatten_signals(chunks)[0], seg, fseg)
-        if feature_type == 'PLP':
-            feats = api.plp_post(plan.ctx, feats, fseg, sr / 2.0)
+        if plan is None:
+            from .sidekit_features import plp_features_batch
+            feats, fseg = plp_features_batch(chunks, fs=int(sr), with_mfcc=True)
+        else:
+            seg = api.Segments.from_lengths(plan.ctx, [sr] * len(chunks))
+            fseg = plan.frame_segments(seg)
+            feats = plan.run(api.flatten_signals(chunks)[0], seg, fseg)
+            if feature_type == 'PLP':
+                feats = api.plp_post(plan.ctx, feats, fseg, sr / 2.0)
         feats = np.asarray(feats, dtype=np.float64)
         feature, label = [], []
         for i, lab in enumerate(labels):

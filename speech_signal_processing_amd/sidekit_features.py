@@ -39,6 +39,55 @@ def plp_batch(signals, fs=16000, nwin=0.025, shift=0.01, plp_order=13, prefac=0.
     return api.plp_post(plan.ctx, logspec, fseg, fs / 2.0, plp_order, rasta), fseg
 
 
+@functools.lru_cache(maxsize=8)
+def _mfcc_recipe_plan(fs, nwin, shift, nceps, prefac, delta_order, cmvn):
+    return api.MfccPlan(api.default_context(), frontend.preset_sidekit(fs=fs, nwin=nwin, shift=shift, nceps=nceps, prefac=prefac,
+                                                                       delta_order=delta_order, cmvn=cmvn))
+
+
+def _upload(flat):
+    """the flat sample array on the default context's device, in one copy (int16 PCM stays int16)"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(flat)).to("cuda:%d" % api.default_context().device)
+
+
+def mfcc_batch(signals, fs=16000, nwin=0.025, shift=0.01, nceps=13, prefac=0.97, delta_order=0, scale=False, out_dtype=np.float64):
+    """sidekit MFCC cepstra of a list of utterances in one launch (the chunk loop of UI/tmp.py:309-313 as a batch), with the recipe's
+    delta blocks and per-utterance scale when asked for: -> (feats (sum T_i, (1 + delta_order) nceps) array, frame Segments)."""
+    plan = _mfcc_recipe_plan(int(fs), float(nwin), float(shift), int(nceps), float(prefac), int(delta_order), int(bool(scale)))
+    flat, lens = api.flatten_signals(signals)
+    seg = api.Segments.from_lengths(plan.ctx, lens)
+    fseg = plan.frame_segments(seg)
+    return np.asarray(plan.run(flat, seg, fseg), dtype=out_dtype), fseg
+
+
+def plp_features_batch(signals, fs=16000, nwin=0.025, shift=0.01, plp_order=13, prefac=0.97, rasta=True, with_mfcc=False, nceps=13,
+                       delta_order=0, scale=False, out_dtype=np.float64):
+    """The PLP and MFCC+PLP feature recipes of a list of utterances (GMM_UBM.py:94-99, UI/tmp.py:314-324): the samples go to the device
+    once, the PLP front end (and, ``with_mfcc``, the sidekit MFCC plan with cmvn = scale and the same delta_order) runs on them there,
+    api.plp_features makes the final rows on the device and one copy brings them back.  Rows are [plp | d plp ...], with_mfcc
+    [mfcc | plp | d mfcc | d plp ...].  -> (feats (sum T_i, D) array of out_dtype, frame Segments)."""
+    out_dtype = np.dtype(out_dtype)
+    plan = _plp_plan(int(fs), float(nwin), float(shift), float(prefac))
+    flat, lens = api.flatten_signals(signals)
+    seg = api.Segments.from_lengths(plan.ctx, lens)
+    fseg = plan.frame_segments(seg)
+    D = (1 + int(delta_order)) * (int(plp_order) + (int(nceps) if with_mfcc else 0))
+    if fseg.total == 0:
+        return np.zeros((0, D), dtype=out_dtype), fseg
+    dev = _upload(flat)
+    logspec = plan.run(dev, seg, fseg)
+    left = None
+    if with_mfcc:
+        mplan = _mfcc_recipe_plan(int(fs), float(nwin), float(shift), int(nceps), float(prefac), int(delta_order), int(bool(scale)))
+        mfseg = mplan.frame_segments(seg)
+        assert np.array_equal(mfseg.offsets, fseg.offsets), "the MFCC and PLP plans cut different frames"
+        left = mplan.run(dev, seg, mfseg)
+    feats = api.plp_features(plan.ctx, logspec, fseg, fs / 2.0, plp_order, rasta, left=left, delta_order=delta_order, scale=scale,
+                             out_dtype=out_dtype)
+    return feats.cpu().numpy(), fseg
+
+
 def plp(input_sig, nwin=0.025, fs=16000, plp_order=13, shift=0.01, get_spec=False, get_mspec=False, prefac=0.97, rasta=True):
     """sidekit plp (call sites GMM_UBM.py:95, d_vector.py:93, UI/GMM_UBM_GUI.py:93): [cepstra (T, plp_order), None, None, None].
     (log-energy / spectra, items 1-3 of sidekit's list, are not used by the reference and not computed.)"""
