@@ -1022,12 +1022,95 @@ class DnnForward:
             pass
 
 
-class DnnTrainer:
+class _Trainer:
+    """What DnnTrainer, LstmTrainer and GruTrainer share: the data checks, epoch / evaluate, the step counter and the handle's life.  A
+    subclass names its entry points' prefix (ssp_<prefix>_trainer_*), creates ``_h`` and sets ``_row``, the shape of one row of X."""
+
+    _PREFIX = ""
+    _CHANNEL_AXIS = False  # X may come with a trailing axis of one channel, (N, T, D, 1): what the Keras model takes
+
+    def _fn(self, name):
+        return getattr(self._lib, "ssp_%s_trainer_%s" % (self._PREFIX, name))
+
+    def _data(self, X, labels):
+        xk, xp, where = _as_f32(X, "X")
+        if self._CHANNEL_AXIS and xk.ndim == 4 and int(xk.shape[3]) == 1:
+            xk = xk.reshape(xk.shape[0], xk.shape[1], xk.shape[2])
+        if tuple(int(v) for v in xk.shape[1:]) != self._row:
+            raise ValueError("X must be (N, %s)" % ", ".join("%d" % v for v in self._row))
+        if where == _lib.DEVICE:
+            import torch
+            if not (_is_torch(labels) and labels.is_cuda):
+                raise ValueError("labels must live where X lives")
+            lk = labels.to(torch.int32).contiguous()
+            lp = lk.data_ptr()
+        else:
+            lk = np.ascontiguousarray(labels, dtype=np.int32)
+            lp = lk.ctypes.data
+        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
+            raise ValueError("one label per row of X")
+        return (xk, lk), xp, lp, int(xk.shape[0]), where
+
+    def _epoch(self, X, labels, order, batch_size, lr, extra, timing):
+        keep, xp, lp, N, where = self._data(X, labels)
+        ok, op = None, None
+        if order is not None:
+            ok = np.ascontiguousarray(order, dtype=np.int64)
+            if ok.shape != (N,):
+                raise ValueError("order must hold N row indices")
+            op = ok.ctypes.data
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._fn("epoch")(self._h, xp, lp, N, op, int(batch_size), float(lr), *extra, C.byref(loss), C.byref(corr), where,
+                                         C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
+        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
+        as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
+        return self._epoch(X, labels, order, batch_size, lr, (), timing)
+
+    def evaluate(self, X, labels, timing: bool = False):
+        """loss sum and correct rows over (X, labels), dropout off; nothing is updated"""
+        keep, xp, lp, N, where = self._data(X, labels)
+        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._fn("evaluate")(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
+        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+
+    def _read_into(self, name, out):
+        """the array ``read`` fills for tensor ``name``: a new one, or ``out`` when it is a contiguous float32 array of the tensor's size"""
+        if out is None:
+            return np.empty(self.shapes[name], dtype=np.float32)
+        if out.dtype != np.float32 or out.size != int(np.prod(self.shapes[name])) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous float32 array of %d entries" % int(np.prod(self.shapes[name])))
+        return out
+
+    @property
+    def steps(self) -> int:
+        t = C.c_int64(0)
+        _lib.check(self._fn("steps")(self._h, C.byref(t)))
+        return t.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DnnTrainer(_Trainer):
     """A fully connected network with its gradients and Adam state on the GPU (ssp_dnn_trainer): nn_model.inference's spk.fit,
     d_vector.py:168-206.  ``layers`` = list of (W (d_in, units) float32 in Keras' layout, bias (units,) or None, relu bool, dropout rate
     after the activation).  X and labels are numpy arrays (host) or torch CUDA tensors (X float32, labels int32)."""
 
     WHAT = {"W": 0, "b": 1, "dW": 2, "db": 3, "mW": 4, "mb": 5, "vW": 6, "vb": 7}
+    _PREFIX = "dnn"
 
     def __init__(self, ctx: Context, layers, max_batch: int = 128):
         self.ctx = ctx
@@ -1044,6 +1127,7 @@ class DnnTrainer:
             if w.shape[0] != dims[i] or (bs[i] is not None and bs[i].shape[0] != dims[i + 1]):
                 raise ValueError("layer %d: kernel (d_in, units) / bias (units,) do not chain" % i)
         self.dims, self.has_bias, self.max_batch = dims, [b is not None for b in bs], int(max_batch)
+        self._row = (dims[0],)
         c_dims = (C.c_int32 * (n + 1))(*dims)
         c_r = (C.c_int32 * n)(*[1 if r else 0 for _, _, r, _ in layers])
         c_p = (C.c_float * n)(*[float(p) for _, _, _, p in layers])
@@ -1053,46 +1137,10 @@ class DnnTrainer:
         _lib.check(self._lib.ssp_dnn_trainer_create(ctx._h, n, c_dims, c_r, c_p, c_w, c_b, int(max_batch), C.byref(h)))
         self._h = h
 
-    def _data(self, X, labels):
-        xk, xp, where = _as_f32(X, "X")
-        if xk.ndim != 2 or int(xk.shape[1]) != self.dims[0]:
-            raise ValueError("X must be (N, %d)" % self.dims[0])
-        if where == _lib.DEVICE:
-            import torch
-            if not (_is_torch(labels) and labels.is_cuda):
-                raise ValueError("labels must live where X lives")
-            lk = labels.to(torch.int32).contiguous()
-            lp = lk.data_ptr()
-        else:
-            lk = np.ascontiguousarray(labels, dtype=np.int32)
-            lp = lk.ctypes.data
-        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
-            raise ValueError("one label per row of X")
-        return (xk, lk), xp, lp, int(xk.shape[0]), where
-
     def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, seed: int = 0, timing: bool = False):
         """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
-        as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        ok, op = None, None
-        if order is not None:
-            ok = np.ascontiguousarray(order, dtype=np.int64)
-            if ok.shape != (N,):
-                raise ValueError("order must hold N row indices")
-            op = ok.ctypes.data
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_dnn_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), int(seed) & (2 ** 64 - 1),
-                                                       C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
-
-    def evaluate(self, X, labels, timing: bool = False):
-        """loss sum and correct rows over (X, labels) with dropout off; nothing is updated"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_dnn_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+        as the steps ran; with ``timing`` the kernel milliseconds as a third entry.  ``seed`` keys the dropout"""
+        return self._epoch(X, labels, order, batch_size, lr, (int(seed) & (2 ** 64 - 1),), timing)
 
     def read(self, what: str, layer: int):
         """'W', 'b' (parameters), 'dW', 'db' (the last step's gradients), 'mW', 'mb', 'vW', 'vb' (Adam's moments) of ``layer`` -> numpy"""
@@ -1103,23 +1151,6 @@ class DnnTrainer:
         out = np.empty((self.dims[layer + 1],) if code & 1 else (self.dims[layer], self.dims[layer + 1]), dtype=np.float32)
         _lib.check(self._lib.ssp_dnn_trainer_read(self._h, code, layer, out.ctypes.data))
         return out
-
-    @property
-    def steps(self) -> int:
-        t = C.c_int64(0)
-        _lib.check(self._lib.ssp_dnn_trainer_steps(self._h, C.byref(t)))
-        return t.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_dnn_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def dropout_keep(seed: int, step: int, layer: int, rows: int, width: int, rate: float):
@@ -1213,7 +1244,7 @@ class LstmForward:
             pass
 
 
-class LstmTrainer:
+class LstmTrainer(_Trainer):
     """The recurrent d-vector network with its gradients and Adam state on the GPU (ssp_lstm_trainer): nn_model.inference_lstm's spk.fit,
     d_vector.py:271-294 — one LSTM(units) over a (T, d_in) chunk, Dense(n_class) and a softmax on the last hidden state.  W (d_in, 4 units),
     U (units, 4 units), b (4 units,) or None, Wd (units, n_class), bd (n_class,) or None in Keras' layout; ``recurrent_activation``
@@ -1222,6 +1253,7 @@ class LstmTrainer:
 
     WHAT = {"": 0, "d": 1, "m": 2, "v": 3}
     TENSOR = {"W": 0, "U": 1, "b": 2, "Wd": 3, "bd": 4}
+    _PREFIX = "lstm"
 
     def __init__(self, ctx: Context, W, U, b, Wd, bd, *, T, recurrent_activation, max_batch: int = 128):
         if recurrent_activation not in LSTM_ACTIVATIONS:
@@ -1234,6 +1266,7 @@ class LstmTrainer:
         if Wd.ndim != 2 or Wd.shape[0] != U.shape[0] or (bd is not None and bd.shape[0] != Wd.shape[1]):
             raise ValueError("Wd must be (units, n_class) and bd (n_class,)")
         self.d_in, self.units, self.n_class, self.T = int(W.shape[0]), int(U.shape[0]), int(Wd.shape[1]), int(T)
+        self._row = (self.T, self.d_in)
         self.recurrent_activation, self.max_batch = recurrent_activation, int(max_batch)
         self.has_bias = {"b": b is not None, "bd": bd is not None}
         self.shapes = {"W": (self.d_in, 4 * self.units), "U": (self.units, 4 * self.units), "b": (4 * self.units,),
@@ -1243,47 +1276,6 @@ class LstmTrainer:
                                                      W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data, Wd.ctypes.data,
                                                      None if bd is None else bd.ctypes.data, int(max_batch), C.byref(h)))
         self._h = h
-
-    def _data(self, X, labels):
-        xk, xp, where = _as_f32(X, "X")
-        if xk.ndim != 3 or int(xk.shape[1]) != self.T or int(xk.shape[2]) != self.d_in:
-            raise ValueError("X must be (N, %d, %d)" % (self.T, self.d_in))
-        if where == _lib.DEVICE:
-            import torch
-            if not (_is_torch(labels) and labels.is_cuda):
-                raise ValueError("labels must live where X lives")
-            lk = labels.to(torch.int32).contiguous()
-            lp = lk.data_ptr()
-        else:
-            lk = np.ascontiguousarray(labels, dtype=np.int32)
-            lp = lk.ctypes.data
-        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
-            raise ValueError("one label per row of X")
-        return (xk, lk), xp, lp, int(xk.shape[0]), where
-
-    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
-        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
-        as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        ok, op = None, None
-        if order is not None:
-            ok = np.ascontiguousarray(order, dtype=np.int64)
-            if ok.shape != (N,):
-                raise ValueError("order must hold N row indices")
-            op = ok.ctypes.data
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_lstm_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), C.byref(loss), C.byref(corr), where,
-                                                        C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
-
-    def evaluate(self, X, labels, timing: bool = False):
-        """loss sum and correct rows over (X, labels); nothing is updated"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_lstm_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
 
     STEP_LAUNCHES = ("forward+stash", "dense head", "loss", "dWd", "dh_T", "backward through time", "dW+db", "dU", "adam")
 
@@ -1307,29 +1299,9 @@ class LstmTrainer:
                 break
         else:
             raise ValueError("unknown tensor %r" % (what,))
-        if out is None:
-            out = np.empty(self.shapes[name], dtype=np.float32)
-        elif out.dtype != np.float32 or out.size != int(np.prod(self.shapes[name])) or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous float32 array of %d entries" % int(np.prod(self.shapes[name])))
+        out = self._read_into(name, out)
         _lib.check(self._lib.ssp_lstm_trainer_read(self._h, self.WHAT[prefix], self.TENSOR[name], out.ctypes.data))
         return out
-
-    @property
-    def steps(self) -> int:
-        t = C.c_int64(0)
-        _lib.check(self._lib.ssp_lstm_trainer_steps(self._h, C.byref(t)))
-        return t.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_lstm_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 GRU_ACTIVATIONS = LSTM_ACTIVATIONS
@@ -1463,7 +1435,7 @@ def l2_normalize(ctx: Context, X, eps: float = 1e-12, timing: bool = False):
     return (Y, ms.value) if timing else Y
 
 
-class GruTrainer:
+class GruTrainer(_Trainer):
     """The conv + GRU d-vector network with its gradients and Adam state on the GPU (ssp_gru_trainer): nn_model.inference_gru's spk.fit,
     d_vector.py:213-269 — Conv2D (l2-regularised kernel, lambda 0.01) -> n GRU layers -> mean over time -> Dense(E) -> l2_normalize ->
     Dense(n_class) softmax.  ``conv`` = (K (kh, kw, 1, F), b (F,) or None, strides), ``grus`` = [(W (d_in, 3 units), U (units, 3 units),
@@ -1476,6 +1448,8 @@ class GruTrainer:
 
     WHAT = {"": 0, "d": 1, "m": 2, "v": 3}
     MAX_LAYERS = 4
+    _PREFIX = "gru"
+    _CHANNEL_AXIS = True
 
     def __init__(self, ctx: Context, conv, grus, dense, head, *, T, D, recurrent_activation, reset_after, max_batch: int = 128):
         if recurrent_activation not in GRU_ACTIVATIONS:
@@ -1495,6 +1469,7 @@ class GruTrainer:
         bc = vec(bc, F, "conv bias")
         sh, sw = int(strides[0]), int(strides[1])
         self.T, self.D, self.strides = int(T), int(D), (sh, sw)
+        self._row = (self.T, self.D)
         if sh < 1 or sw < 1 or self.D < 1:
             raise ValueError("strides and D must be >= 1")
         To, Do = conv2d_same_out_shape(max(self.T, 1), self.D, (sh, sw))
@@ -1544,49 +1519,6 @@ class GruTrainer:
                                                     GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, int(max_batch), C.byref(h)))
         self._h = h
 
-    def _data(self, X, labels):
-        xk, xp, where = _as_f32(X, "X")
-        if xk.ndim == 4 and int(xk.shape[3]) == 1:
-            xk = xk.reshape(xk.shape[0], xk.shape[1], xk.shape[2])
-        if xk.ndim != 3 or int(xk.shape[1]) != self.T or int(xk.shape[2]) != self.D:
-            raise ValueError("X must be (N, %d, %d)" % (self.T, self.D))
-        if where == _lib.DEVICE:
-            import torch
-            if not (_is_torch(labels) and labels.is_cuda):
-                raise ValueError("labels must live where X lives")
-            lk = labels.to(torch.int32).contiguous()
-            lp = lk.data_ptr()
-        else:
-            lk = np.ascontiguousarray(labels, dtype=np.int32)
-            lp = lk.ctypes.data
-        if lk.ndim != 1 or int(lk.shape[0]) != int(xk.shape[0]):
-            raise ValueError("one label per row of X")
-        return (xk, lk), xp, lp, int(xk.shape[0]), where
-
-    def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
-        """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum with the regulariser's
-        term, correct rows) as the steps ran; with ``timing`` the kernel milliseconds as a third entry"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        ok, op = None, None
-        if order is not None:
-            ok = np.ascontiguousarray(order, dtype=np.int64)
-            if ok.shape != (N,):
-                raise ValueError("order must hold N row indices")
-            op = ok.ctypes.data
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_gru_trainer_epoch(self._h, xp, lp, N, op, int(batch_size), float(lr), C.byref(loss), C.byref(corr), where,
-                                                       C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
-
-    def evaluate(self, X, labels, timing: bool = False):
-        """loss sum and correct rows over (X, labels); nothing is updated"""
-        keep, xp, lp, N, where = self._data(X, labels)
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_gru_trainer_evaluate(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
-
     STEP_KINDS = ("conv forward", "mean+dense+l2+head", "loss+regulariser", "head+l2+dense+mean backward", "conv backward", "adam+repack")
     LAYER_KINDS = ("projection", "forward steps", "backward steps", "dW+db", "dU", "dx")
 
@@ -1617,29 +1549,9 @@ class GruTrainer:
         """a tensor name (parameters), or one with a prefix 'd' (the last step's gradients), 'm' or 'v' (Adam's moments), e.g. 'dgru0_U',
         'mhead_W' -> numpy; ``out``: a float32 array of the tensor's size to fill instead (it needs 4-byte alignment only)"""
         prefix, name = self._name(what)
-        if out is None:
-            out = np.empty(self.shapes[name], dtype=np.float32)
-        elif out.dtype != np.float32 or out.size != int(np.prod(self.shapes[name])) or not out.flags.c_contiguous:
-            raise ValueError("out must be a contiguous float32 array of %d entries" % int(np.prod(self.shapes[name])))
+        out = self._read_into(name, out)
         _lib.check(self._lib.ssp_gru_trainer_read(self._h, self.WHAT[prefix], self.TENSOR[name], out.ctypes.data))
         return out
-
-    @property
-    def steps(self) -> int:
-        t = C.c_int64(0)
-        _lib.check(self._lib.ssp_gru_trainer_steps(self._h, C.byref(t)))
-        return t.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_gru_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _gru_vec(b, n, what):

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "nn_device.hpp"
 
 namespace ssp {
 
@@ -13,7 +14,6 @@ int launch_dense_reg(ssp_ctx* ctx, const float* dX, int64_t N, int d_in, const f
                      hipStream_t s);  // cosine.hip
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int DBM = 128;  // units per block step
 constexpr int DBN = 128;  // samples per workgroup
@@ -28,10 +28,6 @@ struct DenseArgs {
     float* Y;           // [N x units]
     int64_t N;
     int32_t d_in, units, relu;
-};
-
-struct __attribute__((packed, aligned(4))) f4u {
-    float x, y, z, w;
 };
 
 // a [128 x DBK] slab of a row-major matrix goes global -> registers -> MFMA operand image [q=DBK/8][h=2] planes of [row=128][e=4]

@@ -14,13 +14,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "nn_device.hpp"
 
 namespace ssp {
 
 int launch_dense_reg(ssp_ctx* ctx, const float* dX, int64_t N, int d_in, const float* dW, const float* dB, int units, int relu, float* dY,
                      hipStream_t s);  // cosine.hip
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
@@ -36,10 +36,6 @@ struct ChainArgs {
     int64_t N;
     int32_t n_layers, d_in, d_out;
     int32_t relu[CH_MAXL];
-};
-
-struct __attribute__((packed, aligned(4))) f4u {
-    float x, y, z, w;
 };
 
 __global__ __launch_bounds__(256, 3) void dnn_chain_kernel(ChainArgs a) {

@@ -23,17 +23,13 @@
 #include <vector>
 
 #include "common.hpp"
+#include "nn_device.hpp"
+#include "trainer_core.hpp"
 
 namespace ssp {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int DT_MAXW = 4096;  // widest layer
 constexpr int DT_MAXB = 1024;  // largest batch
-
-struct __attribute__((packed, aligned(4))) dt_f4u {
-    float x, y, z, w;
-};
 
 // ---- the dropout generator (host and device): lowbias32 mixing, a key per (seed, step, layer), one mix per element
 __host__ __device__ static inline uint32_t dt_mix32(uint32_t x) {
@@ -96,7 +92,7 @@ __global__ __launch_bounds__(256) void dt_gemm_kernel(GemmArgs a) {
         if (MODE != 2) {
             if (m_ok) {
                 if (k + 3 < kend) {
-                    const dt_f4u t = *reinterpret_cast<const dt_f4u*>(arow + k);
+                    const f4u t = *reinterpret_cast<const f4u*>(arow + k);
                     av[0] = t.x, av[1] = t.y, av[2] = t.z, av[3] = t.w;
                 } else {
 #pragma unroll
@@ -112,7 +108,7 @@ __global__ __launch_bounds__(256) void dt_gemm_kernel(GemmArgs a) {
         if (MODE == 1) {
             if (n_ok) {
                 if (k + 3 < kend) {
-                    const dt_f4u t = *reinterpret_cast<const dt_f4u*>(brow + k);
+                    const f4u t = *reinterpret_cast<const f4u*>(brow + k);
                     bv[0] = t.x, bv[1] = t.y, bv[2] = t.z, bv[3] = t.w;
                 } else {
 #pragma unroll
@@ -286,17 +282,13 @@ static int dt_gemm(const GemmArgs& a, hipStream_t s) {
 
 }  // namespace ssp
 
-struct ssp_dnn_trainer {
-    ssp_ctx* ctx = nullptr;
-    int32_t L = 0, max_batch = 0;
+struct ssp_dnn_trainer : ssp::TrainerCore {
+    int32_t L = 0;
     std::vector<int32_t> dims, relu, has_bias;
     std::vector<float> rate, scale;
     std::vector<uint32_t> thr;
     std::vector<int64_t> woff, boff, aoff;  // layer l's kernel / bias in the flat buffers; its output in `act` / `dz`
-    int64_t n_params = 0, t = 0;
-    ssp::DevBuf P, G, Mo, Vo;               // parameters, last step's gradients, Adam's moments: one flat buffer each
     ssp::DevBuf act, dz;                    // every layer's output and the gradient at it (the last layer's lives in act: in place)
-    ssp::DevBuf rowloss, rowcorr, ticket, slot_loss, slot_corr, order;
 };
 
 using namespace ssp;
@@ -331,23 +323,6 @@ int dt_forward(ssp_dnn_trainer* tr, const float* X, const int64_t* idx, int64_t 
     return SSP_OK;
 }
 
-int dt_loss(ssp_dnn_trainer* tr, const int32_t* labels, const int64_t* idx, int64_t row0, int Bn, bool grad, int64_t slot, hipStream_t s) {
-    LossArgs a{};
-    a.Z = dt_act(tr, tr->L - 1);
-    a.labels = idx ? labels : labels + row0;
-    a.idx = idx ? idx + row0 : nullptr;
-    a.B = Bn, a.C = tr->dims[tr->L], a.write_grad = grad ? 1 : 0;
-    a.inv_B = 1.f / (float)Bn;
-    a.rowloss = tr->rowloss.as<float>();
-    a.rowcorr = tr->rowcorr.as<int32_t>();
-    a.ticket = tr->ticket.as<uint32_t>();
-    a.loss_slot = tr->slot_loss.as<float>() + slot;
-    a.corr_slot = tr->slot_corr.as<int32_t>() + slot;
-    hipLaunchKernelGGL(dt_loss_kernel, dim3((unsigned)((Bn + 3) / 4)), dim3(256), 0, s, a);
-    SSP_HIP(hipGetLastError());
-    return SSP_OK;
-}
-
 int dt_backward(ssp_dnn_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, uint64_t seed, int64_t step, hipStream_t s) {
     for (int l = tr->L - 1; l >= 0; --l) {
         GemmArgs w{};
@@ -377,39 +352,6 @@ int dt_backward(ssp_dnn_trainer* tr, const float* X, const int64_t* idx, int64_t
         x.scale = tr->scale[l - 1];
         SSP_TRY(dt_gemm<1>(x, s));
     }
-    return SSP_OK;
-}
-
-int dt_slots(ssp_dnn_trainer* tr, int64_t n) {
-    SSP_TRY(tr->slot_loss.reserve((size_t)n * sizeof(float)));
-    SSP_TRY(tr->slot_corr.reserve((size_t)n * sizeof(int32_t)));
-    return SSP_OK;
-}
-
-// the per-step sums back to the host, once, and added in float64 in step order
-int dt_collect(ssp_dnn_trainer* tr, int64_t n, double* loss_sum, int64_t* n_correct, hipStream_t s) {
-    std::vector<float> hl((size_t)n);
-    std::vector<int32_t> hc((size_t)n);
-    SSP_HIP(hipMemcpyAsync(hl.data(), tr->slot_loss.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipMemcpyAsync(hc.data(), tr->slot_corr.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipStreamSynchronize(s));
-    double ls = 0.0;
-    int64_t nc = 0;
-    for (int64_t i = 0; i < n; ++i) ls += (double)hl[(size_t)i], nc += hc[(size_t)i];
-    if (loss_sum) *loss_sum = ls;
-    if (n_correct) *n_correct = nc;
-    return SSP_OK;
-}
-
-int dt_check_data(const char* who, const ssp_dnn_trainer* tr, const float* X, const int32_t* labels, int64_t N, int where) {
-    if (!tr) SSP_FAIL(SSP_ERR_INVALID, "%s: null handle", who);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", who);
-    if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "%s: N < 0", who);
-    if (N > 0 && (!X || !labels)) SSP_FAIL(SSP_ERR_INVALID, "%s: null array", who);
-    if (where == SSP_HOST)
-        for (int64_t r = 0; r < N; ++r)
-            if (labels[r] < 0 || labels[r] >= tr->dims[tr->L])
-                SSP_FAIL(SSP_ERR_INVALID, "%s: label %d of row %lld lies outside [0, %d)", who, labels[r], (long long)r, tr->dims[tr->L]);
     return SSP_OK;
 }
 
@@ -452,6 +394,7 @@ int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, 
     tr->ctx = ctx;
     tr->L = n_layers;
     tr->max_batch = max_batch;
+    tr->n_class = dims[n_layers];
     int64_t np = 0, na = 0;
     for (int l = 0; l < n_layers; ++l) {
         tr->relu.push_back(relu[l] ? 1 : 0);
@@ -467,31 +410,15 @@ int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, 
         na += (int64_t)max_batch * dims[l + 1];
     }
     tr->dims.assign(dims, dims + n_layers + 1);
-    tr->n_params = np;
     std::vector<float> flat((size_t)np, 0.f);
     for (int l = 0; l < n_layers; ++l) {
         memcpy(flat.data() + tr->woff[l], W[l], (size_t)dims[l] * dims[l + 1] * sizeof(float));
         if (tr->has_bias[l]) memcpy(flat.data() + tr->boff[l], bias[l], (size_t)dims[l + 1] * sizeof(float));
     }
-    hipStream_t s = ctx->stream;
-    const size_t pb = (size_t)np * sizeof(float);
-    int rc = tr->P.alloc(pb);
-    if (rc == SSP_OK) rc = tr->G.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Mo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Vo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->act.alloc((size_t)na * sizeof(float));
+    int rc = tr->act.alloc((size_t)na * sizeof(float));
     if (rc == SSP_OK) rc = tr->dz.alloc((size_t)na * sizeof(float));
-    if (rc == SSP_OK) rc = tr->rowloss.alloc((size_t)max_batch * sizeof(float));
-    if (rc == SSP_OK) rc = tr->rowcorr.alloc((size_t)max_batch * sizeof(int32_t));
-    if (rc == SSP_OK) rc = tr->ticket.alloc(sizeof(uint32_t));
-    if (rc == SSP_OK) rc = dt_slots(tr, 4096);  // (an epoch of up to 4096 steps allocates nothing)
-    if (rc == SSP_OK &&
-        (hipMemcpyAsync(tr->P.p, flat.data(), pb, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(tr->G.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->Mo.p, 0, pb, s) != hipSuccess || hipMemsetAsync(tr->Vo.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->ticket.p, 0, sizeof(uint32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
-        set_error("ssp_dnn_trainer_create: upload failed");
-        rc = SSP_ERR_HIP;
-    }
+    if (rc == SSP_OK) rc = tr->alloc_state("ssp_dnn_trainer_create", flat);
+    if (rc == SSP_OK) rc = tr->wait_state("ssp_dnn_trainer_create");
     if (rc != SSP_OK) {
         delete tr;
         return rc;
@@ -500,96 +427,29 @@ int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, 
     return SSP_OK;
 }
 
-int ssp_dnn_trainer_destroy(ssp_dnn_trainer* trainer) {
-    if (!trainer) return SSP_OK;
-    ssp::quiesce_ctx(trainer->ctx);
-    delete trainer;
-    return SSP_OK;
-}
+int ssp_dnn_trainer_destroy(ssp_dnn_trainer* trainer) { return trainer_destroy(trainer); }
 
 int ssp_dnn_trainer_epoch(ssp_dnn_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                           float lr, uint64_t seed, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_dnn_trainer_epoch");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(dt_check_data("ssp_dnn_trainer_epoch", trainer, X, labels, N, where));
     ssp_dnn_trainer* tr = trainer;
-    if (batch_size < 1 || batch_size > tr->max_batch)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_epoch: batch_size %d outside [1, %d]", batch_size, tr->max_batch);
-    if (!(lr >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_epoch: lr");
-    if (order)
-        for (int64_t r = 0; r < N; ++r)
-            if (order[r] < 0 || order[r] >= N) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_epoch: order[%lld] lies outside [0, N)", (long long)r);
-    if (N == 0) return SSP_OK;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + batch_size - 1) / batch_size;
-    SSP_TRY(dt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->dims[0] * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    const int64_t* dO = nullptr;
-    if (order) {
-        SSP_TRY(tr->order.reserve((size_t)N * sizeof(int64_t)));
-        SSP_HIP(hipMemcpyAsync(tr->order.p, order, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        dO = tr->order.as<int64_t>();
-    }
-    const double b1 = 0.9, b2 = 0.999;
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * batch_size;
-        const int Bn = (int)(N - row0 < batch_size ? N - row0 : batch_size);
-        const int64_t step = tr->t;  // the dropout counter: steps taken before this one, over the whole fit
-        SSP_TRY(dt_forward(tr, dX, dO, row0, Bn, true, seed, step, s));
-        SSP_TRY(dt_loss(tr, dL, dO, row0, Bn, true, st, s));
-        SSP_TRY(dt_backward(tr, dX, dO, row0, Bn, seed, step, s));
-        const double t1 = (double)(step + 1);
-        const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, t1)) / (1.0 - std::pow(b1, t1)));
-        hipLaunchKernelGGL(dt_adam_kernel, dim3((unsigned)((tr->n_params + 255) / 256)), dim3(256), 0, s, tr->P.as<float>(), tr->G.as<float>(),
-                           tr->Mo.as<float>(), tr->Vo.as<float>(), tr->n_params, lr_t, (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), 1e-7f);
-        SSP_HIP(hipGetLastError());
-        ++tr->t;  // (per queued step: a call that fails half way leaves t in step with the weights it has already moved)
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return dt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_epoch("ssp_dnn_trainer_epoch", tr, X, tr ? tr->dims[0] : 0, labels, N, order, batch_size, lr, loss_sum, n_correct, where, kernel_ms,
+                         [&](const float* dX, const int32_t* dL, const int64_t* dO, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                             const int64_t step = tr->t;  // the dropout counter: steps taken before this one, over the whole fit
+                             SSP_TRY(dt_forward(tr, dX, dO, row0, Bn, true, seed, step, s));
+                             SSP_TRY(tr->loss(dL, dO, row0, Bn, true, slot, dt_act(tr, tr->L - 1), s));
+                             SSP_TRY(dt_backward(tr, dX, dO, row0, Bn, seed, step, s));
+                             return tr->adam(lr, s);
+                         });
 }
 
 int ssp_dnn_trainer_evaluate(ssp_dnn_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
                              int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_dnn_trainer_evaluate");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(dt_check_data("ssp_dnn_trainer_evaluate", trainer, X, labels, N, where));
-    if (N == 0) return SSP_OK;
     ssp_dnn_trainer* tr = trainer;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + tr->max_batch - 1) / tr->max_batch;
-    SSP_TRY(dt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->dims[0] * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * tr->max_batch;
-        const int Bn = (int)(N - row0 < tr->max_batch ? N - row0 : tr->max_batch);
-        SSP_TRY(dt_forward(tr, dX, nullptr, row0, Bn, false, 0, 0, s));
-        SSP_TRY(dt_loss(tr, dL, nullptr, row0, Bn, false, st, s));
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return dt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_evaluate("ssp_dnn_trainer_evaluate", tr, X, tr ? tr->dims[0] : 0, labels, N, loss_sum, n_correct, where, kernel_ms,
+                            [&](const float* dX, const int32_t* dL, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                                SSP_TRY(dt_forward(tr, dX, nullptr, row0, Bn, false, 0, 0, s));
+                                return tr->loss(dL, nullptr, row0, Bn, false, slot, dt_act(tr, tr->L - 1), s);
+                            });
 }
 
 int ssp_dnn_trainer_read(ssp_dnn_trainer* trainer, int32_t what, int32_t layer, float* out) {
@@ -599,25 +459,15 @@ int ssp_dnn_trainer_read(ssp_dnn_trainer* trainer, int32_t what, int32_t layer, 
     if (what < 0 || what > 7) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_read: what must be SSP_DNN_W .. SSP_DNN_V_B");
     const bool is_bias = (what & 1) != 0;
     if (is_bias && !tr->has_bias[layer]) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_read: layer %d has no bias", layer);
-    const DevBuf& buf = what < 2 ? tr->P : what < 4 ? tr->G : what < 6 ? tr->Mo : tr->Vo;
-    const int64_t off = is_bias ? tr->boff[layer] : tr->woff[layer];
-    const size_t n = is_bias ? (size_t)tr->dims[layer + 1] : (size_t)tr->dims[layer] * tr->dims[layer + 1];
-    SSP_TRY(use_ctx(tr->ctx));
-    SSP_HIP(hipMemcpyAsync(out, buf.as<float>() + off, n * sizeof(float), hipMemcpyDeviceToHost, tr->ctx->stream));
-    SSP_HIP(hipStreamSynchronize(tr->ctx->stream));
-    return SSP_OK;
+    const int64_t n = is_bias ? (int64_t)tr->dims[layer + 1] : (int64_t)tr->dims[layer] * tr->dims[layer + 1];
+    return tr->read_flat("ssp_dnn_trainer_read", what >> 1, is_bias ? tr->boff[layer] : tr->woff[layer], n, out);
 }
 
-int ssp_dnn_trainer_steps(const ssp_dnn_trainer* trainer, int64_t* t) {
-    if (!trainer || !t) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_steps: null argument");
-    *t = trainer->t;
-    return SSP_OK;
-}
+int ssp_dnn_trainer_steps(const ssp_dnn_trainer* trainer, int64_t* t) { return trainer_steps("ssp_dnn_trainer_steps", trainer, t); }
 
 }  // extern "C"
 
-// ---- the step kernels as plain launches for the other trainers (dnn_train.hpp)
-#include "dnn_train.hpp"
+// ---- the step kernels as plain launches (dnn_train.hpp): what every trainer, this one included, queues them through
 
 namespace ssp {
 

@@ -1,7 +1,7 @@
-// The dense trainer's step kernels (dnn_train.hip: dt_gemm_kernel modes 0 / 1 / 2, dt_loss_kernel, dt_adam_kernel) as plain launches for the
-// other trainers of the library (lstm_train.hip: the Dense head, the loss, the weight gradients over the stash, Adam).  The kernels and
-// their arithmetic live in dnn_train.hip; these only fill the argument blocks.  Every pointer is a device pointer, every launch goes on
-// `s` without a host wait.
+// The dense trainer's step kernels (dnn_train.hip: dt_gemm_kernel modes 0 / 1 / 2, dt_loss_kernel, dt_adam_kernel) as plain launches.  Every
+// trainer queues its loss and its Adam update through them (trainer_core.hpp), the dense trainer included; the recurrent trainers also
+// run their Dense heads and their weight gradients over the stash on the GEMM.  The kernels and their arithmetic live in dnn_train.hip;
+// these only fill the argument blocks.  Every pointer is a device pointer, every launch goes on `s` without a host wait.
 #pragma once
 #include <hip/hip_runtime.h>
 

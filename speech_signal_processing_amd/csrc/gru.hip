@@ -22,10 +22,9 @@
 #include <vector>
 
 #include "common.hpp"
+#include "nn_device.hpp"
 
 namespace ssp {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int GRU_MAXH = 1024;   // widest state
 constexpr int GRU_MAXD = 4096;   // widest input
@@ -43,15 +42,6 @@ struct GruStepArgs {
     int64_t N, ld_src, ld_seq, ld_p;
     int32_t H;
 };
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float sigm(float z) { return __builtin_amdgcn_rcpf(1.f + ex2(-1.44269504088896341f * z)); }
-__device__ __forceinline__ float tanh_hw(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + ex2(2.88539008177792681f * z)); }
-__device__ __forceinline__ float hard_sigm(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
-template <int ACT>
-__device__ __forceinline__ float gate(float z) {
-    return ACT == 0 ? hard_sigm(z) : sigm(z);
-}
 
 // MODE 0: reset_after = 1, all three gates, one launch per step
 // MODE 1: reset_after = 0, first launch: z and r; leaves z and r . h_{t-1} in the workspace

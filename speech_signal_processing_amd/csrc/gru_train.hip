@@ -30,11 +30,10 @@
 #include <vector>
 
 #include "common.hpp"
-#include "dnn_train.hpp"
+#include "nn_device.hpp"
+#include "trainer_core.hpp"
 
 namespace ssp {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int GT_MAXH = 1024, GT_MAXD = 4096, GT_MAXK = 7, GT_MAXF = 256, GT_MAXT = 1024, GT_MAXB = 1024, GT_MAXC = 4096, GT_MAXE = 4096;
 constexpr int GT_MAXL = 4;
@@ -45,20 +44,6 @@ constexpr int GT_CCH = 64;                    // chunks of output positions in t
 constexpr size_t GT_WS_CAP = (size_t)4 << 30; // workspace cap, bytes
 constexpr float GT_LAMBDA = 0.01f;            // regularizers.l2()'s default factor
 constexpr float GT_EPS = 1e-12f;              // K.l2_normalize's epsilon
-
-__device__ __forceinline__ float gt_ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float gt_sigm(float z) { return __builtin_amdgcn_rcpf(1.f + gt_ex2(-1.44269504088896341f * z)); }
-__device__ __forceinline__ float gt_tanh(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + gt_ex2(2.88539008177792681f * z)); }
-__device__ __forceinline__ float gt_hard_sigm(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
-template <int ACT>
-__device__ __forceinline__ float gt_gate(float z) {
-    return ACT == 0 ? gt_hard_sigm(z) : gt_sigm(z);
-}
-// s' from the fp32 activation: Keras' clip passes no gradient at or beyond the bounds
-template <int ACT>
-__device__ __forceinline__ float gt_dgate(float s) {
-    return ACT == 0 ? ((s > 0.f && s < 1.f) ? 0.2f : 0.f) : s * (1.f - s);
-}
 
 // acc[q] += sum over g < KG of A_q(g) B(g): lane (kq, i) holds A_q[i][16 g + 4 kq + r] at ap[q] + g astride and B[16 g + 4 kq + r][n] at
 // bp + 16 g, r = 0..3 one 16-byte load each.  k ascends in one accumulator per gate.  Two register sets: the loads of group g + 1 are
@@ -136,8 +121,8 @@ __global__ __launch_bounds__(256) void gt_fwd_kernel(GtFwdArgs a) {
         f32x4 z, rg, rh;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            z[r] = gt_gate<ACT>(xz[r] + acc[0][r]);
-            rg[r] = gt_gate<ACT>(xr[r] + acc[NG - 1][r]);
+            z[r] = gate<ACT>(xz[r] + acc[0][r]);
+            rg[r] = gate<ACT>(xr[r] + acc[NG - 1][r]);
             rh[r] = rg[r] * hp[r];
         }
         *reinterpret_cast<f32x4*>(a.Z + o) = z;
@@ -149,7 +134,7 @@ __global__ __launch_bounds__(256) void gt_fwd_kernel(GtFwdArgs a) {
         f32x4 hh, out;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            hh[r] = gt_tanh(xh[r] + acc[0][r]);
+            hh[r] = tanh_hw(xh[r] + acc[0][r]);
             out[r] = z[r] * hp[r] + (1.f - z[r]) * hh[r];
         }
         *reinterpret_cast<f32x4*>(a.HH + o) = hh;
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(256) void gt_bwd_r_kernel(GtBwdArgs a) {
         f32x4 gr;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            dr[r] = acc[0][r] * hp[r] * gt_dgate<ACT>(rg[r]);
+            dr[r] = acc[0][r] * hp[r] * dgate<ACT>(rg[r]);
             gr[r] = acc[0][r] * rg[r];
         }
         *reinterpret_cast<f32x4*>(a.GR + o) = gr;
@@ -238,7 +223,7 @@ __global__ __launch_bounds__(256) void gt_bwd_h_kernel(GtBwdArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         dc[r] = dh[r] * (1.f - z[r]) * (1.f - hh[r] * hh[r]);
-        dz[r] = dh[r] * (hp[r] - hh[r]) * gt_dgate<ACT>(z[r]);
+        dz[r] = dh[r] * (hp[r] - hh[r]) * dgate<ACT>(z[r]);
     }
     float* da = a.dA + (size_t)seq * 3 * H + u;
     *reinterpret_cast<f32x4*>(da) = dz;
@@ -447,20 +432,16 @@ __global__ __launch_bounds__(256) void gt_l2_bwd_kernel(const float* __restrict_
 
 }  // namespace ssp
 
-struct ssp_gru_trainer {
-    ssp_ctx* ctx = nullptr;
+struct ssp_gru_trainer : ssp::TrainerCore {
     int32_t T = 0, D = 0, kh = 0, kw = 0, F = 0, sh = 0, sw = 0, To = 0, Do = 0, pt = 0, pl = 0, d0 = 0;
-    int32_t L = 0, H[ssp::GT_MAXL] = {}, E = 0, C = 0, act = 0, max_batch = 0, Hmax = 0;
+    int32_t L = 0, H[ssp::GT_MAXL] = {}, E = 0, act = 0, Hmax = 0;
     bool has[ssp::GT_TENSORS] = {};
     int64_t off[ssp::GT_TENSORS] = {}, len[ssp::GT_TENSORS] = {};
-    int64_t n_params = 0, t = 0;
-    ssp::DevBuf P, G, Mo, Vo;                   // parameters, last step's gradients, Adam's moments: one flat buffer each
     ssp::DevBuf img[ssp::GT_MAXL];              // packed U per layer (forward)
     ssp::DevBuf X0, proj;                       // conv output [To Bn x d0]; the running layer's projection [To Bn x 3H]
     ssp::DevBuf Hs[ssp::GT_MAXL], Zs[ssp::GT_MAXL], Rs[ssp::GT_MAXL], HHs[ssp::GT_MAXL], RHs[ssp::GT_MAXL];  // the stash, [To Bn x H] each
     ssp::DevBuf dA, Dx, GR, DH;                 // [To Bn x 3H]; the gradient at a layer's input [To Bn x max(H, d0)]; [Bn x H] each
     ssp::DevBuf mean, e1, l2s, y, dy, de, dmean, dMT, logits, cpart;
-    ssp::DevBuf rowloss, rowcorr, ticket, slot_loss, slot_corr, order;
 };
 
 using namespace ssp;
@@ -477,58 +458,6 @@ float* gt_g(ssp_gru_trainer* tr, int tensor) { return tr->G.as<float>() + tr->of
 const float* gt_pb(ssp_gru_trainer* tr, int tensor) { return tr->has[tensor] ? gt_p(tr, tensor) : nullptr; }
 float* gt_gb(ssp_gru_trainer* tr, int tensor) { return tr->has[tensor] ? gt_g(tr, tensor) : nullptr; }
 int gt_din(const ssp_gru_trainer* tr, int l) { return l ? tr->H[l - 1] : tr->d0; }
-
-// hipEvents between the launch kinds of one step (ssp_gru_trainer_step_times): the time since the mark before goes to `slot`
-struct GtMarks {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> slot;
-    ~GtMarks() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-int gt_mark(GtMarks* m, hipStream_t s, int slot) {
-    if (!m) return SSP_OK;
-    hipEvent_t e = nullptr;
-    SSP_HIP(hipEventCreate(&e));
-    m->ev.push_back(e);
-    m->slot.push_back(slot);
-    SSP_HIP(hipEventRecord(e, s));
-    return SSP_OK;
-}
-
-int gt_slots(ssp_gru_trainer* tr, int64_t n) {
-    SSP_TRY(tr->slot_loss.reserve((size_t)n * sizeof(float)));
-    SSP_TRY(tr->slot_corr.reserve((size_t)n * sizeof(int32_t)));
-    return SSP_OK;
-}
-
-// the per-step sums back to the host, once, and added in float64 in step order
-int gt_collect(ssp_gru_trainer* tr, int64_t n, double* loss_sum, int64_t* n_correct, hipStream_t s) {
-    std::vector<float> hl((size_t)n);
-    std::vector<int32_t> hc((size_t)n);
-    SSP_HIP(hipMemcpyAsync(hl.data(), tr->slot_loss.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipMemcpyAsync(hc.data(), tr->slot_corr.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipStreamSynchronize(s));
-    double ls = 0.0;
-    int64_t nc = 0;
-    for (int64_t i = 0; i < n; ++i) ls += (double)hl[(size_t)i], nc += hc[(size_t)i];
-    if (loss_sum) *loss_sum = ls;
-    if (n_correct) *n_correct = nc;
-    return SSP_OK;
-}
-
-int gt_check_data(const char* who, const ssp_gru_trainer* tr, const float* X, const int32_t* labels, int64_t N, int where) {
-    if (!tr) SSP_FAIL(SSP_ERR_INVALID, "%s: null handle", who);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", who);
-    if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "%s: N < 0", who);
-    if (N > 0 && (!X || !labels)) SSP_FAIL(SSP_ERR_INVALID, "%s: null array", who);
-    if (where == SSP_HOST)
-        for (int64_t r = 0; r < N; ++r)
-            if (labels[r] < 0 || labels[r] >= tr->C)
-                SSP_FAIL(SSP_ERR_INVALID, "%s: label %d of row %lld lies outside [0, %d)", who, labels[r], (long long)r, tr->C);
-    return SSP_OK;
-}
 
 GtConvArgs gt_conv_args(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn) {
     GtConvArgs a{};
@@ -552,19 +481,19 @@ int gt_launch(K kernel, dim3 grid, dim3 block, hipStream_t s, const A& a) {
 dim3 gt_grid(int H, int Bn) { return dim3((unsigned)((H + 63) / 64), (unsigned)((Bn + 15) / 16)); }
 
 // forward of rows [row0, row0 + Bn) (of idx when given) up to the logits, stashing what the backward needs
-int gt_forward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, hipStream_t s, GtMarks* mk = nullptr) {
+int gt_forward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, hipStream_t s, StepMarks* mk = nullptr) {
     const int To = tr->To;
     const int64_t rows = (int64_t)To * Bn;
     GtConvArgs c = gt_conv_args(tr, X, idx, row0, Bn);
     c.Y = tr->X0.as<float>();
     SSP_TRY(gt_launch(gt_conv_fwd_kernel, dim3((unsigned)((c.total + 255) / 256)), dim3(256), s, c));
-    SSP_TRY(gt_mark(mk, s, 0));
+    SSP_TRY(mark(mk, s, 0));
     for (int l = 0; l < tr->L; ++l) {
         const int H = tr->H[l], d_in = gt_din(tr, l);
         const float* in = l ? tr->Hs[l - 1].as<float>() : tr->X0.as<float>();
         float* P = tr->proj.as<float>();
         SSP_TRY(dt_launch_gemm(0, in, gt_p(tr, gt_w(l)), P, nullptr, (int32_t)rows, 3 * H, d_in, d_in, gt_pb(tr, gt_b(l)), nullptr, s));
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l));
+        SSP_TRY(mark(mk, s, 6 + 6 * l));
         GtFwdArgs a{};
         a.img = tr->img[l].as<float>();
         a.Bn = Bn, a.H = H;
@@ -578,7 +507,7 @@ int gt_forward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t 
             else SSP_TRY(gt_launch(gt_fwd_kernel<1, 0>, gt_grid(H, Bn), dim3(256), s, a));
             SSP_TRY(gt_launch(gt_fwd_kernel<2, 0>, gt_grid(H, Bn), dim3(256), s, a));
         }
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l + 1));
+        SSP_TRY(mark(mk, s, 6 + 6 * l + 1));
     }
     const int Hl = tr->H[tr->L - 1];
     hipLaunchKernelGGL(gt_mean_kernel, dim3((unsigned)((Bn * Hl + 255) / 256)), dim3(256), 0, s, tr->Hs[tr->L - 1].as<float>(), Bn, To, Hl,
@@ -587,15 +516,13 @@ int gt_forward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t 
     SSP_TRY(dt_launch_gemm(0, tr->mean.as<float>(), gt_p(tr, GT_DENSE_W), tr->e1.as<float>(), nullptr, Bn, tr->E, Hl, Hl, gt_pb(tr, GT_DENSE_B), nullptr, s));
     hipLaunchKernelGGL(gt_l2_kernel, dim3((unsigned)((Bn + 3) / 4)), dim3(256), 0, s, tr->e1.as<float>(), Bn, tr->E, tr->y.as<float>(), tr->l2s.as<float>());
     SSP_HIP(hipGetLastError());
-    SSP_TRY(dt_launch_gemm(0, tr->y.as<float>(), gt_p(tr, GT_HEAD_W), tr->logits.as<float>(), nullptr, Bn, tr->C, tr->E, tr->E, gt_pb(tr, GT_HEAD_B), nullptr, s));
-    return gt_mark(mk, s, 1);
+    SSP_TRY(dt_launch_gemm(0, tr->y.as<float>(), gt_p(tr, GT_HEAD_W), tr->logits.as<float>(), nullptr, Bn, tr->n_class, tr->E, tr->E, gt_pb(tr, GT_HEAD_B), nullptr, s));
+    return mark(mk, s, 1);
 }
 
 // cross-entropy of the batch into its slot, then the regulariser's Bn lambda sum K^2 on top
 int gt_loss(ssp_gru_trainer* tr, const int32_t* labels, const int64_t* idx, int64_t row0, int Bn, bool grad, int64_t slot, hipStream_t s) {
-    SSP_TRY(dt_launch_loss(tr->logits.as<float>(), idx ? labels : labels + row0, idx ? idx + row0 : nullptr, Bn, tr->C, grad ? 1 : 0,
-                           tr->rowloss.as<float>(), tr->rowcorr.as<int32_t>(), tr->ticket.as<uint32_t>(), tr->slot_loss.as<float>() + slot,
-                           tr->slot_corr.as<int32_t>() + slot, s));
+    SSP_TRY(tr->loss(labels, idx, row0, Bn, grad, slot, tr->logits.as<float>(), s));
     hipLaunchKernelGGL(gt_reg_kernel, dim3(1), dim3(256), 0, s, gt_p(tr, GT_CONV_K), (int32_t)tr->len[GT_CONV_K], (float)Bn * GT_LAMBDA,
                        tr->slot_loss.as<float>() + slot);
     SSP_HIP(hipGetLastError());
@@ -608,8 +535,8 @@ int gt_gemm_tn(const float* A, const float* B, float* C, int M, int N, int K, in
     return gt_launch(gt_gemm_tn_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)((M + 15) / 16)), dim3(256), s, g);
 }
 
-int gt_backward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, hipStream_t s, GtMarks* mk = nullptr) {
-    const int To = tr->To, E = tr->E, C = tr->C, Hl = tr->H[tr->L - 1];
+int gt_backward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, hipStream_t s, StepMarks* mk = nullptr) {
+    const int To = tr->To, E = tr->E, C = tr->n_class, Hl = tr->H[tr->L - 1];
     const int64_t rows = (int64_t)To * Bn;
     float* dlog = tr->logits.as<float>();
     // the head, the normalisation, Dense(E), the mean
@@ -622,7 +549,7 @@ int gt_backward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t
     SSP_TRY(dt_launch_gemm(1, tr->de.as<float>(), gt_p(tr, GT_DENSE_W), tr->dmean.as<float>(), nullptr, Bn, Hl, E, E, nullptr, nullptr, s));
     hipLaunchKernelGGL(gt_mean_bwd_kernel, dim3((unsigned)((Bn * Hl + 255) / 256)), dim3(256), 0, s, tr->dmean.as<float>(), Bn * Hl, To, tr->dMT.as<float>());
     SSP_HIP(hipGetLastError());
-    SSP_TRY(gt_mark(mk, s, 3));
+    SSP_TRY(mark(mk, s, 3));
     float* dA = tr->dA.as<float>();
     float* Dx = tr->Dx.as<float>();
     for (int l = tr->L - 1; l >= 0; --l) {
@@ -654,16 +581,16 @@ int gt_backward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t
             else SSP_TRY(gt_launch(gt_bwd_r_kernel<0>, gt_grid(H, Bn), dim3(256), s, b));
             if (t) SSP_TRY(finish(t - 1));
         }
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l + 2));
+        SSP_TRY(mark(mk, s, 6 + 6 * l + 2));
         const float* in = l ? tr->Hs[l - 1].as<float>() : tr->X0.as<float>();
         SSP_TRY(dt_launch_gemm(2, in, dA, gt_g(tr, gt_w(l)), nullptr, d_in, 3 * H, (int32_t)rows, d_in, nullptr, gt_gb(tr, gt_b(l)), s));
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l + 3));
+        SSP_TRY(mark(mk, s, 6 + 6 * l + 3));
         // dU_zr = h_{t-1}^T [da_z | da_r] over the rows of t >= 1 (h_{-1} = 0); dU_h = (r . h_{t-1})^T da_h (its rows of t = 0 are zero)
         SSP_TRY(gt_gemm_tn(tr->Hs[l].as<float>(), dA + 3 * bh, gt_g(tr, gt_u(l)), H, 2 * H, (To - 1) * Bn, H, 3 * H, 3 * H, s));
         SSP_TRY(gt_gemm_tn(tr->RHs[l].as<float>(), dA + 2 * H, gt_g(tr, gt_u(l)) + 2 * H, H, H, (int)rows, H, 3 * H, 3 * H, s));
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l + 4));
+        SSP_TRY(mark(mk, s, 6 + 6 * l + 4));
         SSP_TRY(dt_launch_gemm(1, dA, gt_p(tr, gt_w(l)), Dx, nullptr, (int32_t)rows, d_in, 3 * H, 3 * H, nullptr, nullptr, s));
-        SSP_TRY(gt_mark(mk, s, 6 + 6 * l + 5));
+        SSP_TRY(mark(mk, s, 6 + 6 * l + 5));
     }
     GtConvArgs c = gt_conv_args(tr, X, idx, row0, Bn);
     c.dY = Dx, c.part = tr->cpart.as<float>();
@@ -672,7 +599,7 @@ int gt_backward(ssp_gru_trainer* tr, const float* X, const int64_t* idx, int64_t
     hipLaunchKernelGGL(gt_conv_sum_kernel, dim3((unsigned)(((taps + 1) * tr->F + 255) / 256)), dim3(256), 0, s, tr->cpart.as<float>(), gt_p(tr, GT_CONV_K),
                        gt_g(tr, GT_CONV_K), gt_gb(tr, GT_CONV_B), taps, tr->F, 2.f * GT_LAMBDA);
     SSP_HIP(hipGetLastError());
-    return gt_mark(mk, s, 4);
+    return mark(mk, s, 4);
 }
 
 int gt_pack(ssp_gru_trainer* tr, hipStream_t s) {
@@ -686,16 +613,15 @@ int gt_pack(ssp_gru_trainer* tr, hipStream_t s) {
 
 // one training step on rows [row0, row0 + Bn) (of idx when given)
 int gt_step(ssp_gru_trainer* tr, const float* X, const int32_t* labels, const int64_t* idx, int64_t row0, int Bn, int64_t slot, float lr,
-            hipStream_t s, GtMarks* mk = nullptr) {
-    SSP_TRY(gt_mark(mk, s, -1));
+            hipStream_t s, StepMarks* mk = nullptr) {
+    SSP_TRY(mark(mk, s, -1));
     SSP_TRY(gt_forward(tr, X, idx, row0, Bn, s, mk));
     SSP_TRY(gt_loss(tr, labels, idx, row0, Bn, true, slot, s));
-    SSP_TRY(gt_mark(mk, s, 2));
+    SSP_TRY(mark(mk, s, 2));
     SSP_TRY(gt_backward(tr, X, idx, row0, Bn, s, mk));
-    SSP_TRY(dt_launch_adam(tr->P.as<float>(), tr->G.as<float>(), tr->Mo.as<float>(), tr->Vo.as<float>(), tr->n_params, lr, tr->t + 1, s));
-    ++tr->t;  // (per queued step: a call that fails half way leaves t in step with the weights it has already moved)
+    SSP_TRY(tr->adam(lr, s));
     SSP_TRY(gt_pack(tr, s));
-    return gt_mark(mk, s, 5);
+    return mark(mk, s, 5);
 }
 
 }  // namespace
@@ -752,7 +678,7 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
     tr->T = T, tr->D = D, tr->kh = kh, tr->kw = kw, tr->F = F, tr->sh = sh, tr->sw = sw, tr->To = To, tr->Do = Do, tr->d0 = (int32_t)d0;
     const int ph = (To - 1) * sh + kh - T, pw = (Do - 1) * sw + kw - D;  // TensorFlow's `same`: the smaller half goes in front
     tr->pt = (ph > 0 ? ph : 0) / 2, tr->pl = (pw > 0 ? pw : 0) / 2;
-    tr->L = n_gru, tr->E = E, tr->C = n_class, tr->act = recurrent_activation, tr->max_batch = max_batch, tr->Hmax = Hmax;
+    tr->L = n_gru, tr->E = E, tr->n_class = n_class, tr->act = recurrent_activation, tr->max_batch = max_batch, tr->Hmax = Hmax;
     const float* src[GT_TENSORS] = {};
     src[GT_CONV_K] = conv_K, tr->len[GT_CONV_K] = (int64_t)kh * kw * F;
     src[GT_CONV_B] = conv_b, tr->len[GT_CONV_B] = F;
@@ -773,18 +699,11 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
         tr->off[i] = np;
         np += (tr->len[i] + 3) / 4 * 4;  // (every tensor starts on 16 bytes: the step kernels read U with 16-byte loads; the padding stays zero)
     }
-    tr->n_params = np;
     std::vector<float> flat((size_t)np, 0.f);
     for (int i = 0; i < GT_TENSORS; ++i)
         if (src[i]) memcpy(flat.data() + tr->off[i], src[i], (size_t)tr->len[i] * sizeof(float));
-    hipStream_t s = ctx->stream;
-    const size_t pb = (size_t)np * sizeof(float), f4 = sizeof(float);
-    const size_t mb = (size_t)max_batch;
-    int rc = tr->P.alloc(pb);
-    if (rc == SSP_OK) rc = tr->G.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Mo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Vo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->X0.alloc(rows * d0 * f4);
+    const size_t f4 = sizeof(float), mb = (size_t)max_batch;
+    int rc = tr->X0.alloc(rows * d0 * f4);
     if (rc == SSP_OK) rc = tr->proj.alloc(rows * 3 * Hmax * f4);
     if (rc == SSP_OK) rc = tr->dA.alloc(rows * 3 * Hmax * f4);
     if (rc == SSP_OK) rc = tr->Dx.alloc(rows * wide * f4);
@@ -809,22 +728,9 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
     if (rc == SSP_OK) rc = tr->l2s.alloc(mb * f4);
     if (rc == SSP_OK) rc = tr->logits.alloc(mb * n_class * f4);
     if (rc == SSP_OK) rc = tr->cpart.alloc((size_t)(kh * kw + 1) * GT_CCH * F * f4);
-    if (rc == SSP_OK) rc = tr->rowloss.alloc(mb * sizeof(float));
-    if (rc == SSP_OK) rc = tr->rowcorr.alloc(mb * sizeof(int32_t));
-    if (rc == SSP_OK) rc = tr->ticket.alloc(sizeof(uint32_t));
-    if (rc == SSP_OK) rc = gt_slots(tr, 4096);  // (an epoch of up to 4096 steps allocates nothing)
-    if (rc == SSP_OK &&
-        (hipMemcpyAsync(tr->P.p, flat.data(), pb, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(tr->G.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->Mo.p, 0, pb, s) != hipSuccess || hipMemsetAsync(tr->Vo.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->ticket.p, 0, sizeof(uint32_t), s) != hipSuccess)) {
-        set_error("%s: upload failed", who);
-        rc = SSP_ERR_HIP;
-    }
-    if (rc == SSP_OK) rc = gt_pack(tr, s);
-    if (rc == SSP_OK && hipStreamSynchronize(s) != hipSuccess) {
-        set_error("%s: upload failed", who);
-        rc = SSP_ERR_HIP;
-    }
+    if (rc == SSP_OK) rc = tr->alloc_state(who, flat);
+    if (rc == SSP_OK) rc = gt_pack(tr, ctx->stream);  // (queued behind the upload: one host wait for both)
+    if (rc == SSP_OK) rc = tr->wait_state(who);
     if (rc != SSP_OK) {
         delete tr;
         return rc;
@@ -833,107 +739,34 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
     return SSP_OK;
 }
 
-int ssp_gru_trainer_destroy(ssp_gru_trainer* trainer) {
-    if (!trainer) return SSP_OK;
-    ssp::quiesce_ctx(trainer->ctx);
-    delete trainer;
-    return SSP_OK;
-}
+int ssp_gru_trainer_destroy(ssp_gru_trainer* trainer) { return trainer_destroy(trainer); }
 
 int ssp_gru_trainer_epoch(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                           float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_gru_trainer_epoch");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(gt_check_data("ssp_gru_trainer_epoch", trainer, X, labels, N, where));
     ssp_gru_trainer* tr = trainer;
-    if (batch_size < 1 || batch_size > tr->max_batch)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_epoch: batch_size %d outside [1, %d]", batch_size, tr->max_batch);
-    if (!(lr >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_epoch: lr");
-    if (order)
-        for (int64_t r = 0; r < N; ++r)
-            if (order[r] < 0 || order[r] >= N) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_epoch: order[%lld] lies outside [0, N)", (long long)r);
-    if (N == 0) return SSP_OK;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + batch_size - 1) / batch_size;
-    SSP_TRY(gt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->T * tr->D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    const int64_t* dO = nullptr;
-    if (order) {
-        SSP_TRY(tr->order.reserve((size_t)N * sizeof(int64_t)));
-        SSP_HIP(hipMemcpyAsync(tr->order.p, order, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        dO = tr->order.as<int64_t>();
-    }
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * batch_size;
-        const int Bn = (int)(N - row0 < batch_size ? N - row0 : batch_size);
-        SSP_TRY(gt_step(tr, dX, dL, dO, row0, Bn, st, lr, s));
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return gt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_epoch("ssp_gru_trainer_epoch", tr, X, tr ? (int64_t)tr->T * tr->D : 0, labels, N, order, batch_size, lr, loss_sum, n_correct, where,
+                         kernel_ms, [&](const float* dX, const int32_t* dL, const int64_t* dO, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                             return gt_step(tr, dX, dL, dO, row0, Bn, slot, lr, s);
+                         });
 }
 
 int ssp_gru_trainer_evaluate(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
                              int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_gru_trainer_evaluate");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(gt_check_data("ssp_gru_trainer_evaluate", trainer, X, labels, N, where));
-    if (N == 0) return SSP_OK;
     ssp_gru_trainer* tr = trainer;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + tr->max_batch - 1) / tr->max_batch;
-    SSP_TRY(gt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->T * tr->D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * tr->max_batch;
-        const int Bn = (int)(N - row0 < tr->max_batch ? N - row0 : tr->max_batch);
-        SSP_TRY(gt_forward(tr, dX, nullptr, row0, Bn, s));
-        SSP_TRY(gt_loss(tr, dL, nullptr, row0, Bn, false, st, s));
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return gt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_evaluate("ssp_gru_trainer_evaluate", tr, X, tr ? (int64_t)tr->T * tr->D : 0, labels, N, loss_sum, n_correct, where, kernel_ms,
+                            [&](const float* dX, const int32_t* dL, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                                SSP_TRY(gt_forward(tr, dX, nullptr, row0, Bn, s));
+                                return gt_loss(tr, dL, nullptr, row0, Bn, false, slot, s);
+                            });
 }
 
 int ssp_gru_trainer_step_times(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int32_t batch_size, float lr, float* ms_out) {
-    if (!ms_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_step_times: null output");
-    SSP_TRY(gt_check_data("ssp_gru_trainer_step_times", trainer, X, labels, batch_size, SSP_DEVICE));
+    const char* who = "ssp_gru_trainer_step_times";
     ssp_gru_trainer* tr = trainer;
-    if (batch_size < 1 || batch_size > tr->max_batch)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_step_times: batch_size %d outside [1, %d]", batch_size, tr->max_batch);
-    if (!(lr >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_step_times: lr");
-    SSP_TRY(use_ctx(tr->ctx));
-    hipStream_t s = tr->ctx->stream;
-    GtMarks mk;
-    SSP_TRY(gt_step(tr, X, labels, nullptr, 0, batch_size, 0, lr, s, &mk));
-    SSP_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < GT_TIMES; ++i) ms_out[i] = 0.f;
-    for (size_t i = 1; i < mk.ev.size(); ++i) {
-        float ms = 0.f;
-        SSP_HIP(hipEventElapsedTime(&ms, mk.ev[i - 1], mk.ev[i]));
-        if (mk.slot[i] >= 0 && mk.slot[i] < GT_TIMES) ms_out[mk.slot[i]] += ms;
-    }
-    return SSP_OK;
+    StepMarks mk;
+    SSP_TRY(trainer_timed_step(who, tr, X, labels, batch_size, lr, ms_out, mk,
+                               [&](hipStream_t s, StepMarks* m) { return gt_step(tr, X, labels, nullptr, 0, batch_size, 0, lr, s, m); }));
+    return mk.times(ms_out, GT_TIMES);
 }
 
 int ssp_gru_trainer_read(ssp_gru_trainer* trainer, int32_t what, int32_t tensor, float* out) {
@@ -942,17 +775,9 @@ int ssp_gru_trainer_read(ssp_gru_trainer* trainer, int32_t what, int32_t tensor,
     if (what < 0 || what > 3) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_read: what must be SSP_GRUT_PARAM .. SSP_GRUT_V");
     if (tensor < 0 || tensor >= GT_TENSORS || tr->len[tensor] == 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_read: the network has no tensor %d", tensor);
     if (!tr->has[tensor]) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_read: the network has no such bias");
-    const DevBuf& buf = what == 0 ? tr->P : what == 1 ? tr->G : what == 2 ? tr->Mo : tr->Vo;
-    SSP_TRY(use_ctx(tr->ctx));
-    SSP_HIP(hipMemcpyAsync(out, buf.as<float>() + tr->off[tensor], (size_t)tr->len[tensor] * sizeof(float), hipMemcpyDeviceToHost, tr->ctx->stream));
-    SSP_HIP(hipStreamSynchronize(tr->ctx->stream));
-    return SSP_OK;
+    return tr->read_flat("ssp_gru_trainer_read", what, tr->off[tensor], tr->len[tensor], out);
 }
 
-int ssp_gru_trainer_steps(const ssp_gru_trainer* trainer, int64_t* t) {
-    if (!trainer || !t) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_trainer_steps: null argument");
-    *t = trainer->t;
-    return SSP_OK;
-}
+int ssp_gru_trainer_steps(const ssp_gru_trainer* trainer, int64_t* t) { return trainer_steps("ssp_gru_trainer_steps", trainer, t); }
 
 }  // extern "C"

@@ -18,10 +18,10 @@
 #include <vector>
 
 #include "common.hpp"
+#include "nn_device.hpp"
 
 namespace ssp {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
@@ -36,15 +36,6 @@ struct LstmArgs {
     int64_t n_seq;
     int32_t D, dT, H;
 };
-
-struct __attribute__((packed, aligned(4))) f4u {
-    float x, y, z, w;
-};
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float sigm(float z) { return __builtin_amdgcn_rcpf(1.f + ex2(-1.44269504088896341f * z)); }
-__device__ __forceinline__ float tanh_hw(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + ex2(2.88539008177792681f * z)); }
-__device__ __forceinline__ float hard_sigm(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
 
 // HT = hidden tiles of 16 units (1, 2, 4, 8); ACT = 0 hard_sigmoid | 1 sigmoid
 template <int HT, int ACT>

@@ -23,18 +23,12 @@
 #include <vector>
 
 #include "common.hpp"
-#include "dnn_train.hpp"
+#include "nn_device.hpp"
+#include "trainer_core.hpp"
 
 namespace ssp {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 constexpr int LT_MAXH = 128, LT_MAXD = 64, LT_MAXT = 1024, LT_MAXB = 1024, LT_MAXC = 4096;
-
-__device__ __forceinline__ float lt_ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float lt_sigm(float z) { return __builtin_amdgcn_rcpf(1.f + lt_ex2(-1.44269504088896341f * z)); }
-__device__ __forceinline__ float lt_tanh(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + lt_ex2(2.88539008177792681f * z)); }
-__device__ __forceinline__ float lt_hard_sigm(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.f), 1.f); }
 
 struct LtFwdArgs {
     const float* X;      // [rows x T x D]
@@ -157,17 +151,17 @@ __global__ __launch_bounds__(64 * (KG - 1 < 8 ? KG - 1 : 8)) void lt_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (a.act == 0) {
-                gi[r] = lt_hard_sigm(acc[0][r]);
-                gf[r] = lt_hard_sigm(acc[1][r]);
-                go[r] = lt_hard_sigm(acc[3][r]);
+                gi[r] = hard_sigm(acc[0][r]);
+                gf[r] = hard_sigm(acc[1][r]);
+                go[r] = hard_sigm(acc[3][r]);
             } else {
-                gi[r] = lt_sigm(acc[0][r]);
-                gf[r] = lt_sigm(acc[1][r]);
-                go[r] = lt_sigm(acc[3][r]);
+                gi[r] = sigm(acc[0][r]);
+                gf[r] = sigm(acc[1][r]);
+                go[r] = sigm(acc[3][r]);
             }
-            gg[r] = lt_tanh(acc[2][r]);
+            gg[r] = tanh_hw(acc[2][r]);
             c[r] = gf[r] * c[r] + gi[r] * gg[r];
-            h[r] = go[r] * lt_tanh(c[r]);
+            h[r] = go[r] * tanh_hw(c[r]);
         }
         *reinterpret_cast<f32x4*>(&op[cur ^ 1][n][16 * dT + u0]) = h;
         store_x(t + 1, cur ^ 1, xn);
@@ -236,18 +230,18 @@ __global__ __launch_bounds__(64 * HT) void lt_bwd_kernel(LtBwdArgs a) {
         f32x4 zi, zf, zg, zo;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float tc = lt_tanh(ct[r]);
+            const float tc = tanh_hw(ct[r]);
             const float d_o = dh[r] * tc;
             const float d_c = dc[r] + dh[r] * go[r] * (1.f - tc * tc);
             float si, sf, so;
-            if (a.act == 0) {  // Keras' clip passes no gradient at or beyond the bounds
-                si = (gi[r] > 0.f && gi[r] < 1.f) ? 0.2f : 0.f;
-                sf = (gf[r] > 0.f && gf[r] < 1.f) ? 0.2f : 0.f;
-                so = (go[r] > 0.f && go[r] < 1.f) ? 0.2f : 0.f;
+            if (a.act == 0) {
+                si = dgate<0>(gi[r]);
+                sf = dgate<0>(gf[r]);
+                so = dgate<0>(go[r]);
             } else {
-                si = gi[r] * (1.f - gi[r]);
-                sf = gf[r] * (1.f - gf[r]);
-                so = go[r] * (1.f - go[r]);
+                si = dgate<1>(gi[r]);
+                sf = dgate<1>(gf[r]);
+                so = dgate<1>(go[r]);
             }
             zi[r] = d_c * gg[r] * si;
             zf[r] = d_c * cp[r] * sf;
@@ -331,16 +325,12 @@ static int lt_bwd(const LtBwdArgs& a, hipStream_t s) {
 
 }  // namespace ssp
 
-struct ssp_lstm_trainer {
-    ssp_ctx* ctx = nullptr;
-    int32_t D = 0, H = 0, C = 0, T = 0, act = 0, max_batch = 0;
+struct ssp_lstm_trainer : ssp::TrainerCore {
+    int32_t D = 0, H = 0, T = 0, act = 0;
     bool has_b = false, has_bd = false;
     int64_t off[5] = {0, 0, 0, 0, 0}, len[5] = {0, 0, 0, 0, 0};  // W U B WD BD in the flat buffers
-    int64_t n_params = 0, t = 0;
-    ssp::DevBuf P, G, Mo, Vo;          // parameters, last step's gradients, Adam's moments: one flat buffer each
     ssp::DevBuf Xs, Hs, Cs, Gs;        // the stash of one step, time-major
     ssp::DevBuf hlast, dH, logits;     // evaluate's last hidden state; the gradient at it; the logits and the gradient at them (in place)
-    ssp::DevBuf rowloss, rowcorr, ticket, slot_loss, slot_corr, order;
 };
 
 using namespace ssp;
@@ -349,59 +339,10 @@ namespace {
 
 float* lt_p(ssp_lstm_trainer* tr, const DevBuf& b, int tensor) { return b.as<float>() + tr->off[tensor]; }
 
-// hipEvents between the launches of one step (ssp_lstm_trainer_step_times); a null pointer marks nothing
-constexpr int LT_LAUNCHES = 9;
-struct LtMarks {
-    hipEvent_t ev[LT_LAUNCHES + 1] = {};
-    int n = 0;
-    ~LtMarks() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-int lt_mark(LtMarks* m, hipStream_t s) {
-    if (!m || m->n > LT_LAUNCHES) return SSP_OK;
-    SSP_HIP(hipEventCreate(&m->ev[m->n]));
-    SSP_HIP(hipEventRecord(m->ev[m->n], s));
-    ++m->n;
-    return SSP_OK;
-}
-
-int lt_slots(ssp_lstm_trainer* tr, int64_t n) {
-    SSP_TRY(tr->slot_loss.reserve((size_t)n * sizeof(float)));
-    SSP_TRY(tr->slot_corr.reserve((size_t)n * sizeof(int32_t)));
-    return SSP_OK;
-}
-
-// the per-step sums back to the host, once, and added in float64 in step order
-int lt_collect(ssp_lstm_trainer* tr, int64_t n, double* loss_sum, int64_t* n_correct, hipStream_t s) {
-    std::vector<float> hl((size_t)n);
-    std::vector<int32_t> hc((size_t)n);
-    SSP_HIP(hipMemcpyAsync(hl.data(), tr->slot_loss.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipMemcpyAsync(hc.data(), tr->slot_corr.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SSP_HIP(hipStreamSynchronize(s));
-    double ls = 0.0;
-    int64_t nc = 0;
-    for (int64_t i = 0; i < n; ++i) ls += (double)hl[(size_t)i], nc += hc[(size_t)i];
-    if (loss_sum) *loss_sum = ls;
-    if (n_correct) *n_correct = nc;
-    return SSP_OK;
-}
-
-int lt_check_data(const char* who, const ssp_lstm_trainer* tr, const float* X, const int32_t* labels, int64_t N, int where) {
-    if (!tr) SSP_FAIL(SSP_ERR_INVALID, "%s: null handle", who);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", who);
-    if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "%s: N < 0", who);
-    if (N > 0 && (!X || !labels)) SSP_FAIL(SSP_ERR_INVALID, "%s: null array", who);
-    if (where == SSP_HOST)
-        for (int64_t r = 0; r < N; ++r)
-            if (labels[r] < 0 || labels[r] >= tr->C)
-                SSP_FAIL(SSP_ERR_INVALID, "%s: label %d of row %lld lies outside [0, %d)", who, labels[r], (long long)r, tr->C);
-    return SSP_OK;
-}
+constexpr int LT_LAUNCHES = 9;  // of one step: the slots of ssp_lstm_trainer_step_times, in launch order
 
 // recurrent forward of rows [row0, row0 + Bn) (of idx when given), then the Dense head's logits
-int lt_forward(ssp_lstm_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, bool stash, hipStream_t s, LtMarks* mk = nullptr) {
+int lt_forward(ssp_lstm_trainer* tr, const float* X, const int64_t* idx, int64_t row0, int Bn, bool stash, hipStream_t s, StepMarks* mk = nullptr) {
     LtFwdArgs a{};
     a.X = idx ? X : X + row0 * tr->T * tr->D;
     a.idx = idx ? idx + row0 : nullptr;
@@ -410,54 +351,46 @@ int lt_forward(ssp_lstm_trainer* tr, const float* X, const int64_t* idx, int64_t
     a.hlast = tr->hlast.as<float>();
     a.Bn = Bn, a.T = tr->T, a.D = tr->D, a.dT = (tr->D + 15) / 16, a.H = tr->H, a.act = tr->act;
     SSP_TRY(stash ? lt_fwd<true>(a, s) : lt_fwd<false>(a, s));
-    SSP_TRY(lt_mark(mk, s));
+    SSP_TRY(mark(mk, s, 0));
     const float* hl = stash ? tr->Hs.as<float>() + (int64_t)(tr->T - 1) * Bn * tr->H : tr->hlast.as<float>();
-    return dt_launch_gemm(0, hl, lt_p(tr, tr->P, 3), tr->logits.as<float>(), nullptr, Bn, tr->C, tr->H, tr->H,
+    return dt_launch_gemm(0, hl, lt_p(tr, tr->P, 3), tr->logits.as<float>(), nullptr, Bn, tr->n_class, tr->H, tr->H,
                           tr->has_bd ? lt_p(tr, tr->P, 4) : nullptr, nullptr, s);
 }
 
-int lt_loss(ssp_lstm_trainer* tr, const int32_t* labels, const int64_t* idx, int64_t row0, int Bn, bool grad, int64_t slot, hipStream_t s) {
-    return dt_launch_loss(tr->logits.as<float>(), idx ? labels : labels + row0, idx ? idx + row0 : nullptr, Bn, tr->C, grad ? 1 : 0,
-                          tr->rowloss.as<float>(), tr->rowcorr.as<int32_t>(), tr->ticket.as<uint32_t>(), tr->slot_loss.as<float>() + slot,
-                          tr->slot_corr.as<int32_t>() + slot, s);
-}
-
-int lt_backward(ssp_lstm_trainer* tr, int Bn, hipStream_t s, LtMarks* mk = nullptr) {
+int lt_backward(ssp_lstm_trainer* tr, int Bn, hipStream_t s, StepMarks* mk = nullptr) {
     const int H = tr->H, H4 = 4 * tr->H, T = tr->T;
     const float* hl = tr->Hs.as<float>() + (int64_t)(T - 1) * Bn * H;
     float* dlog = tr->logits.as<float>();
     // the Dense head: dWd = h_T^T dlogits, dbd; dh_T = dlogits Wd^T
-    SSP_TRY(dt_launch_gemm(2, hl, dlog, lt_p(tr, tr->G, 3), nullptr, H, tr->C, Bn, H, nullptr, tr->has_bd ? lt_p(tr, tr->G, 4) : nullptr, s));
-    SSP_TRY(lt_mark(mk, s));
-    SSP_TRY(dt_launch_gemm(1, dlog, lt_p(tr, tr->P, 3), tr->dH.as<float>(), nullptr, Bn, H, tr->C, tr->C, nullptr, nullptr, s));
-    SSP_TRY(lt_mark(mk, s));
+    SSP_TRY(dt_launch_gemm(2, hl, dlog, lt_p(tr, tr->G, 3), nullptr, H, tr->n_class, Bn, H, nullptr, tr->has_bd ? lt_p(tr, tr->G, 4) : nullptr, s));
+    SSP_TRY(mark(mk, s, 3));
+    SSP_TRY(dt_launch_gemm(1, dlog, lt_p(tr, tr->P, 3), tr->dH.as<float>(), nullptr, Bn, H, tr->n_class, tr->n_class, nullptr, nullptr, s));
+    SSP_TRY(mark(mk, s, 4));
     LtBwdArgs b{};
     b.U = lt_p(tr, tr->P, 1), b.dH = tr->dH.as<float>(), b.Gs = tr->Gs.as<float>(), b.Cs = tr->Cs.as<float>();
     b.Bn = Bn, b.T = T, b.H = H, b.act = tr->act;
     SSP_TRY(lt_bwd(b, s));
-    SSP_TRY(lt_mark(mk, s));
+    SSP_TRY(mark(mk, s, 5));
     // dW = Xs^T dZ and db over the T Bn rows; dU = H_prev^T dZ over the rows of t >= 1 (h_{-1} = 0)
     const float* dZ = tr->Gs.as<float>();
     SSP_TRY(dt_launch_gemm(2, tr->Xs.as<float>(), dZ, lt_p(tr, tr->G, 0), nullptr, tr->D, H4, T * Bn, tr->D, nullptr,
                            tr->has_b ? lt_p(tr, tr->G, 2) : nullptr, s));
-    SSP_TRY(lt_mark(mk, s));
+    SSP_TRY(mark(mk, s, 6));
     SSP_TRY(dt_launch_gemm(2, tr->Hs.as<float>(), dZ + (int64_t)Bn * H4, lt_p(tr, tr->G, 1), nullptr, H, H4, (T - 1) * Bn, H, nullptr, nullptr, s));
-    return lt_mark(mk, s);
+    return mark(mk, s, 7);
 }
 
 // one training step on rows [row0, row0 + Bn) (of idx when given): nine launches
 int lt_step(ssp_lstm_trainer* tr, const float* X, const int32_t* labels, const int64_t* idx, int64_t row0, int Bn, int64_t slot, float lr,
-            hipStream_t s, LtMarks* mk = nullptr) {
-    SSP_TRY(lt_mark(mk, s));
+            hipStream_t s, StepMarks* mk = nullptr) {
+    SSP_TRY(mark(mk, s, -1));
     SSP_TRY(lt_forward(tr, X, idx, row0, Bn, true, s, mk));
-    SSP_TRY(lt_mark(mk, s));
-    SSP_TRY(lt_loss(tr, labels, idx, row0, Bn, true, slot, s));
-    SSP_TRY(lt_mark(mk, s));
+    SSP_TRY(mark(mk, s, 1));
+    SSP_TRY(tr->loss(labels, idx, row0, Bn, true, slot, tr->logits.as<float>(), s));
+    SSP_TRY(mark(mk, s, 2));
     SSP_TRY(lt_backward(tr, Bn, s, mk));
-    SSP_TRY(dt_launch_adam(tr->P.as<float>(), tr->G.as<float>(), tr->Mo.as<float>(), tr->Vo.as<float>(), tr->n_params, lr, tr->t + 1, s));
-    SSP_TRY(lt_mark(mk, s));
-    ++tr->t;  // (per queued step: a call that fails half way leaves t in step with the weights it has already moved)
-    return SSP_OK;
+    SSP_TRY(tr->adam(lr, s));
+    return mark(mk, s, 8);
 }
 
 }  // namespace
@@ -482,42 +415,26 @@ int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n
     ssp_lstm_trainer* tr = new (std::nothrow) ssp_lstm_trainer;
     if (!tr) SSP_FAIL(SSP_ERR_NOMEM, "lstm trainer: host alloc");
     tr->ctx = ctx;
-    tr->D = d_in, tr->H = units, tr->C = n_class, tr->T = T, tr->act = recurrent_activation, tr->max_batch = max_batch;
+    tr->D = d_in, tr->H = units, tr->n_class = n_class, tr->T = T, tr->act = recurrent_activation, tr->max_batch = max_batch;
     tr->has_b = bias != nullptr, tr->has_bd = bd != nullptr;
     const int64_t H4 = 4 * (int64_t)units;
     tr->len[0] = d_in * H4, tr->len[1] = units * H4, tr->len[2] = H4, tr->len[3] = (int64_t)units * n_class, tr->len[4] = n_class;
     int64_t np = 0;
     for (int i = 0; i < 5; ++i) tr->off[i] = np, np += tr->len[i];
-    tr->n_params = np;
     std::vector<float> flat((size_t)np, 0.f);
     const float* src[5] = {W, U, bias, Wd, bd};
     for (int i = 0; i < 5; ++i)
         if (src[i]) memcpy(flat.data() + tr->off[i], src[i], (size_t)tr->len[i] * sizeof(float));
-    hipStream_t s = ctx->stream;
-    const size_t pb = (size_t)np * sizeof(float);
     const size_t rows = (size_t)T * max_batch;
-    int rc = tr->P.alloc(pb);
-    if (rc == SSP_OK) rc = tr->G.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Mo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Vo.alloc(pb);
-    if (rc == SSP_OK) rc = tr->Xs.alloc(rows * d_in * sizeof(float));
+    int rc = tr->Xs.alloc(rows * d_in * sizeof(float));
     if (rc == SSP_OK) rc = tr->Hs.alloc(rows * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->Cs.alloc(rows * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->Gs.alloc(rows * H4 * sizeof(float));
     if (rc == SSP_OK) rc = tr->hlast.alloc((size_t)max_batch * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->dH.alloc((size_t)max_batch * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->logits.alloc((size_t)max_batch * n_class * sizeof(float));
-    if (rc == SSP_OK) rc = tr->rowloss.alloc((size_t)max_batch * sizeof(float));
-    if (rc == SSP_OK) rc = tr->rowcorr.alloc((size_t)max_batch * sizeof(int32_t));
-    if (rc == SSP_OK) rc = tr->ticket.alloc(sizeof(uint32_t));
-    if (rc == SSP_OK) rc = lt_slots(tr, 4096);  // (an epoch of up to 4096 steps allocates nothing)
-    if (rc == SSP_OK &&
-        (hipMemcpyAsync(tr->P.p, flat.data(), pb, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(tr->G.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->Mo.p, 0, pb, s) != hipSuccess || hipMemsetAsync(tr->Vo.p, 0, pb, s) != hipSuccess ||
-         hipMemsetAsync(tr->ticket.p, 0, sizeof(uint32_t), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
-        set_error("ssp_lstm_trainer_create: upload failed");
-        rc = SSP_ERR_HIP;
-    }
+    if (rc == SSP_OK) rc = tr->alloc_state("ssp_lstm_trainer_create", flat);
+    if (rc == SSP_OK) rc = tr->wait_state("ssp_lstm_trainer_create");
     if (rc != SSP_OK) {
         delete tr;
         return rc;
@@ -526,103 +443,35 @@ int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n
     return SSP_OK;
 }
 
-int ssp_lstm_trainer_destroy(ssp_lstm_trainer* trainer) {
-    if (!trainer) return SSP_OK;
-    ssp::quiesce_ctx(trainer->ctx);
-    delete trainer;
-    return SSP_OK;
-}
+int ssp_lstm_trainer_destroy(ssp_lstm_trainer* trainer) { return trainer_destroy(trainer); }
 
 int ssp_lstm_trainer_epoch(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                            float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_lstm_trainer_epoch");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(lt_check_data("ssp_lstm_trainer_epoch", trainer, X, labels, N, where));
     ssp_lstm_trainer* tr = trainer;
-    if (batch_size < 1 || batch_size > tr->max_batch)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_epoch: batch_size %d outside [1, %d]", batch_size, tr->max_batch);
-    if (!(lr >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_epoch: lr");
-    if (order)
-        for (int64_t r = 0; r < N; ++r)
-            if (order[r] < 0 || order[r] >= N) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_epoch: order[%lld] lies outside [0, N)", (long long)r);
-    if (N == 0) return SSP_OK;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + batch_size - 1) / batch_size;
-    SSP_TRY(lt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->T * tr->D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    const int64_t* dO = nullptr;
-    if (order) {
-        SSP_TRY(tr->order.reserve((size_t)N * sizeof(int64_t)));
-        SSP_HIP(hipMemcpyAsync(tr->order.p, order, (size_t)N * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        dO = tr->order.as<int64_t>();
-    }
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * batch_size;
-        const int Bn = (int)(N - row0 < batch_size ? N - row0 : batch_size);
-        SSP_TRY(lt_step(tr, dX, dL, dO, row0, Bn, st, lr, s));
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return lt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_epoch("ssp_lstm_trainer_epoch", tr, X, tr ? (int64_t)tr->T * tr->D : 0, labels, N, order, batch_size, lr, loss_sum, n_correct, where,
+                         kernel_ms, [&](const float* dX, const int32_t* dL, const int64_t* dO, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                             return lt_step(tr, dX, dL, dO, row0, Bn, slot, lr, s);
+                         });
 }
 
 int ssp_lstm_trainer_evaluate(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int64_t N, double* loss_sum, int64_t* n_correct,
                               int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_lstm_trainer_evaluate");
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (loss_sum) *loss_sum = 0.0;
-    if (n_correct) *n_correct = 0;
-    SSP_TRY(lt_check_data("ssp_lstm_trainer_evaluate", trainer, X, labels, N, where));
-    if (N == 0) return SSP_OK;
     ssp_lstm_trainer* tr = trainer;
-    ssp_ctx* ctx = tr->ctx;
-    SSP_TRY(use_ctx(ctx));
-    hipStream_t s = ctx->stream;
-    const int64_t steps = (N + tr->max_batch - 1) / tr->max_batch;
-    SSP_TRY(lt_slots(tr, steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * tr->T * tr->D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    Timer tm;
-    SSP_TRY(tm.start(kernel_ms != nullptr, s));
-    for (int64_t st = 0; st < steps; ++st) {
-        const int64_t row0 = st * tr->max_batch;
-        const int Bn = (int)(N - row0 < tr->max_batch ? N - row0 : tr->max_batch);
-        SSP_TRY(lt_forward(tr, dX, nullptr, row0, Bn, false, s));
-        SSP_TRY(lt_loss(tr, dL, nullptr, row0, Bn, false, st, s));
-    }
-    SSP_TRY(tm.stop(s, kernel_ms));
-    return lt_collect(tr, steps, loss_sum, n_correct, s);
+    return trainer_evaluate("ssp_lstm_trainer_evaluate", tr, X, tr ? (int64_t)tr->T * tr->D : 0, labels, N, loss_sum, n_correct, where, kernel_ms,
+                            [&](const float* dX, const int32_t* dL, int64_t row0, int Bn, int64_t slot, hipStream_t s) {
+                                SSP_TRY(lt_forward(tr, dX, nullptr, row0, Bn, false, s));
+                                return tr->loss(dL, nullptr, row0, Bn, false, slot, tr->logits.as<float>(), s);
+                            });
 }
 
 int ssp_lstm_trainer_step_times(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int32_t batch_size, float lr, float* ms_out) {
-    if (!ms_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_step_times: null output");
-    SSP_TRY(lt_check_data("ssp_lstm_trainer_step_times", trainer, X, labels, batch_size, SSP_DEVICE));
+    const char* who = "ssp_lstm_trainer_step_times";
     ssp_lstm_trainer* tr = trainer;
-    if (batch_size < 1 || batch_size > tr->max_batch)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_step_times: batch_size %d outside [1, %d]", batch_size, tr->max_batch);
-    if (!(lr >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_step_times: lr");
-    SSP_TRY(use_ctx(tr->ctx));
-    hipStream_t s = tr->ctx->stream;
-    LtMarks mk;
-    SSP_TRY(lt_step(tr, X, labels, nullptr, 0, batch_size, 0, lr, s, &mk));
-    SSP_HIP(hipStreamSynchronize(s));
-    if (mk.n != LT_LAUNCHES + 1) SSP_FAIL(SSP_ERR_HIP, "ssp_lstm_trainer_step_times: %d marks", mk.n);
-    for (int i = 0; i < LT_LAUNCHES; ++i) SSP_HIP(hipEventElapsedTime(&ms_out[i], mk.ev[i], mk.ev[i + 1]));
-    return SSP_OK;
+    StepMarks mk;
+    SSP_TRY(trainer_timed_step(who, tr, X, labels, batch_size, lr, ms_out, mk,
+                               [&](hipStream_t s, StepMarks* m) { return lt_step(tr, X, labels, nullptr, 0, batch_size, 0, lr, s, m); }));
+    if (mk.slot.size() != LT_LAUNCHES + 1) SSP_FAIL(SSP_ERR_HIP, "%s: %d marks", who, (int)mk.slot.size());
+    return mk.times(ms_out, LT_LAUNCHES);
 }
 
 int ssp_lstm_trainer_read(ssp_lstm_trainer* trainer, int32_t what, int32_t tensor, float* out) {
@@ -631,17 +480,9 @@ int ssp_lstm_trainer_read(ssp_lstm_trainer* trainer, int32_t what, int32_t tenso
     if (what < 0 || what > 3) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_read: what must be SSP_LSTM_PARAM .. SSP_LSTM_V");
     if (tensor < 0 || tensor > 4) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_read: tensor must be SSP_LSTM_W .. SSP_LSTM_BD");
     if ((tensor == 2 && !tr->has_b) || (tensor == 4 && !tr->has_bd)) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_read: the network has no such bias");
-    const DevBuf& buf = what == 0 ? tr->P : what == 1 ? tr->G : what == 2 ? tr->Mo : tr->Vo;
-    SSP_TRY(use_ctx(tr->ctx));
-    SSP_HIP(hipMemcpyAsync(out, buf.as<float>() + tr->off[tensor], (size_t)tr->len[tensor] * sizeof(float), hipMemcpyDeviceToHost, tr->ctx->stream));
-    SSP_HIP(hipStreamSynchronize(tr->ctx->stream));
-    return SSP_OK;
+    return tr->read_flat("ssp_lstm_trainer_read", what, tr->off[tensor], tr->len[tensor], out);
 }
 
-int ssp_lstm_trainer_steps(const ssp_lstm_trainer* trainer, int64_t* t) {
-    if (!trainer || !t) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_steps: null argument");
-    *t = trainer->t;
-    return SSP_OK;
-}
+int ssp_lstm_trainer_steps(const ssp_lstm_trainer* trainer, int64_t* t) { return trainer_steps("ssp_lstm_trainer_steps", trainer, t); }
 
 }  // extern "C"
