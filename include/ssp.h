@@ -318,7 +318,24 @@ int ssp_gmm_destroy(ssp_gmm* gmm);
  *  the UBM — are scored again in fp32 and only THEIR entries of its scores_out row are replaced; the row's other entries keep their
  *  bf16x3 values (within the band of the fp32 path's).  The arg-max is the fp32 path's in every case.  A re-scoring pass too large for
  *  one launch scores every model and replaces the whole row.)
- * Without loglik_out the per-utterance means are formed inside the scoring kernel (the [n_models x frames] matrix never exists). */
+ * Without loglik_out the per-utterance means are formed inside the scoring kernel (the [n_models x frames] matrix never exists).  With
+ * loglik_out the matrix is scored in ONE pass at the asked precision and scores_out / argmax_out are its per-utterance means: nothing is
+ * listed or scored twice and there is no host wait at any precision (precision 1 / 3 then answer as 2, ssp_gmm_last_rescored is 0).
+ * Non-finite rows.  A frame is BAD when any of its D entries is NaN or +-inf (the sidekit front end hands a digitally silent frame on as
+ * a NaN row on purpose).  What the call does with one, at every precision (0 to 4), fed from the host, the device, in slices, in
+ * scratch-bounded batches or through ssp_gmm_score_list:
+ *   bad frame       loglik_out is NaN at that frame under EVERY model (never -inf: an infinite entry meets inf - inf in the exponent or
+ *                   in the log-sum-exp's running maximum).
+ *   bad utterance   (one that holds a bad frame) every entry of its scores_out row is NaN and its argmax_out is 0 — numpy.argmax of an
+ *                   all-NaN row.  An empty utterance (T = 0) keeps the same NaN row and arg-max 0, the mean over no frames.
+ *   everything else no other frame and no other utterance changes.  precision 0 / 2: the other columns of loglik_out and the other rows of
+ *                   scores_out / argmax_out are BIT-IDENTICAL to those of the same call with the bad entries replaced by finite ones (same
+ *                   layout).  precision 1 / 3 / 4: the arg-max is the same and the scores stay within the tolerance class; the set of
+ *                   listed utterances changes (below) and with it a clean listed utterance's place in the compact re-scoring matrix.
+ *   listing         precision 1 / 3 (calls without loglik_out: those with it list nothing) always list a bad utterance (its margin is
+ *                   not comparable), score it again under every model, and count it in ssp_gmm_last_rescored.
+ * The call itself stays IEEE and reports no error for such rows; the sklearn-shaped Python layer (gmm_train.GaussianMixture,
+ * GMM_UBM.score_matrix) raises ValueError, as sklearn's input validation does. */
 int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_seg, float* loglik_out,
                   float* scores_out, int32_t* argmax_out, int where, int precision, float* kernel_ms);
 /* ssp_gmm_score_list: the scoring loops GMM_UBM.py:181-197 on a LIST of per-utterance feature matrices, without the host's vstack and
@@ -329,7 +346,8 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
  * scores_out / argmax_out as there, bit for bit, every precision.  A bad argument answers SSP_ERR_INVALID before any GPU work. */
 int ssp_gmm_score_list(ssp_gmm* gmm, const void* const* rows, int row_type, int32_t dim, const ssp_segments* frame_seg,
                        float* scores_out, int32_t* argmax_out, int precision, float* kernel_ms);
-/* utterances the last precision = 1 call scored again on the fp32 path (diagnostics) */
+/* utterances the last ssp_gmm_score / ssp_gmm_score_list call scored again on the fp32 path (diagnostics): the close calls of
+ * precision 1 / 3 (and of 4 when it ran as 1), bad and empty utterances among them; 0 after a call at precision 0 / 2 or with loglik_out */
 int ssp_gmm_last_rescored(const ssp_gmm* gmm, int32_t* n_out);
 /* precision = 4 (auto; GMM_UBM.py:183-187's arg-max with the fp32 path's result on every utterance, never dearer than the cheaper of the
  * two ways to get it): precision 1's guarantee scores close calls twice, which costs more than precision 0 once most utterances are
@@ -349,7 +367,11 @@ int ssp_gmm_last_auto(const ssp_gmm* gmm, int32_t* precision_used, int32_t* pilo
 /* Current parameters: HOST double weights[K], means[K x D], covars[K x D].  feats: float[n_frames x D].
  * Outputs (HOST double): nk_out[K] = sum_t resp[t,k];  sx_out[K x D] = sum_t resp[t,k] x[t,d];  sxx_out[K x D] = sum_t resp[t,k] x[t,d]^2;
  * loglik_sum_out = sum_t logsumexp_k(log w_k + log N(x_t | k))  (n_frames x sklearn's lower bound of the E step).
- * The O(K x D) closing arithmetic of the M step and the convergence test stay with the caller (float64). */
+ * The O(K x D) closing arithmetic of the M step and the convergence test stay with the caller (float64).
+ * Non-finite rows.  When any of the n_frames rows holds a NaN or +-inf entry (a BAD frame, as for ssp_gmm_score), EVERY entry of nk_out,
+ * sx_out and sxx_out and loglik_sum_out are NaN, on each kernel family (D <= 47 with K <= 64 or K > 64, D > 47); the call reports no
+ * error, and nothing of it stays behind in the ctx's scratch: the next call on clean rows gives the bits it gave before.  A caller that
+ * iterates (gmm_train.GaussianMixture.fit) must look before it loops: |NaN - previous bound| < tol never holds. */
 int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, const double* means, const double* covars,
                      const float* feats, int64_t n_frames, double* nk_out, double* sx_out, double* sxx_out,
                      double* loglik_sum_out, int where, float* kernel_ms);
@@ -363,6 +385,10 @@ int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, 
  * Contract.  K <= 64: each model's outputs are BIT-IDENTICAL to ssp_gmm_em_stats on that model's rows (same kernel body, same partition
  * of its frames, same float64 reduction order).  K > 64: fp32 MFMA log-sum-exp per frame and fp32 partial sums reduced in float64, within
  * fp32 rounding of ssp_gmm_em_stats (whose log-sum-exp comes from the scoring kernel) but not bit for bit.
+ * Non-finite rows.  A model whose row range holds a bad frame gets NaN in all of its nk_out, sx_out, sxx_out and loglik_sum_out, as
+ * ssp_gmm_em_stats gives.  A model whose range holds none is BIT-IDENTICAL to the same call without the bad entries — whichever other
+ * models of the launch are poisoned, overlapping ranges included — and a bad frame in a gap between the ranges, or in the rows of a
+ * model's last 64-frame tile that lie past its range, is never read.
  * Work: one upload of the parameters and one result copy + host wait per call; the models' partial sums are grouped into launches under
  * a scratch budget (SSP_EM_BATCH_SCRATCH_MB, default 1024). */
 int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,

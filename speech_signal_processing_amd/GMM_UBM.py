@@ -115,11 +115,19 @@ def score_matrix(models, ubm, feats):
     """GMM_UBM.py:181-187 as a function: pred[j, i] = models[i].score(feats[j]) - ubm.score(feats[j]).
 
     models / ubm: fitted sklearn GaussianMixture(covariance_type='diag') objects (or anything with weights_,
-    means_, covariances_).  feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64)."""
+    means_, covariances_).  feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64).
+    ValueError when an utterance with frames holds a NaN or infinite entry, as sklearn's score raises (the scorer answers such an
+    utterance with a NaN row — include/ssp.h, ssp_gmm_score — so this is read off the scores: no pass over the host arrays).  An empty
+    utterance keeps its NaN row."""
     ctx = api.default_context()
     scorer = api.GmmScorer.from_sklearn(ctx, models, ubm)
     r = scorer.score_list(feats)   # (the rows are gathered and narrowed by the library: no vstack + astype here)
     sc = np.asarray(r["scores"], dtype=np.float64)
+    lens = np.array([np.shape(f)[0] for f in feats], dtype=np.int64)
+    bad = np.flatnonzero(~np.isfinite(sc).all(axis=1) & (lens > 0))
+    if bad.size:
+        raise ValueError("Input contains NaN, infinity or a value too large for float32: utterance %d%s"
+                         % (int(bad[0]), "" if bad.size == 1 else " (and %d more)" % (bad.size - 1)))
     return sc[:, 1:] - sc[:, :1], np.asarray(r["argmax"]).astype(np.int64)
 
 

@@ -1279,6 +1279,7 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
         float* d_ll = (float*)sll.out(ctx, loglik_out, ll_bytes, where, &rc);
         SSP_TRY(rc);
         SSP_TRY(tm.start(kernel_ms != nullptr, s));
+        gmm->last_rescored = 0;  // (one pass at the asked precision, nothing is listed or scored twice: an earlier call's count does not stand)
         GmmArgs a{};
         a.feats = d_feats;
         a.wimg = gmm->wimg.as<float>();

@@ -22,6 +22,21 @@ import numpy as np
 from . import api
 
 
+def _nonfinite_message(what, row=None):
+    """sklearn's input validation in this layer's words: the model / utterance and the first offending row are named"""
+    at = "" if row is None else " (first at row %d)" % row
+    return "Input X%s contains NaN, infinity or a value too large for float32%s." % (what, at)
+
+
+def _first_bad_row(X):
+    """index of the first row of the device matrix X with a non-finite entry, or None: ONE reduction over what already sits on the device
+    (the row index is only looked up when the answer is yes)"""
+    import torch
+    if bool(torch.isfinite(X).all()):
+        return None
+    return int(torch.nonzero(~torch.isfinite(X).all(dim=1))[0, 0])
+
+
 class GaussianMixture:
     def __init__(self, n_components=1, covariance_type='diag', tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1,
                  weights_init=None, means_init=None, precisions_init=None, random_state=None, init_params='kmeans', ctx=None):
@@ -166,6 +181,11 @@ class GaussianMixture:
             import torch
             X = torch.from_numpy(X).to("cuda:%d" % ctx.device)
             torch.cuda.synchronize()
+        # sklearn validates its input (ValueError on NaN / infinity); the EM kernels answer such a row with NaN statistics, and
+        # |NaN - prev| < tol never holds: without this look the loop would run max_iter iterations and leave a model of NaNs
+        bad = _first_bad_row(X) if n > 0 else None
+        if bad is not None:
+            raise ValueError(_nonfinite_message("", bad))
         rng = np.random.RandomState(self.random_state) if not isinstance(self.random_state, np.random.RandomState) else self.random_state
         best = None
         for _ in range(self.n_init):
@@ -191,17 +211,26 @@ class GaussianMixture:
         ctx = self._ctx or api.default_context()
         return api.GmmScorer(ctx, self.weights_[None], self.means_[None], self.covariances_[None], has_ubm=False), ctx
 
+    # (sklearn raises ValueError on a NaN / infinite entry; the scorer answers one with NaN at that frame and in the utterance's score
+    #  — include/ssp.h, ssp_gmm_score — so the answer is read off the result: no extra pass over X)
     def score_samples(self, X):
         sc, ctx = self._scorer()
         X = np.ascontiguousarray(X, dtype=np.float32)
         seg = api.Segments.from_lengths(ctx, [X.shape[0]])
-        return np.asarray(sc.score(X, seg, loglik=True, scores=False, argmax=False)["loglik"], dtype=np.float64)[0]
+        ll = np.asarray(sc.score(X, seg, loglik=True, scores=False, argmax=False)["loglik"], dtype=np.float64)[0]
+        bad = np.flatnonzero(~np.isfinite(ll))
+        if bad.size:
+            raise ValueError(_nonfinite_message("", int(bad[0])))
+        return ll
 
     def score(self, X, y=None):
         sc, ctx = self._scorer()
         X = np.ascontiguousarray(X, dtype=np.float32)
         seg = api.Segments.from_lengths(ctx, [X.shape[0]])
-        return float(np.asarray(sc.score(X, seg, loglik=False, scores=True, argmax=False)["scores"])[0, 0])
+        v = float(np.asarray(sc.score(X, seg, loglik=False, scores=True, argmax=False)["scores"])[0, 0])
+        if X.shape[0] > 0 and not np.isfinite(v):
+            raise ValueError(_nonfinite_message(""))
+        return v
 
 
 def _m_step_many(nk, sx, sxx, n, reg_covar):
@@ -263,7 +292,13 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
         if X.shape[0] < K:
             raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, X.shape[0]))
     if 2 * D + 1 > 96:  # no batched kernel (ssp_gmm_em_stats_batch: D <= 47)
-        return [gm.fit(X) for gm, X in zip(gms, hosts)]
+        out = []
+        for m, (gm, X) in enumerate(zip(gms, hosts)):
+            try:
+                out.append(gm.fit(X))
+            except ValueError as e:
+                raise ValueError("model %d: %s" % (m, e)) from None
+        return out
     g0 = gms[0]
     ctx = g0._ctx or api.default_context()
     ns = np.array([X.shape[0] for X in hosts], dtype=np.int64)
@@ -271,6 +306,11 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
     import torch
     feats = torch.from_numpy(np.concatenate(hosts)).to("cuda:%d" % ctx.device)
     torch.cuda.synchronize()
+    # sklearn's input validation, before any model is touched: one reduction over the rows that already sit on the device
+    bad = _first_bad_row(feats)
+    if bad is not None:
+        m = int(np.searchsorted(offs, bad, side="right")) - 1
+        raise ValueError(_nonfinite_message(" of model %d" % m, bad - int(offs[m])))
     prof = profile if profile is not None else {}
     for k in ("kernel_ms", "mstep_s", "kmeanspp_s", "calls", "em_iters"):
         prof.setdefault(k, 0.0)

@@ -7,6 +7,10 @@ from oracle import ref_cpu as O
 ctx = api.default_context()
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 n_cases = int(sys.argv[2]) if len(sys.argv) > 2 else 30
+# non-finite rows (include/ssp.h, ssp_gmm_score / ssp_gmm_em_stats): with probability 1/4 a GMM or EM case carries ONE bad entry — NaN, +inf
+# or -inf — drawn from a stream of its own, so the shapes of a seed stay what they were
+rng_bad = np.random.default_rng([0x6ad, int(sys.argv[1]) if len(sys.argv) > 1 else 0])
+BAD_VALUES = (np.nan, np.inf, -np.inf)
 verbose = '-v' in sys.argv
 t_start = time.time()
 for case in range(n_cases):
@@ -24,18 +28,44 @@ for case in range(n_cases):
     X = rng.standard_normal((sum(lens), D)).astype(np.float32)
     seg = api.Segments.from_lengths(ctx, lens)
     sc = api.GmmScorer(ctx, w, mu, cov, has_ubm=has_ubm)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    bad_f = bad_u = -1
+    Xc = X
+    if rng_bad.random() < 0.25 and len(X):
+        bad_f = int(rng_bad.integers(0, len(X)))
+        bad_u = int(np.searchsorted(off, bad_f, side="right")) - 1
+        X = X.copy()
+        X[bad_f, int(rng_bad.integers(0, D))] = BAD_VALUES[int(rng_bad.integers(0, 3))]
+        if verbose:
+            print(case, "gmm bad entry: frame", bad_f, "utterance", bad_u, flush=True)
     for prec in ((0, 1) if D <= 64 else (0,)):
         r = sc.score(X, seg, loglik=True, scores=True, argmax=True, precision=prec)
         ll = np.asarray(r["loglik"])
+        ok = np.arange(len(X)) != bad_f
         for m in range(M):
-            ref = O.gmm_score_samples(w[m], mu[m], cov[m], X) if len(X) else np.zeros(0)
-            assert np.allclose(ll[m], ref, rtol=2e-4, atol=2e-4), (case, "loglik", K, D, m, prec, np.abs(ll[m] - ref).max())
-        off = np.concatenate([[0], np.cumsum(lens)])
+            ref = O.gmm_score_samples(w[m], mu[m], cov[m], Xc) if len(X) else np.zeros(0)
+            assert np.allclose(ll[m][ok], ref[ok], rtol=2e-4, atol=2e-4), (case, "loglik", K, D, m, prec, np.abs(ll[m][ok] - ref[ok]).max())
         for u, L in enumerate(lens):
-            if L == 0:
+            if L == 0 or u == bad_u:
                 continue
             refs = np.array([O.gmm_score(w[m], mu[m], cov[m], X[off[u]:off[u + 1]]) for m in range(M)])
             assert np.allclose(np.asarray(r["scores"])[u], refs, rtol=2e-4, atol=2e-4), (case, "score", u, prec)
+        if bad_f >= 0:
+            # rule 1: NaN exactly in the bad frame's column; rule 2: the bad utterance's row is NaN, arg-max 0; rule 3: nobody else moves
+            # (precision 0: bit for bit against the same call on the clean batch; precision 1: the tolerances above, and the fp32 arg-max)
+            assert np.isnan(ll[:, bad_f]).all() and np.isfinite(ll[:, ok]).all(), (case, "bad frame", K, D, prec, bad_f)
+            assert np.isnan(np.asarray(r["scores"])[bad_u]).all() and np.asarray(r["argmax"])[bad_u] == 0, (case, "bad utterance", prec, bad_u)
+            rc = sc.score(Xc, seg, loglik=True, scores=True, argmax=True, precision=0)
+            good = (np.array(lens) > 0) & (np.arange(len(lens)) != bad_u)
+            if prec == 0:
+                assert np.array_equal(ll[:, ok], np.asarray(rc["loglik"])[:, ok]), (case, "a clean frame changed", K, D)
+                assert np.array_equal(np.asarray(r["scores"])[good], np.asarray(rc["scores"])[good]), (case, "a clean utterance changed", K, D)
+            # (the arg-max promise of precision 1 belongs to calls without loglik: those list the close calls and the bad utterance)
+            rf = r if prec == 0 else sc.score(X, seg, precision=prec)
+            assert np.isnan(np.asarray(rf["scores"])[bad_u]).all() and np.asarray(rf["argmax"])[bad_u] == 0, (case, "bad utterance", prec, bad_u)
+            assert np.array_equal(np.asarray(rf["argmax"])[good], np.asarray(rc["argmax"])[good]), (case, "a clean arg-max changed", prec)
+            assert prec == 0 or M - int(has_ubm) < 2 or sc.last_rescored >= 1, (case, "bad utterance not listed", prec)
+    X = Xc
     # ---- the split-precision modes keep the fp32 path's arg-max (proven band: precision 1; calibrated band: 3), speakers a hair apart
     if D <= 64 and M - int(has_ubm) >= 2 and sum(lens) > 0:
         mu2 = mu.copy()
@@ -83,6 +113,11 @@ for case in range(n_cases):
         print(case, "em", Ke, De, ne, flush=True)
     we = rng.dirichlet(5 * np.ones(Ke)); mue = rng.standard_normal((Ke, De)); cve = rng.uniform(0.5, 2.0, (Ke, De))
     Xe = rng.standard_normal((ne, De)).astype(np.float32)
+    if rng_bad.random() < 0.25:   # a bad entry: every statistic is NaN, and the clean call right after it is untouched by it
+        Xb = Xe.copy()
+        Xb[int(rng_bad.integers(0, ne)), int(rng_bad.integers(0, De))] = BAD_VALUES[int(rng_bad.integers(0, 3))]
+        sb = api.gmm_em_stats(ctx, we, mue, cve, Xb)
+        assert all(np.isnan(sb[k]).all() for k in ("nk", "sx", "sxx")) and np.isnan(sb["loglik_sum"]), (case, "em bad entry", Ke, De, ne)
     st = api.gmm_em_stats(ctx, we, mue, cve, Xe)
     nk, sx, sxx, ll = O.gmm_em_stats(we, mue, cve, Xe)
     assert abs(st["loglik_sum"] - ll) <= 2e-5 * max(1.0, abs(ll)), (case, "em ll", Ke, De, ne)
