@@ -77,8 +77,15 @@ __device__ __forceinline__ float delta_weight(float t, float tp, float Tm1, floa
 // WALK: the THIRD kernel of a launch (mfcc_stream_walk.hip).  It walks the chunks the scan kernel flagged (a non-finite cepstrum in a time
 // step's window: a digitally silent frame, a NaN sample) once more, sequentially, with every step formed term by term as the reference
 // forms it, and rewrites every row of them; nothing flagged — the normal case — costs one load per workgroup.
-template <int NZ, int POWER, int PRE, int MELV, int KS, int NS, int OCC, int CM, int WALK>
-__global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(MfccArgs a, FastArgs f, StreamArgs sa) {
+// GEO: 0 = the geometry is read from the plan at run time; 1 + delta order = the sidekit call sites' geometry as constants (window 400,
+// hop 160: a stage of three whole DMA pieces and a half one; 24 filters, no padded log-mel slots; 13 (1 + order) columns).  The arithmetic
+// is the same; what goes is the scalar work that re-derives the plan's constants every quad (stream_fixed_geo chooses the instance)
+// (one body, two kernel names: mfcc_stream512_kernel<nine parameters> are the run-time-geometry instances, as ever;
+//  mfcc_stream512_geo_kernel<the same nine, GEO> the fixed-geometry ones)
+template <int NZ, int POWER, int PRE, int MELV, int KS, int NS, int OCC, int CM, int WALK, int GEO>
+__device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const FastArgs& f, const StreamArgs& sa) {
+    static_assert(GEO >= 0 && GEO <= 3 && (GEO == 0 || (NZ == 13 && KS == 6 && MELV != 0)), "fixed geometry: the 400 / 160 / 24-filter family only");
+    constexpr bool FIXG = GEO != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (WALK && sa.work_counter[1] == 0) return;  // nothing was flagged
     const int tid = threadIdx.x, lane = tid & 63;
@@ -87,6 +94,7 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
     constexpr int nc = 13;
     constexpr int mel_ns = NS;
 
+    // (the per-wave LDS offsets stay run-time values in the fixed-geometry instances too: as constants they measured 0.04 ms slower)
     char* zbuf = smem + wave * sa.wave_bytes;            // 4 frame images
     float* stage = reinterpret_cast<float*>(zbuf + 4 * ZFRAME);
     char* ring = zbuf + 4 * ZFRAME + sa.stage_bytes;     // [RING_FRAMES][16] floats
@@ -149,14 +157,17 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
         mfid = f.pc_fid[lane];
     }
 
-    const int hop = a.hop;
+    const int hop = FIXG ? 160 : a.hop;
     const float pre = PRE ? a.preemph : 0.f;
     const float npre = -pre;
-    const int n_piece = (f.slen + 255) >> 8;
-    const bool has_half = (f.slen & 255) != 0 && (f.slen & 255) <= 128;
+    const int slen = FIXG ? 3 * 160 + 32 * 13 : f.slen;  // (896 floats: three whole 1-KiB pieces and a half one)
+    const int n_piece = (slen + 255) >> 8;
+    const bool has_half = (slen & 255) != 0 && (slen & 255) <= 128;
     const int n_full = has_half ? n_piece - 1 : n_piece;
-    const int dord = a.delta_order;
-    const int Dd = a.d_out;
+    const int dord = FIXG ? GEO - 1 : a.delta_order;
+    const int Dd = FIXG ? nc * GEO : a.d_out;
+    const int n_filt = FIXG ? 24 : a.n_filt;
+    const int lm_pad = FIXG ? 0 : f.lm_pad;
     const float half_inv = 0.5f * a.delta_inv_denom;
     const uint32_t stage_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr_t)stage);
 
@@ -223,9 +234,20 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
 
         // sample DMA of quad q: slen floats from (ta + 4 q) hop, 1-KiB pieces (instruction offsets advance the global and the
         // LDS address together), a trailing half piece on lanes 0..31; outside [0, N) reads as zero
+        // (GEO: three whole pieces and the half one, no tests, one LDS base for all four.  The pieces leave back to back: issued one
+        //  at a time between the window and FFT phases instead — three placements, profiles/stream_fixed_geometry.md — they change nothing)
         auto prefetch = [&](int q) {
-            const int vo = (ta + 4 * q) * hop * 4 + lane * 16;
+            int ol = lane;
+            if (FIXG) asm volatile("" : "+v"(ol));  // (opaque: or the offset becomes an induction variable — one more register live across the loop)
+            const int vo = (ta + 4 * q) * hop * 4 + ol * 16;
             const lds_ptr_t lp = (lds_ptr_t)(uintptr_t)stage_lds;
+            if (FIXG) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 1024, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 2048, 0);
+                if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 3072, 0);
+                return;
+            }
             if (n_full > 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 0, 0);
             if (n_full > 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 1024, 0);
             if (n_full > 2) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 2048, 0);
@@ -272,12 +294,26 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
         // the quad's DMA has landed; the stores of a preceding step were issued behind it and may still be in flight
         auto wait_dma = [&]() {
 #ifndef SSP_S_NOWAIT  // (ablation, wrong results: what the wait for the sample DMA costs)
-            if (stores_pending == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (stores_pending == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-            else if (stores_pending == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else if (stores_pending == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else if (stores_pending == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+            if constexpr (FIXG) {
+                // three quad tops in four have no store behind the DMA: one compare in front of vmcnt(0).  The counted waits sit behind
+                // it; the count goes through an opaque copy, or the compiler merges the two levels into one compare tree again.  A step
+                // of this instance leaves 2 (1 + order) stores in the transposed form, 4 / 9 / 13 in the chained one
+                if (__builtin_expect(stores_pending == 0, 1)) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                } else {
+                    int np = stores_pending;
+                    asm volatile("" : "+s"(np));
+                    if (np == 2 * GEO) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GEO) : "memory");
+                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GEO >= 3 ? 13 : (GEO == 2 ? 9 : 4)) : "memory");
+                }
+            } else {  // (the run-time-geometry instances keep the compare tree: with the two-level form their order-1 pass measured 2 % slower)
+                if (stores_pending == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                else if (stores_pending == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                else if (stores_pending == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                else if (stores_pending == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+                else if (stores_pending == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(13)" ::: "memory");
+            }
 #endif
             stores_pending = 0;
         };
@@ -433,11 +469,11 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
 #ifndef SSP_S_NOMEL
             if (!CM) {
                 float* lm = reinterpret_cast<float*>(zbuf + g * ZFRAME + LM_OFF - 64 * g);
-                if (j < f.lm_pad) lm[a.n_filt + j] = 0.f;
-            } else if (j < f.lm_pad) {  // (scaling instances: the address from an opaque copy of the lane id — hoisted out of the loop it costs the register that spills)
+                if (j < lm_pad) lm[n_filt + j] = 0.f;
+            } else if (j < lm_pad) {  // (scaling instances: the address from an opaque copy of the lane id — hoisted out of the loop it costs the register that spills)
                 int ol = lane;
                 asm volatile("" : "+v"(ol));
-                reinterpret_cast<float*>(zbuf + (ol >> 4) * (ZFRAME - 64) + LM_OFF)[a.n_filt + (ol & 15)] = 0.f;
+                reinterpret_cast<float*>(zbuf + (ol >> 4) * (ZFRAME - 64) + LM_OFF)[n_filt + (ol & 15)] = 0.f;
             }
             float sfr[4];
 #pragma unroll
@@ -498,6 +534,13 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
         };
         // cepstra of quad qq -> ring: lane (g, j): cepstra 4 g .. 4 g + 3 of frame ta + 4 qq + j (j < 4); frames past the chunk's last one
         // and virtual quads behind it store zeros (their ring rows must read as finite values)
+        // GEO: ring positions are wrapped counters, not remainders (a division by 6 or 24 is four to seven scalar instructions, and the
+        // loop and a step took eight of them): qrow = byte offset of quad qq's four rows, QROW (qq mod 6); srow = byte offset of
+        // relative frame 16 b, the step's base, 0 / 16 / 8 rows in turn.  (The run-time-geometry instances keep the remainders — their
+        // code is the one every other plan was measured on)
+        constexpr int RING_BYTES = RING_FRAMES * RING_ROW, QROW = 4 * RING_ROW;
+        auto ring_wrap = [](int o) { return o >= RING_BYTES ? o - RING_BYTES : o; };
+        int qrow = 0, srow = 0;
         auto ring_put = [&](int qq, v4f cq, bool real) {
             int ol = lane;
             asm volatile("" : "+v"(ol));
@@ -505,8 +548,10 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
             if (j < 4) {
                 const bool ok = real && ta + 4 * qq + j < tb;
                 const v4f cv = ok ? cq : v4f{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<v4f*>(ring + ((((qq + 6) % 6) * 4 + j) * RING_ROW) + g * 16) = cv;
+                if constexpr (FIXG) *reinterpret_cast<v4f*>(ring + qrow + j * RING_ROW + g * 16) = cv;
+                else *reinterpret_cast<v4f*>(ring + ((((qq + 6) % 6) * 4 + j) * RING_ROW) + g * 16) = cv;
             }
+            if (FIXG) qrow = ring_wrap(qrow + QROW);
         };
         // ================= time step b: rows [16 b - 4, 16 b + 12) of (c, delta, delta-delta) leave =================
         typedef float cbarr_t[6];
@@ -516,10 +561,16 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
             int ol = lane;
             asm volatile("" : "+v"(ol));
             const int g = ol >> 4, j = ol & 15;
+            int mb = ring_wrap(srow + 16 * RING_ROW);  // GEO: row (16 b - 8) mod 24, a multiple of 4; then four rows on per operand
 #pragma unroll
             for (int s = 0; s < 6; ++s) {
-                const int m = (rb + 16 + 4 * s) % RING_FRAMES;  // (rb - 8 + 4 s) mod 24, a multiple of 4
-                cb[s] = *reinterpret_cast<const float*>(ring + (m + g) * RING_ROW + j * 4);
+                if constexpr (FIXG) {
+                    cb[s] = *reinterpret_cast<const float*>(ring + mb + g * RING_ROW + j * 4);
+                    mb = ring_wrap(mb + QROW);
+                } else {
+                    const int m = (rb + 16 + 4 * s) % RING_FRAMES;  // (rb - 8 + 4 s) mod 24, a multiple of 4
+                    cb[s] = *reinterpret_cast<const float*>(ring + (m + g) * RING_ROW + j * 4);
+                }
             }
         };
         auto time_step = [&](int b, const cbarr_t& cb) {
@@ -570,10 +621,16 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
             if (CM && b == 0) piv = j < nc ? *reinterpret_cast<const float*>(ring + j * 4) : 0.f;  // cepstra of frame 0 (CM: ta == 0)
             // cepstra of the output rows straight from the ring
             {
-                const int m4 = (rb + 20) % RING_FRAMES;  // (rb - 4) mod 24
-                int slot = m4 + 4 * g;
-                slot = slot >= RING_FRAMES ? slot - RING_FRAMES : slot;
-                const float* cr = reinterpret_cast<const float*>(ring + slot * RING_ROW + j * 4);
+                const float* cr;
+                if constexpr (FIXG) {
+                    const int slot = ring_wrap(ring_wrap(srow + 20 * RING_ROW) + 4 * g * RING_ROW);  // row (rb - 4) mod 24, + 4 g
+                    cr = reinterpret_cast<const float*>(ring + slot + j * 4);
+                } else {
+                    const int m4 = (rb + 20) % RING_FRAMES;  // (rb - 4) mod 24
+                    int slot = m4 + 4 * g;
+                    slot = slot >= RING_FRAMES ? slot - RING_FRAMES : slot;
+                    cr = reinterpret_cast<const float*>(ring + slot * RING_ROW + j * 4);
+                }
                 const v4f o0 = v4f{cr[0], cr[16], cr[32], cr[48]};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) put(r, 0, o0[r], true);
@@ -637,9 +694,15 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
                 // the cepstra of this lane's frame need no product (until round 5 they took four with a unit matrix): four consecutive
                 // cepstra of one frame are 16 contiguous bytes of its ring row.  (A non-finite frame therefore stays in its own row of this
                 // block; what the scan kernel looks at is the delta block, or every row when there are no deltas.)
-                int slot = (rb + 20) % RING_FRAMES + j;  // (rb - 4 + j) mod 24
-                slot = slot >= RING_FRAMES ? slot - RING_FRAMES : slot;
-                const v4f c = *reinterpret_cast<const v4f*>(ring + slot * RING_ROW + g * 16);
+                v4f c;
+                if constexpr (FIXG) {
+                    const int slot = ring_wrap(ring_wrap(srow + 20 * RING_ROW) + j * RING_ROW);  // row (rb - 4 + j) mod 24
+                    c = *reinterpret_cast<const v4f*>(ring + slot + g * 16);
+                } else {
+                    int slot = (rb + 20) % RING_FRAMES + j;  // (rb - 4 + j) mod 24
+                    slot = slot >= RING_FRAMES ? slot - RING_FRAMES : slot;
+                    c = *reinterpret_cast<const v4f*>(ring + slot * RING_ROW + g * 16);
+                }
                 store(c, 0);
             }
             if (dord >= 1) {
@@ -721,6 +784,7 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
             if (TSTEP && interior) time_step_T(b, cb);
             else time_step(b, cb);
 #endif
+            if (FIXG) srow = ring_wrap(srow + 16 * RING_ROW);  // (the steps of a chunk come in turn, b = 0, 1, 2 ...)
         };
 
         if constexpr (DENSE) {
@@ -849,6 +913,7 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
 #ifdef SSP_S_PAD  // (diagnostic: the loop's code address shifted by SSP_S_PAD instructions)
             asm volatile(".rept " SSP_STR(SSP_S_PAD) "\n s_nop 0\n .endr");
 #endif
+            if (FIXG) qrow = 5 * QROW;  // (the first put is quad -1's)
             for (int q = 0; q < nquads; ++q) {
                 zarr_t z;
                 pfarr_t pf;
@@ -995,9 +1060,42 @@ __global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(
 #endif
 }
 
+template <int NZ, int POWER, int PRE, int MELV, int KS, int NS, int OCC, int CM, int WALK>
+__global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_kernel(MfccArgs a, FastArgs f, StreamArgs sa) {
+    mfcc_stream512_body<NZ, POWER, PRE, MELV, KS, NS, OCC, CM, WALK, 0>(a, f, sa);
+}
+template <int NZ, int POWER, int PRE, int MELV, int KS, int NS, int OCC, int CM, int WALK, int GEO>
+__global__ __launch_bounds__(64 * STREAM_WAVES, OCC) void mfcc_stream512_geo_kernel(MfccArgs a, FastArgs f, StreamArgs sa) {
+    static_assert(GEO >= 1, "GEO = 0 is mfcc_stream512_kernel");
+    mfcc_stream512_body<NZ, POWER, PRE, MELV, KS, NS, OCC, CM, WALK, GEO>(a, f, sa);
+}
+// No instance of this kernel carries scratch: a spill reload inside the quad loop waits on vmcnt behind the sample DMA.  The one member of
+// the fixed-geometry family that does not compile without it — delta order 1, three filterbank reads, two scan steps, no scaling: three
+// registers spilled, reloaded every quad — is not instantiated; those plans keep the run-time-geometry instance (165 registers, no spill).
+// (tests/test_isa_guards.py selects kernels by the name mfcc_stream512_kernel and does not see the geo instances: their register / spill
+//  figures are read off every build by hand, profiles/stream_fixed_geometry.md has the table)
+constexpr bool stream_geo_excluded(int melv, int ns, int cm, int geo) { return geo == 2 && cm == 0 && melv == 3 && ns <= 2; }
+typedef void (*stream_kernel_t)(MfccArgs, FastArgs, StreamArgs);
+template <int NZ, int POWER, int PRE, int MELV, int KS, int NS, int OCC, int CM, int WALK, int GEO>
+static inline stream_kernel_t stream_kernel() {
+    if constexpr (GEO == 0) return mfcc_stream512_kernel<NZ, POWER, PRE, MELV, KS, NS, OCC, CM, WALK>;
+    else if constexpr (stream_geo_excluded(MELV, NS, CM, GEO)) return nullptr;  // (never asked for: launch_mfcc_stream_impl, geo)
+    else return mfcc_stream512_geo_kernel<NZ, POWER, PRE, MELV, KS, NS, OCC, CM, WALK, GEO>;
+}
+
 // ------------------------------------------------------------------------------------------------ launch (first / third kernel)
 // k-steps of the DCT product the instances are built for: 6 (<= 24 filters: the sidekit dialects) or 10 (<= 40: the in-repo MFCC)
 static inline int stream_ks(const ssp_mfcc_cfg& c) { return (c.n_filt + 3) / 4 <= 6 ? 6 : 10; }
+
+// The fixed-geometry instances (GEO = 1 + delta order) cover the sidekit call sites' framing — window 400, hop 160, 24 filters, 13 cepstra,
+// power spectrum, pre-emphasis — and nothing else; every other plan takes the instances that read the geometry at run time.
+// SSP_MFCC_STREAM_RUNTIME_GEO=1 sends these plans there too (the two must agree bit for bit: tests/test_stream_fixed_geometry_gpu.py)
+static inline bool stream_fixed_geo(const ssp_mfcc_cfg& c, const FastArgs& f, const MfccArgs& a) {
+    if (getenv("SSP_MFCC_STREAM_RUNTIME_GEO")) return false;
+    return c.win_len == 400 && c.hop == 160 && a.hop == 160 && c.n_filt == 24 && a.n_filt == 24 && c.n_ceps == 13 && c.spec_power == 2 &&
+           c.preemph_mode != 0 && f.slen == 3 * 160 + 32 * 13 && f.melv >= 2 && f.melv <= 4 && a.delta_order >= 0 && a.delta_order <= 2 &&
+           a.d_out == 13 * (1 + a.delta_order);
+}
 
 // WALK = 0: the first kernel of a launch (mfcc_stream.hip instantiates these); WALK = 1: the second (mfcc_stream_walk.hip), same
 // instance, same grid, same arguments.  dry_run: only answers whether an instance of the kernel exists for (cfg, in-kernel scaling) — the
@@ -1042,39 +1140,61 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
     // (scaling instances keep three waves per SIMD only where the seven extra registers of the column sums fit without a spill)
     const int occ = (nz == 13 && KS == 6 && lds <= 53248 && f.melv != 0 && (!cm || (f.melv <= 3 && f.mel_ns <= 2))) ? 3 : 2;
     const int wg_waves = STREAM_WAVES;
+    // geometry as template constants where such an instance exists (the non-scaling ones at three waves per SIMD only); the answer is
+    // the same for a dry run and for the launch, and the same in both translation units
+#ifdef SSP_FAST_MINIMAL
+    const bool geo_inst = f.melv == 3 && f.mel_ns <= 2 && !cm && occ == 3;
+#else
+    const bool geo_inst = cm || occ == 3;
+#endif
+    const int geo = (stream_fixed_geo(c, f, args) && KS == 6 && nz == 13 && sa.stage_bytes == 3 * 1024 + 512 && geo_inst &&
+                     !stream_geo_excluded(f.melv, f.mel_ns <= 2 ? 2 : 4, cm, 1 + args.delta_order)) ? 1 + args.delta_order : 0;
     bool launched = false;
 #define SSP_STREAM_CASE(NZ_, PW_, PR_, MV_, KS_, OCC_) SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, 0)
-#define SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_)                                                        \
-    if (!launched && dry_run && nz == NZ_ && pw == PW_ && pr == PR_ && f.melv == MV_ && KS == KS_ && occ == OCC_ && cm == CM_) \
+#define SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_) SSP_STREAM_CASE_G(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_, 0)
+#define SSP_STREAM_CASE_G(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_, GEO_)                                                   \
+    if (!launched && dry_run && nz == NZ_ && pw == PW_ && pr == PR_ && f.melv == MV_ && KS == KS_ && occ == OCC_ && cm == CM_ && geo == GEO_) \
         launched = true;                                                                                                \
-    if (!launched && nz == NZ_ && pw == PW_ && pr == PR_ && f.melv == MV_ && KS == KS_ && occ == OCC_ && cm == CM_) {   \
-        auto* kfn = f.mel_ns <= 2 ? mfcc_stream512_kernel<NZ_, PW_, PR_, MV_, KS_, 2, OCC_, CM_, WALK>                    \
-                                  : mfcc_stream512_kernel<NZ_, PW_, PR_, MV_, KS_, 4, OCC_, CM_, WALK>;                   \
+    if (!launched && nz == NZ_ && pw == PW_ && pr == PR_ && f.melv == MV_ && KS == KS_ && occ == OCC_ && cm == CM_ && geo == GEO_) { \
+        const stream_kernel_t kfn = f.mel_ns <= 2 ? stream_kernel<NZ_, PW_, PR_, MV_, KS_, 2, OCC_, CM_, WALK, GEO_>()    \
+                                                  : stream_kernel<NZ_, PW_, PR_, MV_, KS_, 4, OCC_, CM_, WALK, GEO_>();   \
         if (lds > 64 * 1024)                                                                                            \
             SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         int per_cu = 0;                                                                                                 \
         SSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 64 * wg_waves, lds));                        \
         const int grid = std::min((n_chunks + wg_waves - 1) / wg_waves, std::max(1, per_cu) * p->ctx->num_cu);          \
         if (!WALK) SSP_HIP(hipMemsetAsync(sa.work_counter, 0, 64 + (size_t)n_chunks * 4, stream)); /* counters + flags */    \
-        if (getenv("SSP_DEBUG")) fprintf(stderr, "[ssp] mfcc stream%s: grid %d (%d per CU), lds %zu\n", WALK ? " (second kernel)" : "", grid, per_cu, lds); \
+        if (getenv("SSP_DEBUG")) fprintf(stderr, "[ssp] mfcc stream%s: grid %d (%d per CU), lds %zu, geo %d cm %d\n", WALK ? " (second kernel)" : "", grid, per_cu, lds, GEO_, CM_); \
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * wg_waves), lds, stream, args, f, sa);                             \
         launched = true;                                                                                                \
     }
     // (scaling at three waves per SIMD exists for two scan steps only: occ above)
-#define SSP_STREAM_CASE_CM3(MV_)                                                                                          \
-    if (!launched && dry_run && nz == 13 && pw == 2 && pr == 1 && f.melv == MV_ && KS == 6 && occ == 3 && cm == 1) launched = true; \
-    if (!launched && nz == 13 && pw == 2 && pr == 1 && f.melv == MV_ && KS == 6 && occ == 3 && cm == 1) {                   \
-        auto* kfn = mfcc_stream512_kernel<13, 2, 1, MV_, 6, 2, 3, 1, WALK>;                                               \
+#define SSP_STREAM_CASE_CM3(MV_, GEO_)                                                                                    \
+    if (!launched && dry_run && nz == 13 && pw == 2 && pr == 1 && f.melv == MV_ && KS == 6 && occ == 3 && cm == 1 && geo == GEO_) launched = true; \
+    if (!launched && nz == 13 && pw == 2 && pr == 1 && f.melv == MV_ && KS == 6 && occ == 3 && cm == 1 && geo == GEO_) {    \
+        const stream_kernel_t kfn = stream_kernel<13, 2, 1, MV_, 6, 2, 3, 1, WALK, GEO_>();                               \
         int per_cu = 0;                                                                                                   \
         SSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 64 * wg_waves, lds));                          \
         const int grid = std::min((n_chunks + wg_waves - 1) / wg_waves, std::max(1, per_cu) * p->ctx->num_cu);            \
         if (!WALK) SSP_HIP(hipMemsetAsync(sa.work_counter, 0, 64 + (size_t)n_chunks * 4, stream));                            \
+        if (getenv("SSP_DEBUG")) fprintf(stderr, "[ssp] mfcc stream%s: grid %d (%d per CU), lds %zu, geo %d cm 1\n", WALK ? " (second kernel)" : "", grid, per_cu, lds, GEO_); \
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * wg_waves), lds, stream, args, f, sa);                               \
         launched = true;                                                                                                  \
     }
-    SSP_STREAM_CASE_CM3(2) SSP_STREAM_CASE_CM3(3)
-#undef SSP_STREAM_CASE_CM3
+    SSP_STREAM_CASE_CM3(2, 0) SSP_STREAM_CASE_CM3(3, 0)
     SSP_STREAM_CASE_CM(13, 2, 1, 2, 6, 2, 1) SSP_STREAM_CASE_CM(13, 2, 1, 3, 6, 2, 1) SSP_STREAM_CASE_CM(13, 2, 1, 4, 6, 2, 1)
+    // the fixed-geometry family: the same instance lists once per delta order
+#ifdef SSP_FAST_MINIMAL
+    SSP_STREAM_CASE_G(13, 2, 1, 3, 6, 3, 0, 1) SSP_STREAM_CASE_G(13, 2, 1, 3, 6, 3, 0, 3)  // (order 1: stream_geo_excluded)
+#else
+#define SSP_STREAM_FIXED(GEO_)                                                                                            \
+    SSP_STREAM_CASE_CM3(2, GEO_) SSP_STREAM_CASE_CM3(3, GEO_)                                                             \
+    SSP_STREAM_CASE_G(13, 2, 1, 2, 6, 2, 1, GEO_) SSP_STREAM_CASE_G(13, 2, 1, 3, 6, 2, 1, GEO_) SSP_STREAM_CASE_G(13, 2, 1, 4, 6, 2, 1, GEO_) \
+    SSP_STREAM_CASE_G(13, 2, 1, 2, 6, 3, 0, GEO_) SSP_STREAM_CASE_G(13, 2, 1, 3, 6, 3, 0, GEO_) SSP_STREAM_CASE_G(13, 2, 1, 4, 6, 3, 0, GEO_)
+    SSP_STREAM_FIXED(1) SSP_STREAM_FIXED(2) SSP_STREAM_FIXED(3)
+#undef SSP_STREAM_FIXED
+#endif
+#undef SSP_STREAM_CASE_CM3
     if constexpr (!WALK) {  // dense bands (the PLP front end): no time steps, no second kernel
         SSP_STREAM_CASE(13, 2, 1, 0, 6, 2)
     }
@@ -1102,6 +1222,7 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
 #endif
 #undef SSP_STREAM_CASE
 #undef SSP_STREAM_CASE_CM
+#undef SSP_STREAM_CASE_G
     if (!launched) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc(stream): no kernel instance for this cfg");
     if (dry_run) return SSP_OK;
     SSP_HIP(hipGetLastError());

@@ -12,10 +12,11 @@ for v in "$@"; do
   if [ "$v" = "-" ]; then unset SSP_LIB_PATH; else export SSP_LIB_PATH=$ROOT/tools/scratch/variants/$v.so; fi
   rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $O/p_$v -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline --no-env --detail $O/d_$v.json > $O/$v.log 2>&1
   python3 - $v $(find $O/p_$v -name "*counter_collection.csv" | head -1) >> $ROOT/gpurun_out/lds_attrib.txt <<'PY'
-import csv, sys, collections
+import csv, re, sys, collections
 agg = collections.defaultdict(list)
+first = re.compile(r"mfcc_stream512_kernel<[^>]*, 0>\(|mfcc_stream512_geo_kernel<[^>]*, 0, \d>\(")  # WALK = 0, either geometry
 for r in csv.DictReader(open(sys.argv[2])):
-    if "mfcc_stream512_kernel" in r["Kernel_Name"] and ", 0>(" in r["Kernel_Name"]:
+    if first.search(r["Kernel_Name"]):
         agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
 q = 100000 * 75.0
 print(sys.argv[1], " ".join("%s/quad=%.1f" % (k.replace("SQ_", ""), sum(v) / len(v) / q) for k, v in sorted(agg.items())), "launches", len(next(iter(agg.values()))) if agg else 0)

@@ -2,7 +2,7 @@
 summary of the same command, one per-launch listing per stage (so that every quoted roofline fraction can be recomputed from
 profiles/ alone) and the PMC readings, each tied to the sha256 of the kernel source it was taken on.
     python tools/store_round.py r03"""
-import collections, csv, json, os, shutil, subprocess, sys
+import collections, csv, json, os, re, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (kernel_source_sha256)
@@ -30,7 +30,7 @@ if have("kernel_stats.csv"):
         by = collections.OrderedDict()
         for r in csv.DictReader(open(os.path.join(S, "kernel_trace.csv"))):
             n = r["Kernel_Name"]
-            if any(k in n for k in ("mfcc_stream512_kernel<13, 2, 1, 3, 6, 2, 3, 0, 0>", "gmm_loglik_kernel<10, 2, true>", "cosine_reg_kernel<32, false>")):
+            if any(k in n for k in ("mfcc_stream512_kernel<13, 2, 1, 3, 6, 2, 3, 0, 0>", "mfcc_stream512_geo_kernel<13, 2, 1, 3, 6, 2, 3, 0, 0, 3>", "gmm_loglik_kernel<10, 2, true>", "cosine_reg_kernel<32, false>")):
                 by.setdefault(n, []).append(((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6, int(r["Grid_Size_X"])))
         md += "\nPer workload, from the kernel trace of the SAME run (the host-fed stages launch these kernels once per 64-MiB slice and the\n" \
               "split-precision scorers once per re-scoring pass / pilot: the per-kernel averages above mix those in):\n\n| kernel | launches of one workload (grouped by duration) | avg ms | min ms | max ms |\n|---|---|---|---|---|\n"
@@ -112,29 +112,34 @@ for st, (kern, key) in DOM.items():
 
 
 # ---- PMC
-def pmc(prefix, kern, also=""):
+PMC_NAMES = {}  # prefix -> the kernel names that matched
+
+
+def pmc(prefix, kern, also=""):  # also: a regular expression the kernel's name must match as well
     agg = collections.OrderedDict()
     i = 1
     while have("pmc_%s_%d.csv" % (prefix, i)):
         per = collections.defaultdict(list)
         for r in csv.DictReader(open(os.path.join(S, "pmc_%s_%d.csv" % (prefix, i)))):
-            if kern in r["Kernel_Name"] and also in r["Kernel_Name"]:
+            if kern in r["Kernel_Name"] and re.search(also, r["Kernel_Name"]):
                 per[r["Counter_Name"]].append(float(r["Counter_Value"]))
+                PMC_NAMES.setdefault(prefix, set()).add(r["Kernel_Name"].split("(")[0].replace("void ", "").replace(" ", ""))
         for k, v in per.items():
             agg[k] = {"mean_per_launch": sum(v) / len(v), "launches": len(v)}
         i += 1
     return agg
 
 
-a = pmc("512", "mfcc_stream512", ", 0>(")  # (the first kernel of the launch: <..., WALK = 0>; the second exits on one load)
+a = pmc("512", "mfcc_stream512", r"_kernel<[^>]*, 0>\(|_geo_kernel<[^>]*, 0, \d>\(")  # (the first kernel of the launch: <..., WALK = 0> or the fixed-geometry <..., WALK = 0, GEO>; the second exits on one load)
 if a:
+    kname = " | ".join(sorted(PMC_NAMES.get("512", ()))) or "ssp::mfcc_stream512_kernel"
     line = json.load(open(os.path.join(S, "stage_mfcc_bench_detail.json"))) if have("stage_mfcc_bench_detail.json") else None
     algo = 23848800000
     g = lambda k: a[k]["mean_per_launch"] if k in a else None
     rd = 2.0 * g("FETCH_SIZE") * 1024 if g("FETCH_SIZE") is not None else None
     wr = g("WRITE_SIZE") * 1024 if g("WRITE_SIZE") is not None else None
     if rd is not None and wr is not None:
-        doc = {"kernel": "ssp::mfcc_stream512_kernel<13,2,1,3,6,2,3,0,0> (wave-stream, 3 workgroups per CU)", "round": R, "git": git, "kernel_source_sha256": sha,
+        doc = {"kernel": kname + " (wave-stream, 3 workgroups per CU)", "round": R, "git": git, "kernel_source_sha256": sha,
                "workload": "configs[1]: 100000 x 3 s @16 kHz, 39-d",
                "command": "tools/profile_round.sh %s pmc512  (rocprofv3 --pmc <counter group> --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --stages mfcc --no-cpu-baseline; one pass per counter group; mean over the kernel's launches of the pass)" % R,
                "raw": {k: v["mean_per_launch"] for k, v in a.items() if k.startswith(("FETCH", "WRITE", "TCC"))},
@@ -150,7 +155,7 @@ if a:
         cf = os.path.join(S, "isa_census.json")
         if os.path.exists(cf):
             census = json.load(open(cf))
-        doc = {"kernel": "ssp::mfcc_stream512_kernel<13,2,1,3,6,2,3,0,0>", "round": R, "git": git, "kernel_source_sha256": sha,
+        doc = {"kernel": kname, "round": R, "git": git, "kernel_source_sha256": sha,
                "workload": "configs[1] at FULL size: 100000 x 3 s @16 kHz per pass (7.5e6 quads of 4 frames), 39-d",
                "command": "tools/profile_round.sh %s pmc512" % R,
                "raw_per_launch": {k: v["mean_per_launch"] for k, v in a.items() if k.startswith(("SQ_", "GRBM"))},
