@@ -395,6 +395,30 @@ int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const 
                            const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
                            double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms);
 
+/* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
+ * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with
+ * the random numbers handed in.  feats: float[n_rows x D] on the side `where` names (any 4-byte alignment).  Problem p has n_sel[p] rows:
+ * sel == NULL: rows [row_off[p], row_off[p] + n_sel[p]) of feats; sel != NULL: the rows sel[row_off[p] .. row_off[p] + n_sel[p]) (HOST
+ * int64 row numbers, concatenated, sorted per problem: the subsample the caller drew) — row_off then indexes sel.  Problems may come in
+ * any order, leave gaps and overlap.  first[p]: position of the first centre among the problem's rows; u: HOST double[P x (K-1) x L]
+ * uniforms in [0, 1), L = 2 + (int)ln K candidates per step.
+ * Per problem, in float64 on the float32 rows: d2[i] = |x_i - x_first|^2; then for k = 1 .. K-1: cum = inclusive prefix sum of d2,
+ * total = cum[n-1]; cand[l] = min(n-1, #{i : cum[i] < u[k-1][l] * total}) (numpy searchsorted, side='left', and the clip);
+ * dc[i][l] = |x_i - x_cand[l]|^2; pot[l] = sum_i min(d2[i], dc[i][l]); the pick is cand[b], b the FIRST arg-min of pot;
+ * d2[i] = min(d2[i], dc[i][b]).  All rows equal (total == 0): every candidate is position 0, no error.
+ * Outputs (HOST): seed_rows_out int64[P x K]: the picks as absolute row numbers of feats; centres_out double[P x K x D]: those rows
+ * widened (NULL: not wanted).  Every sum has a fixed shape (no floating-point atomics): the same call gives the same bits every time,
+ * and a problem's picks do not depend on the other problems of the launch.
+ * SSP_ERR_INVALID, each found before any GPU work: P < 1, K < 1, a problem with n_sel < 1, a row outside [0, n_rows), first outside
+ * [0, n_sel), a u outside [0, 1) (the messages name the problem).  SSP_ERR_INVALID after the launch: a problem whose total is not finite
+ * (a NaN or infinite row; K >= 2) — the message names the first such problem, no output is written, and nothing stays behind in the ctx.
+ * SSP_ERR_UNSUPPORTED: D > 64 (a wave stages 64 rows through LDS), more than 24 candidates per step, a problem of 2^31 rows.
+ * Design point: n_sel <= ~32 k rows per problem (the subsample cap max(20000, 50 K)); larger problems are correct, still on one workgroup.
+ * Work: one upload of the draws / lists, one launch, one result copy + host wait. */
+int ssp_kmeanspp_seed(ssp_ctx* ctx, int32_t P, int32_t K, int32_t D, const float* feats, int64_t n_rows, int where,
+                      const int64_t* row_off, const int64_t* n_sel, const int64_t* sel, const int64_t* first, const double* u,
+                      int64_t* seed_rows_out, double* centres_out, float* kernel_ms);
+
 /* ---- DTW template matching: replaces the distance_dtw double loop of MFCC_DTW.py:57-108,187-217
  *      (dtw.accelerated_dtw(x, y, dist='euclidean'), warp 1) for every (query, template) pair ---- */
 /* xq: float[total query rows x dim] with q_seg row offsets; xt, t_seg likewise for the templates (dim = 1: the reference's

@@ -162,13 +162,14 @@ def load_models(model_dir="Model"):
     return gmms, ubm
 
 
-def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None):
+def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None, seeding='host'):
     """GMM_UBM.py:134-199.  ``model`` falsy (the reference's default): one ``GaussianMixture(n_components, 'diag')`` per
     speaker is fitted on ``train[speaker]`` (speakers in ascending label order, like label_encoder.values()) and the UBM
     on the stacked training data (GMM_UBM.py:154-170), EM on the GPU (the speaker models together through gmm_train.fit_many for
     n_components <= 64 and D <= 47, bit for bit the loop's models); with ``model_dir`` (the reference always uses
     "Model") the two pickles of GMM_UBM.py:173-179 are written.  ``model=True``: load those pickles from ``model_dir``
     (default "Model", GMM_UBM.py:141-146).  ``model`` = (list_of_speaker_GMMs, UBM): use them as given.
+    ``seeding``: where the k-means++ seeds of the speaker fits and the UBM fit are computed, 'host' or 'device' (gmm_train.GaussianMixture).
     Prints and returns the train/test accuracies the reference prints; the models are left in ``GMM.last_model``."""
     if model is True:
         model = load_models(model_dir or "Model")
@@ -176,12 +177,12 @@ def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, ra
         speakers = sorted(train.keys())
         D = np.asarray(train[speakers[0]]).shape[1] if speakers else 0
         if n_components <= 64 and D <= 47:  # one EM launch per iteration for all speakers; the same bits as the loop below
-            gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type='diag', random_state=random_state)
+            gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding)
         else:
-            gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state).fit(train[s])
+            gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(train[s])
                     for s in speakers]
         ubm_train = np.vstack([train[s] for s in speakers])
-        ubm = GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state).fit(ubm_train)
+        ubm = GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(ubm_train)
         model = (gmms, ubm)
         if model_dir:
             save_models(gmms, ubm, model_dir)

@@ -87,6 +87,7 @@ SIGNATURES = {
     "ssp_gmm_em_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, C.c_int, _MSP]),
     "ssp_gmm_em_stats_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, _P, _P,
                                          C.c_int, _MSP]),
+    "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),
     "ssp_dnn_destroy": (C.c_int, [_P]),

@@ -691,6 +691,65 @@ def gmm_em_stats_batch(ctx: "Context", weights, means, covars, feats, row_off, n
     return res
 
 
+KMEANSPP_MAX_D = 64  # ssp_kmeanspp_seed's feature dimension (include/ssp.h)
+
+
+def kmeanspp_candidates(K: int) -> int:
+    """candidates per k-means++ step: 2 + int(ln K) (sklearn's kmeans_plusplus; the last axis of ``u`` in kmeanspp_seeds)"""
+    return 2 + int(np.log(K))
+
+
+def kmeanspp_seeds(ctx: "Context", feats, K, first, u, row_off=None, n_sel=None, sel=None, centres=True, timing=False) -> dict:
+    """k-means++ seeds of P problems in one launch, the random numbers handed in (ssp_kmeanspp_seed).
+    feats (n_rows, D) float32, numpy or device tensor.  Problem p: rows [row_off[p], row_off[p] + n_sel[p]) of feats, or — with ``sel``, the
+    concatenated sorted row lists — the rows sel[row_off[p] : row_off[p] + n_sel[p]]; with neither, ONE problem over every row.  first
+    (P,): position of the first centre among the problem's rows; u (P, K-1, 2 + int(ln K)) uniforms in [0, 1).
+    Returns rows (P, K) int64, absolute row numbers of feats, and centres (P, K, D) float64 unless centres=False
+    [and kernel_ms when timing=True].  D > 64: NotImplementedError."""
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2:
+        raise ValueError("feats must be (rows, D)")
+    n_rows, D = int(keep.shape[0]), int(keep.shape[1])
+    K = int(K)
+    fi = np.ascontiguousarray(first, dtype=np.int64).reshape(-1)
+    P = int(fi.shape[0])
+    if row_off is None and n_sel is None:
+        if P != 1:
+            raise ValueError("row_off and n_sel are needed for more than one problem")
+        off = np.zeros(1, dtype=np.int64)
+        cnt = np.array([n_rows if sel is None else np.size(sel)], dtype=np.int64)
+    elif row_off is None or n_sel is None:
+        raise ValueError("row_off and n_sel come together")
+    else:
+        off = np.ascontiguousarray(row_off, dtype=np.int64).reshape(-1)
+        cnt = np.ascontiguousarray(n_sel, dtype=np.int64).reshape(-1)
+    if off.shape != (P,) or cnt.shape != (P,):
+        raise ValueError("row_off, n_sel and first must be (%d,)" % P)
+    L = kmeanspp_candidates(K) if K >= 1 else 2
+    uu = np.ascontiguousarray(u, dtype=np.float64)
+    if uu.size != P * max(K - 1, 0) * L:
+        raise ValueError("u must be (%d, %d, %d)" % (P, K - 1, L))
+    sl = None
+    if sel is not None:
+        sl = np.ascontiguousarray(sel, dtype=np.int64).reshape(-1)
+        if P and cnt.min(initial=1) >= 0 and off.min(initial=0) >= 0 and int((off + cnt).max(initial=0)) > sl.shape[0]:
+            raise ValueError("sel is shorter than row_off + n_sel asks for")
+    rows = np.empty((P, max(K, 0)), dtype=np.int64)
+    cen = np.empty((P, max(K, 0), D), dtype=np.float64) if centres else None
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_kmeanspp_seed(ctx._h, P, K, D, ptr, n_rows, where, off.ctypes.data, cnt.ctypes.data,
+                                              sl.ctypes.data if sl is not None else None, fi.ctypes.data, uu.ctypes.data if uu.size else None,
+                                              rows.ctypes.data, cen.ctypes.data if centres else None, C.byref(ms) if timing else None))
+    del keep
+    res = {"rows": rows}
+    if centres:
+        res["centres"] = cen
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 class GmmScorer:
     """Packed diagonal GMMs (ssp_gmm).  weights (M,K), means (M,K,D), covars (M,K,D) float64.
     has_ubm: model 0 is the UBM (GMM_UBM.py:169-170); scores/argmax are then taken against it."""

@@ -9,7 +9,8 @@ so ``GMM_UBM.score_matrix`` / ``api.GmmScorer.from_sklearn`` take them as they t
 
 Initialisation.  With ``weights_init`` / ``means_init`` / ``precisions_init`` given, the start is exactly sklearn's and
 so is every iterate (parity tests).  Otherwise ``init_params='kmeans'`` (sklearn's default too): k-means++ seeding on a
-host-side subsample (sequential sampling, as sklearn does it on the CPU), Lloyd iterations on the GPU — the E/M statistics
+subsample (sequential sampling; on the host as sklearn does it, or with ``seeding='device'`` the same draws and the same picks through
+``ssp_kmeanspp_seed`` on the GPU), Lloyd iterations on the GPU — the E/M statistics
 kernels at a small shared spherical variance are the hard-assignment limit of the same sums — and the component weights,
 means and variances of the resulting clusters as the start, like sklearn's ``_initialize_parameters``.  The random streams
 differ from sklearn's, so trained models agree in quality, not bit for bit.  ``init_params='random_from_data'``: K distinct
@@ -37,9 +38,24 @@ def _first_bad_row(X):
     return int(torch.nonzero(~torch.isfinite(X).all(dim=1))[0, 0])
 
 
+def _kmeanspp_draws(rng, n, K):
+    """Every random draw of one k-means++ seeding of n rows, in the order GaussianMixture._kmeanspp has always drawn them: the sorted
+    subsample of min(n, max(20000, 50 K)) rows (rng.choice), the position of the first centre in it (rng.randint), and the K - 1 rows of
+    2 + int(ln K) uniforms (rng.uniform) -> (idx int64, first, u (K - 1, L)).  Both seedings draw through this, so they consume a
+    RandomState identically."""
+    idx = np.sort(rng.choice(n, size=min(n, max(20000, 50 * K)), replace=False))
+    first = int(rng.randint(len(idx)))
+    L = 2 + int(np.log(K))
+    u = np.empty((K - 1, L))
+    for k in range(1, K):
+        u[k - 1] = rng.uniform(size=L)
+    return idx, first, u
+
+
 class GaussianMixture:
     def __init__(self, n_components=1, covariance_type='diag', tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1,
-                 weights_init=None, means_init=None, precisions_init=None, random_state=None, init_params='kmeans', ctx=None):
+                 weights_init=None, means_init=None, precisions_init=None, random_state=None, init_params='kmeans', ctx=None,
+                 seeding='host'):
         if covariance_type != 'diag':
             raise ValueError("only covariance_type='diag' is supported (what GMM_UBM.py:158,169 uses)")
         if n_components < 1 or max_iter < 1 or n_init < 1 or tol < 0 or reg_covar < 0:
@@ -52,6 +68,9 @@ class GaussianMixture:
         if init_params not in ('kmeans', 'random_from_data'):
             raise ValueError("init_params must be 'kmeans' or 'random_from_data'")
         self.init_params = init_params
+        if seeding not in ('host', 'device'):
+            raise ValueError("seeding must be 'host' or 'device'")
+        self.seeding = seeding
         self._ctx = ctx
 
     def __getstate__(self):  # picklable like the sklearn object it stands in for (GMM_UBM.py:173-179): no device handles
@@ -74,13 +93,14 @@ class GaussianMixture:
     def _kmeanspp(self, X, n, D, rng):
         """k-means++ seeds on <= 20000 sampled frames (host; the only random draws of the k-means start)"""
         K = self.n_components
-        sub = self._rows(X, np.sort(rng.choice(n, size=min(n, max(20000, 50 * K)), replace=False)))
+        idx, first, u = _kmeanspp_draws(rng, n, K)
+        sub = self._rows(X, idx)
         centres = np.empty((K, D))
-        centres[0] = sub[rng.randint(len(sub))]
+        centres[0] = sub[first]
         d2 = ((sub - centres[0]) ** 2).sum(1)
         sq = (sub * sub).sum(1)
         for k in range(1, K):  # D^2 sampling, best of 2 + log K candidates (sklearn's kmeans_plusplus)
-            cand = np.searchsorted(np.cumsum(d2), rng.uniform(size=2 + int(np.log(K))) * d2.sum())
+            cand = np.searchsorted(np.cumsum(d2), u[k - 1] * d2.sum())
             cand = np.clip(cand, 0, len(sub) - 1)
             # |s - c|^2 = |s|^2 + |c|^2 - 2 s.c as one small matrix product (the broadcast difference cost 0.5 s at K = 64)
             dc = np.maximum(sq[:, None] + sq[cand][None, :] - 2.0 * (sub @ sub[cand].T), 0.0)
@@ -89,6 +109,19 @@ class GaussianMixture:
             centres[k] = sub[cand[b]]
             d2 = np.minimum(d2, dc[:, b])
         return centres
+
+    def _device_seeding(self, D):
+        """seeding='device' and the kernel takes this feature dimension (otherwise: the host seeding)"""
+        return self.seeding == 'device' and D <= api.KMEANSPP_MAX_D
+
+    def _seeds(self, ctx, X, n, D, rng):
+        """the k-means++ centres of one start: on the host, or (seeding='device') the same draws through ONE ssp_kmeanspp_seed problem on
+        the device matrix X — only the K centres come back"""
+        if not self._device_seeding(D):
+            return self._kmeanspp(X, n, D, rng)
+        idx, first, u = _kmeanspp_draws(rng, n, self.n_components)
+        res = api.kmeanspp_seeds(ctx, X, self.n_components, [first], u[None], sel=idx if len(idx) < n else None)
+        return res["centres"][0]
 
     @staticmethod
     def _lloyd_start(K, D, gvar):
@@ -104,9 +137,10 @@ class GaussianMixture:
         return new, shift <= 1e-4 * float(gvar.sum())
 
     def _kmeans(self, ctx, X, n, D, rng, gvar):
-        """k-means++ seeds (host, on <= 20000 sampled frames) + Lloyd on the GPU; returns the clusters' (nk, sx, sxx)."""
+        """k-means++ seeds (on <= 20000 sampled frames; host or device, see ``seeding``) + Lloyd on the GPU; returns the clusters'
+        (nk, sx, sxx)."""
         K = self.n_components
-        centres = self._kmeanspp(X, n, D, rng)
+        centres = self._seeds(ctx, X, n, D, rng)
         w, tau = self._lloyd_start(K, D, gvar)
         st = None
         for _ in range(30):
@@ -269,11 +303,13 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
 
     ``kwargs`` are the constructor's; ``weights_init`` / ``means_init`` / ``precisions_init`` may be one array or a sequence of M.
     The features go to the device once.  Every stage is batched over the models (and ``n_init`` starts) still active: the global
-    variance pass, Lloyd with per-model stop tests, EM with per-model convergence and best-start selection.  k-means++ seeding stays on
-    the host: an int or None ``random_state`` gives every model its own RandomState (as a loop of ``fit`` does; the seeding then runs in
-    a thread pool), a shared RandomState instance is drawn from in model order, as the loop draws.  For K <= 64, D <= 47 the fitted
+    variance pass, Lloyd with per-model stop tests, EM with per-model convergence and best-start selection.  k-means++ seeding runs on
+    the host by default: an int or None ``random_state`` gives every model its own RandomState (as a loop of ``fit`` does; the seeding then
+    runs in a thread pool), a shared RandomState instance is drawn from in model order, as the loop draws.  ``seeding='device'``: the same
+    draws, then ONE ssp_kmeanspp_seed call for every (model, start) on the uploaded matrix (D <= 64; above that the host seeding).  For K <= 64, D <= 47 the fitted
     attributes are bit for bit those of ``GaussianMixture(**kwargs).fit(X)`` per model.  D > 47: the loop of ``fit``.
-    ``profile``: a dict that receives the time split (kernel ms, host M step, k-means++ seconds; measurement only)."""
+    ``profile``: a dict that receives the time split (kernel ms, host M step, k-means++ seconds and — device seeding — its kernel ms;
+    measurement only)."""
     import time
     Xs = list(Xs)
     M = len(Xs)
@@ -312,7 +348,7 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
         m = int(np.searchsorted(offs, bad, side="right")) - 1
         raise ValueError(_nonfinite_message(" of model %d" % m, bad - int(offs[m])))
     prof = profile if profile is not None else {}
-    for k in ("kernel_ms", "mstep_s", "kmeanspp_s", "calls", "em_iters"):
+    for k in ("kernel_ms", "mstep_s", "kmeanspp_s", "kmeanspp_kernel_ms", "calls", "em_iters"):
         prof.setdefault(k, 0.0)
     timing = profile is not None
 
@@ -335,6 +371,8 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
     items = [(m, r) for m in range(M) for r in range(gms[m].n_init)]
     seeds = {}
 
+    device = g0._device_seeding(D)
+
     def draw(m):
         gm, X, n = gms[m], hosts[m], int(ns[m])
         rs = gm.random_state
@@ -343,7 +381,7 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
         for _ in range(gm.n_init):
             centres = drawn = None
             if gm._need_start() and gm.init_params == 'kmeans' and K > 1:
-                centres = gm._kmeanspp(X, n, D, rng)
+                centres = _kmeanspp_draws(rng, n, K) if device else gm._kmeanspp(X, n, D, rng)
             if gm.means_init is None and centres is None and K != 1:
                 drawn = gm._rows(X, np.sort(rng.choice(n, size=K, replace=False)))
             out.append((centres, drawn))
@@ -351,16 +389,31 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
 
     t0 = time.perf_counter()
     shared = any(isinstance(gm.random_state, np.random.RandomState) for gm in gms)
-    if shared or M == 1:
+    if shared or M == 1 or device:
         drawn_all = [draw(m) for m in range(M)]
     else:
         import os
         from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, M))) as ex:
             drawn_all = list(ex.map(draw, range(M)))
-    prof["kmeanspp_s"] += time.perf_counter() - t0
     for m, r in items:
         seeds[(m, r)] = drawn_all[m][r]
+    if device:  # ONE ssp_kmeanspp_seed call for every (model, start) on the matrix already uploaded; only the centres come back
+        todo = [it for it in items if seeds[it][0] is not None]
+        if todo:
+            whole = all(len(seeds[it][0][0]) == int(ns[it[0]]) for it in todo)  # no model above the subsample cap: row ranges
+            cnt = np.array([len(seeds[it][0][0]) for it in todo], dtype=np.int64)
+            if whole:
+                sel, off = None, offs[[m for m, _r in todo]]
+            else:
+                sel = np.concatenate([seeds[it][0][0] + offs[it[0]] for it in todo])
+                off = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int64)
+            res = api.kmeanspp_seeds(ctx, feats, K, [seeds[it][0][1] for it in todo], np.stack([seeds[it][0][2] for it in todo]),
+                                     row_off=off, n_sel=cnt, sel=sel, timing=timing)
+            prof["kmeanspp_kernel_ms"] += res.get("kernel_ms", 0.0)
+            for i, it in enumerate(todo):
+                seeds[it] = (res["centres"][i], seeds[it][1])
+    prof["kmeanspp_s"] += time.perf_counter() - t0
     # ---- Lloyd on every k-means start at once, each with its own stop test
     lloyd = {it: None for it in items if seeds[it][0] is not None}
     cen = {it: seeds[it][0] for it in lloyd}
