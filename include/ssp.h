@@ -296,7 +296,11 @@ int ssp_vad_sweep(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy,
 /* ---- GMM-UBM scoring: replaces the GMM[i].score(x_j) - UBM.score(x_j) double loop
  *      (GMM_UBM.py:181-197) and sklearn GaussianMixture.score_samples/score for diag models ---- */
 /* weights: HOST double[n_models x K]; means, covars: HOST double[n_models x K x D].
- * has_ubm != 0: model 0 is the UBM; argmax/score differences are taken over models 1.. */
+ * has_ubm != 0: model 0 is the UBM; argmax/score differences are taken over models 1..
+ * Weights: every weight is finite and >= 0 and no model's weights are all zero; anything else (a negative, NaN or infinite weight, an
+ * all-zero model) and a covariance that is not > 0 answer SSP_ERR_INVALID before anything is uploaded (the message names the model).  A
+ * mixture of weight 0 does not exist, as in sklearn (log 0 = -inf inside the log-sum-exp): it is packed like a padded mixture and the
+ * model's log-likelihoods are those of its other mixtures, at every precision. */
 int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const double* weights,
                  const double* means, const double* covars, int32_t has_ubm, ssp_gmm** out);
 int ssp_gmm_destroy(ssp_gmm* gmm);
@@ -318,6 +322,10 @@ int ssp_gmm_destroy(ssp_gmm* gmm);
  *  the UBM — are scored again in fp32 and only THEIR entries of its scores_out row are replaced; the row's other entries keep their
  *  bf16x3 values (within the band of the fp32 path's).  The arg-max is the fp32 path's in every case.  A re-scoring pass too large for
  *  one launch scores every model and replaces the whole row.)
+ * What precision 0 delivers: a mixture's exponent is evaluated EXPANDED, [x, x^2, 1] . W in fp32, so its error follows the size of the
+ * expansion's terms (about D (|mu| / sigma)^2 per mixture), not the size of the result: at |mu| / sigma <= 1 the per-frame error is some
+ * 1e-5 nats, on un-centred features it grows with (|mu| / sigma)^2 (measured per |mu| / sigma in profiles/gmm_accuracy.md) — a caller
+ * whose features carry a large common offset subtracts it from the features and the means first (the model is translation invariant).
  * Without loglik_out the per-utterance means are formed inside the scoring kernel (the [n_models x frames] matrix never exists).  With
  * loglik_out the matrix is scored in ONE pass at the asked precision and scores_out / argmax_out are its per-utterance means: nothing is
  * listed or scored twice and there is no host wait at any precision (precision 1 / 3 then answer as 2, ssp_gmm_last_rescored is 0).

@@ -832,6 +832,18 @@ int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const dou
     if (has_ubm && n_models < 2) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_pack: has_ubm needs at least one speaker model");
     const int nq = pick_nq(D);
     if (nq < 0) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_pack: D=%d exceeds the supported feature dimension (127)", D);
+    // weights: >= 0 and not all zero per model.  A zero weight is a mixture that does not exist (sklearn: log 0 = -inf inside the
+    // log-sum-exp) and is packed like a padded one, with the finite constant -1e30: a -inf constant meets -inf - (-inf) in lse2_update
+    // when a lane's 16 rows of a model's first tile are all -inf
+    for (int m = 0; m < n_models; ++m) {
+        bool any = false;
+        for (int k = 0; k < K; ++k) {
+            const double wk = weights[(size_t)m * K + k];
+            if (!(wk >= 0.0) || std::isinf(wk)) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_pack: negative or non-finite weight (model %d, mix %d)", m, k);
+            any |= wk > 0.0;
+        }
+        if (!any) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_pack: every weight of model %d is zero", m);
+    }
     const int tpm = (K + 31) / 32;
     const size_t tile_floats = (size_t)nq * 2 * 32 * 4;
     const size_t n_tiles = (size_t)n_models * tpm;
@@ -854,7 +866,7 @@ int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const dou
                     w[D + d] = -0.5 * P * LOG2E;
                     c += 0.5 * std::log(P) - 0.5 * mu[d] * mu[d] * P;
                 }
-                w[2 * D] = c * LOG2E;
+                w[2 * D] = wk > 0.0 ? c * LOG2E : -1.0e30;  // (zero weight: as a padded mixture)
             } else {
                 w[2 * D] = -1.0e30;  // padded mixture: contributes exp(-1e30 - max) = 0 to the LSE
             }
@@ -906,7 +918,7 @@ int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const dou
                         wv[D + d] = -0.5 * P * LOG2E;
                         cst += 0.5 * std::log(P) - 0.5 * mu[d] * mu[d] * P;
                     }
-                    cst *= LOG2E;
+                    cst = weights[(size_t)m * K + k] > 0.0 ? cst * LOG2E : -1.0e30;
                 }
                 for (int j = 0; j < nk16 * 16; ++j) {
                     const int ks = j >> 4, hh = (j >> 3) & 1, e = j & 7;
