@@ -58,6 +58,7 @@ typedef struct ssp_ctx ssp_ctx;
 typedef struct ssp_segments ssp_segments;
 typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
+typedef struct ssp_gmm_map ssp_gmm_map;
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
@@ -402,6 +403,56 @@ int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, 
 int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
                            const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
                            double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms);
+
+/* The same statistics of M row ranges under ONE shared model: what MAP adaptation of a universal background model needs per speaker
+ * (Reynolds, Quatieri, Dunn 2000).  An EXTENSION: the reference trains every speaker's mixture independently (GMM_UBM.py:158-170) and
+ * has no adaptation step.  HOST double weights[K], means[K x D], covars[K x D]: one parameter block, packed and uploaded once and read by
+ * every range (the batched kernels with a parameter stride of 0).  Everything else as ssp_gmm_em_stats_batch: feats, row_off, n_frames,
+ * the outputs nk_out[M x K], sx_out / sxx_out[M x K x D], loglik_sum_out[M], the error codes and the non-finite-row rules.
+ * Contract.  Every output is BIT-IDENTICAL to ssp_gmm_em_stats_batch called with the parameters repeated M times, for K <= 64 and
+ * K > 64 alike (same kernels, same partition, same reduction order). */
+int ssp_gmm_em_stats_shared(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                            const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
+                            double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms);
+
+/* ---- Top-C fast scoring of mean-adapted GMM-UBM speaker models (GMM_UBM.py:158-170,181-197 are what it stands beside).  An EXTENSION
+ *      the reference does not have: its models are trained independently and its scoring loops evaluate every mixture of every one.
+ *      For speaker models that share the UBM's weights and covariances and differ in their means (MAP adaptation of the means), the
+ *      quantity of GMM_UBM.py:185, GMM[i].score(x) - UBM.score(x), is evaluated over the UBM's best C mixtures of every frame only. ----
+ * Definition (quantities as sklearn mixture/_gaussian_mixture.py:453-512 defines them).  lp_k(x): the UBM's weighted log-probability of
+ * mixture k at frame x.  T(x): the C mixtures of largest lp_k(x); of equal values the lower index ranks first.  For speaker s with means
+ * mu_s: delta_{s,k}(x) = x . a_{s,k} - b_{s,k},  a_{s,k} = (mu_{s,k} - mu_k) P_k,  b_{s,k} = 1/2 sum_d (mu_{s,k,d}^2 - mu_{k,d}^2) P_{k,d}
+ * (P = 1 / covariance; formed in float64 on the host, rounded to fp32).  L_ubm(x) = logsumexp_{k in T(x)} lp_k(x),
+ * L_s(x) = logsumexp_{k in T(x)} (lp_k(x) + delta_{s,k}(x)).  Per utterance u:  diff[u][s] = mean_t (L_s(x_t) - L_ubm(x_t)),
+ * ubm[u] = mean_t L_ubm(x_t).  With C = K (no zero weights) diff is the dense score difference exactly; the common part lp_k enters
+ * only as the posterior of k within T(x), so its rounding error largely cancels.
+ * ssp_gmm_map_pack: HOST double ubm_weights[K], ubm_means[K x D], ubm_covars[K x D], spk_means[S x K x D].  Validation as
+ * ssp_gmm_pack: weights finite and >= 0 and not all zero, covariances > 0, else SSP_ERR_INVALID before anything is uploaded; a mixture
+ * of weight 0 does not exist and is never selected.  SSP_ERR_INVALID: S < 1, K < 1, D < 1.  SSP_ERR_UNSUPPORTED: D > 47 (the selection
+ * kernel's MFMA tiling, as ssp_gmm_em_stats_batch), a K whose bucket table outgrows the LDS.
+ * ssp_gmm_map_score: feats float[total frames x D] (any 4-byte alignment) and frame_seg as ssp_gmm_score.  C: mixtures kept per frame.
+ * Outputs (each nullable, on the side `where` names): diff_out float[n_utt x S]; ubm_out float[n_utt]; argmax_out int32[n_utt], the
+ * FIRST index of the row's maximum (numpy.argmax); idx_out int32[total frames x C], T(x) of every frame in rank order.
+ * SSP_ERR_INVALID, each found before any GPU work: C < 1, C larger than the number of non-zero-weight mixtures.  SSP_ERR_UNSUPPORTED:
+ * C > 8.  The handle and its ctx stay usable after either.
+ * Non-finite rows, as ssp_gmm_score states them: a BAD frame (a NaN or +-inf entry) makes its utterance's diff_out row and ubm_out NaN
+ * and its argmax_out 0; its idx_out row is -1.  An empty utterance (T = 0) has the same NaN row, NaN ubm_out and arg-max 0.  Every other
+ * utterance is BIT-IDENTICAL to the same call with the bad entries replaced by finite ones.  No error is reported; the Python layer
+ * raises ValueError.
+ * Deterministic: no floating-point atomics, every sum has a fixed shape, the same call gives the same bits every time, and an
+ * utterance's results do not depend on the other utterances of the batch.  Stream-ordered: with device pointers the call queues its
+ * kernels on the ctx stream and returns without a host wait; where = SSP_HOST stages the features whole and waits for the results.
+ * Accuracy: lp_k is evaluated expanded in fp32 as ssp_gmm_score's precision 0 does (some 1e-5 nats per frame at |mu| / sigma <= 1):
+ * two mixtures whose lp differ by less than that may swap ranks at the edge of T(x).
+ * ssp_gmm_map_score_list: the same on a LIST of per-utterance matrices, gathered as ssp_gmm_score_list gathers them (rows, row_type, dim
+ * and frame_seg as there; outputs HOST). */
+int ssp_gmm_map_pack(ssp_ctx* ctx, int32_t K, int32_t D, const double* ubm_weights, const double* ubm_means, const double* ubm_covars,
+                     int32_t S, const double* spk_means, ssp_gmm_map** out);
+int ssp_gmm_map_destroy(ssp_gmm_map* map);
+int ssp_gmm_map_score(ssp_gmm_map* map, const float* feats, const ssp_segments* frame_seg, int32_t C, float* diff_out, float* ubm_out,
+                      int32_t* argmax_out, int32_t* idx_out, int where, float* kernel_ms);
+int ssp_gmm_map_score_list(ssp_gmm_map* map, const void* const* rows, int row_type, int32_t dim, const ssp_segments* frame_seg, int32_t C,
+                           float* diff_out, float* ubm_out, int32_t* argmax_out, int32_t* idx_out, float* kernel_ms);
 
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with

@@ -17,7 +17,7 @@ import pickle as pkl
 import numpy as np
 
 from . import api, frontend
-from .gmm_train import GaussianMixture, fit_many
+from .gmm_train import GaussianMixture, fit_many, map_adapt
 from .sidekit_features import mfcc, mfcc_batch, plp, plp_batch, plp_features_batch  # noqa: F401  (GMM_UBM.py:20 imports both names)
 
 
@@ -111,8 +111,11 @@ def identify_language(models, ubm, features, names=('Chinese', 'English', 'Japan
     return out, prob, pred
 
 
-def score_matrix(models, ubm, feats):
+def score_matrix(models, ubm, feats, top_c=None):
     """GMM_UBM.py:181-187 as a function: pred[j, i] = models[i].score(feats[j]) - ubm.score(feats[j]).
+    ``top_c`` (an extension; None: the dense path below, unchanged): an int evaluates the same difference over the UBM's best top_c
+    mixtures of every frame (api.MapScorer; the models must be mean-adapted from ``ubm``, gmm_train.map_adapt(adapt='m')) — same shapes,
+    same ValueError; with top_c = n_components it is the dense difference.
 
     models / ubm: fitted sklearn GaussianMixture(covariance_type='diag') objects (or anything with weights_,
     means_, covariances_).  feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64).
@@ -120,6 +123,17 @@ def score_matrix(models, ubm, feats):
     utterance with a NaN row — include/ssp.h, ssp_gmm_score — so this is read off the scores: no pass over the host arrays).  An empty
     utterance keeps its NaN row."""
     ctx = api.default_context()
+    if top_c is not None:
+        scorer = api.MapScorer.from_sklearn(ctx, models, ubm)
+        r = scorer.score_list(feats, top_c=int(top_c))
+        scorer.close()
+        pred = np.asarray(r["diff"], dtype=np.float64)
+        lens = np.array([np.shape(f)[0] for f in feats], dtype=np.int64)
+        bad = np.flatnonzero(~np.isfinite(pred).all(axis=1) & (lens > 0))
+        if bad.size:
+            raise ValueError("Input contains NaN, infinity or a value too large for float32: utterance %d%s"
+                             % (int(bad[0]), "" if bad.size == 1 else " (and %d more)" % (bad.size - 1)))
+        return pred, np.asarray(r["argmax"]).astype(np.int64)
     scorer = api.GmmScorer.from_sklearn(ctx, models, ubm)
     r = scorer.score_list(feats)   # (the rows are gathered and narrowed by the library: no vstack + astype here)
     sc = np.asarray(r["scores"], dtype=np.float64)
@@ -162,7 +176,8 @@ def load_models(model_dir="Model"):
     return gmms, ubm
 
 
-def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None, seeding='host'):
+def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None, seeding='host',
+        adapt=None, relevance_factor=16.0, top_c=None):
     """GMM_UBM.py:134-199.  ``model`` falsy (the reference's default): one ``GaussianMixture(n_components, 'diag')`` per
     speaker is fitted on ``train[speaker]`` (speakers in ascending label order, like label_encoder.values()) and the UBM
     on the stacked training data (GMM_UBM.py:154-170), EM on the GPU (the speaker models together through gmm_train.fit_many for
@@ -170,27 +185,38 @@ def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, ra
     "Model") the two pickles of GMM_UBM.py:173-179 are written.  ``model=True``: load those pickles from ``model_dir``
     (default "Model", GMM_UBM.py:141-146).  ``model`` = (list_of_speaker_GMMs, UBM): use them as given.
     ``seeding``: where the k-means++ seeds of the speaker fits and the UBM fit are computed, 'host' or 'device' (gmm_train.GaussianMixture).
+    ``adapt`` (an extension; None: the reference's independent fits, unchanged): 'map' trains the UBM on the pooled data exactly as
+    above and derives every speaker model from it by MAP adaptation of the means (gmm_train.map_adapt, ``relevance_factor``) instead of
+    the per-speaker fits.  ``top_c`` (None: dense scoring, unchanged): an int scores through the top-C scorer (score_matrix; needs
+    mean-adapted models).
     Prints and returns the train/test accuracies the reference prints; the models are left in ``GMM.last_model``."""
     if model is True:
         model = load_models(model_dir or "Model")
     elif not model:
         speakers = sorted(train.keys())
         D = np.asarray(train[speakers[0]]).shape[1] if speakers else 0
-        if n_components <= 64 and D <= 47:  # one EM launch per iteration for all speakers; the same bits as the loop below
+        if adapt not in (None, 'map'):
+            raise ValueError("adapt must be None or 'map'")
+        if adapt == 'map':
+            gmms = None  # (from the UBM, below)
+        elif n_components <= 64 and D <= 47:  # one EM launch per iteration for all speakers; the same bits as the loop below
             gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding)
         else:
             gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(train[s])
                     for s in speakers]
         ubm_train = np.vstack([train[s] for s in speakers])
         ubm = GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(ubm_train)
+        if adapt == 'map':
+            gmms = map_adapt(ubm, [train[s] for s in speakers], relevance_factor=relevance_factor, adapt='m')
         model = (gmms, ubm)
         if model_dir:
             save_models(gmms, ubm, model_dir)
     gmms, ubm = model
     GMM.last_model = model
-    valid = score_matrix(gmms, ubm, x_train)[1]
+    kw = {} if top_c is None else {"top_c": top_c}
+    valid = score_matrix(gmms, ubm, x_train, **kw)[1]
     acc_train = (valid == np.array(y_train)).sum() / len(x_train)
-    pred = score_matrix(gmms, ubm, x_test)[1]
+    pred = score_matrix(gmms, ubm, x_test, **kw)[1]
     acc = (pred == np.array(y_test)).sum() / len(x_test)
     print("train acc {:.2%}, test acc {:.2%}".format(acc_train, acc))
     return acc_train, acc

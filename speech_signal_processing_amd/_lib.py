@@ -87,6 +87,12 @@ SIGNATURES = {
     "ssp_gmm_em_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, C.c_int, _MSP]),
     "ssp_gmm_em_stats_batch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, _P, _P,
                                          C.c_int, _MSP]),
+    "ssp_gmm_em_stats_shared": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, _P, _P,
+                                          C.c_int, _MSP]),
+    "ssp_gmm_map_pack": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.POINTER(_P)]),
+    "ssp_gmm_map_destroy": (C.c_int, [_P]),
+    "ssp_gmm_map_score": (C.c_int, [_P, _F32P, _P, C.c_int32, _F32P, _F32P, _P, _P, C.c_int, _MSP]),
+    "ssp_gmm_map_score_list": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int32, _F32P, _F32P, _P, _P, _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

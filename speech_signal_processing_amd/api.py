@@ -691,6 +691,39 @@ def gmm_em_stats_batch(ctx: "Context", weights, means, covars, feats, row_off, n
     return res
 
 
+def gmm_em_stats_shared(ctx: "Context", weights, means, covars, feats, row_off, n_frames, timing: bool = False) -> dict:
+    """The statistics of M row ranges of feats under ONE model (ssp_gmm_em_stats_shared): what MAP adaptation of a UBM needs per speaker.
+    weights (K,), means (K,D), covars (K,D) float64 — packed and uploaded once; feats, row_off, n_frames and the result as
+    gmm_em_stats_batch, whose bits (called with the parameters repeated M times) these are.  D > 47: NotImplementedError."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    mu = np.ascontiguousarray(means, dtype=np.float64)
+    cv = np.ascontiguousarray(covars, dtype=np.float64)
+    if w.ndim != 1 or mu.ndim != 2 or mu.shape != cv.shape or mu.shape[0] != w.shape[0]:
+        raise ValueError("expected weights (K,), means (K,D), covars (K,D)")
+    K, D = mu.shape
+    off = np.ascontiguousarray(row_off, dtype=np.int64)
+    cnt = np.ascontiguousarray(n_frames, dtype=np.int64)
+    if off.ndim != 1 or off.shape != cnt.shape:
+        raise ValueError("row_off and n_frames must be (M,)")
+    M = int(off.shape[0])
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2 or keep.shape[1] != D:
+        raise ValueError("feats must be (frames, %d)" % D)
+    nk = np.empty((M, K), dtype=np.float64)
+    sx = np.empty((M, K, D), dtype=np.float64)
+    sxx = np.empty((M, K, D), dtype=np.float64)
+    ll = np.empty(M, dtype=np.float64)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_gmm_em_stats_shared(ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
+                                                     off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
+                                                     ll.ctypes.data, where, C.byref(ms) if timing else None))
+    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll}
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 KMEANSPP_MAX_D = 64  # ssp_kmeanspp_seed's feature dimension (include/ssp.h)
 
 
@@ -860,6 +893,112 @@ class GmmScorer:
     def close(self):
         if getattr(self, "_h", None):
             self._lib.ssp_gmm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MAP_MAX_C = 8   # ssp_gmm_map_score's largest top-C (include/ssp.h)
+MAP_MAX_D = 47  # ... and feature dimension
+
+
+class MapScorer:
+    """Top-C fast scorer of mean-adapted GMM-UBM speaker models (ssp_gmm_map; an extension the reference does not have).
+    ubm_w (K,), ubm_mu (K,D), ubm_cv (K,D), spk_means (S,K,D) float64: speaker s is the UBM with its means replaced by spk_means[s].
+    Per utterance: diff[u, s] = mean_t (L_s(x_t) - L_ubm(x_t)) over the UBM's best ``top_c`` mixtures of every frame — with top_c = K the
+    dense models[s].score(x) - ubm.score(x) of GMM_UBM.py:185."""
+
+    def __init__(self, ctx: Context, ubm_w, ubm_mu, ubm_cv, spk_means):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        w = np.ascontiguousarray(ubm_w, dtype=np.float64)
+        mu = np.ascontiguousarray(ubm_mu, dtype=np.float64)
+        cv = np.ascontiguousarray(ubm_cv, dtype=np.float64)
+        sm = np.ascontiguousarray(spk_means, dtype=np.float64)
+        if w.ndim != 1 or mu.ndim != 2 or mu.shape != cv.shape or mu.shape[0] != w.shape[0] or sm.ndim != 3 or sm.shape[1:] != mu.shape:
+            raise ValueError("expected ubm_w (K,), ubm_mu (K,D), ubm_cv (K,D), spk_means (S,K,D)")
+        self.K, self.D = mu.shape
+        self.S = int(sm.shape[0])
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_gmm_map_pack(ctx._h, self.K, self.D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, self.S, sm.ctypes.data,
+                                               C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_sklearn(cls, ctx: Context, models: Sequence, ubm) -> "MapScorer":
+        """models: mean-adapted speaker models (gmm_train.map_adapt(ubm, Xs, adapt='m')), ubm: the fitted UBM they were adapted from.
+        ValueError naming the first model whose weights_ or covariances_ are not element for element the UBM's."""
+        uw, ucv = np.asarray(ubm.weights_), np.asarray(ubm.covariances_)
+        for i, g in enumerate(models):
+            if getattr(g, "covariance_type", "diag") != "diag":
+                raise ValueError("only covariance_type='diag' models are supported")
+            for name, ref in (("weights_", uw), ("covariances_", ucv)):
+                v = np.asarray(getattr(g, name))
+                if v.shape != ref.shape or not np.array_equal(v, ref):
+                    raise ValueError("model %d: %s differ from the UBM's: the top-C scorer takes mean-adapted models only "
+                                     "(map_adapt(..., adapt='m'))" % (i, name))
+        return cls(ctx, uw, ubm.means_, ucv, np.stack([g.means_ for g in models]))
+
+    def score(self, feats, frame_seg: Segments, top_c: int = 5, diff: bool = True, ubm: bool = False, argmax: bool = True, idx: bool = False,
+              timing: bool = False) -> dict:
+        """Returns a dict with the requested arrays: diff (U, S) float32, ubm (U,) float32 = mean_t L_ubm, argmax (U,) int32 (first index
+        of the row's maximum), idx (F, top_c) int32: the selected mixtures of every frame in rank order (-1: a non-finite frame).  A
+        non-finite frame or an empty utterance: a NaN diff row, NaN ubm, arg-max 0 (include/ssp.h, ssp_gmm_map_score)."""
+        keep, ptr, where = _as_f32(feats, "feats")
+        if keep.ndim != 2 or keep.shape[1] != self.D:
+            raise ValueError("feats must be (frames, %d)" % self.D)
+        if keep.shape[0] < frame_seg.total:
+            raise ValueError("feats has fewer rows than the frame segments cover")
+        F, U, Ck = frame_seg.total, frame_seg.n, int(top_c)
+        df = self.ctx._empty((U, self.S), where) if diff else None
+        ub = self.ctx._empty((U,), where) if ubm else None
+        am = self.ctx._empty((U,), where, "int32") if argmax else None
+        ix = self.ctx._empty((F, max(Ck, 0)), where, "int32") if idx else None
+
+        def p(x):
+            if x is None:
+                return None
+            return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_gmm_map_score(self._h, ptr, frame_seg._h, Ck, p(df), p(ub), p(am), p(ix), where,
+                                                    C.byref(ms) if timing else None))
+        res = {}
+        for name, v in (("diff", df), ("ubm", ub), ("argmax", am), ("idx", ix)):
+            if v is not None:
+                res[name] = v
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def score_list(self, feats_list, top_c: int = 5, timing: bool = False) -> dict:
+        """score() on a list of (T_j, D) feature matrices without stacking them on the host (ssp_gmm_map_score_list: GmmScorer.score_list's
+        gather): the bits of score(np.vstack(feats_list).astype(float32), ...).  Returns diff (U, S), ubm (U,), argmax (U,)."""
+        table, keep, typ = list_table(feats_list, "rows")
+        for a in keep:
+            if a.ndim != 2 or a.shape[1] != self.D:
+                raise ValueError("every feature matrix must be (frames, %d)" % self.D)
+        fseg = Segments.from_lengths(self.ctx, [a.shape[0] for a in keep])
+        df = np.empty((fseg.n, self.S), dtype=np.float32)
+        ub = np.empty((fseg.n,), dtype=np.float32)
+        am = np.empty((fseg.n,), dtype=np.int32)
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(_lib.HOST):
+            _lib.check(self._lib.ssp_gmm_map_score_list(self._h, table.ctypes.data if table.size else None, typ, self.D, fseg._h, int(top_c),
+                                                         df.ctypes.data, ub.ctypes.data, am.ctypes.data, None, C.byref(ms) if timing else None))
+        del keep
+        res = {"diff": df, "ubm": ub, "argmax": am}
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_gmm_map_destroy(self._h)
             self._h = None
 
     def __del__(self):

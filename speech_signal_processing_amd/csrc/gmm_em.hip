@@ -389,13 +389,14 @@ struct EmModel {
 
 struct EmBatchArgs {
     const float* x;         // [n_rows x D]
-    const float* par;       // [M][Kp][2D+1]
+    const float* par;       // [M][Kp][2D+1]  (shared form: ONE block [Kp][2D+1], par_stride 0)
     float* lse;             // [sum of n]  (K > 64)
     float* lse_part;        // [sum of the models' lse partials]
     float* part;            // the launch group's wave partials
     const EmModel* models;  // [M]
     const int2* work;       // per workgroup: (model, walker g) for the accumulation kernel, (model, tile) for the lse kernel
     int32_t D, K, Kp;
+    int64_t par_stride;     // floats between two models' parameter blocks: Kp (2D+1), or 0 when every model reads the same block
 };
 
 __device__ __forceinline__ int em_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -412,7 +413,7 @@ __device__ __forceinline__ EmArgs em_seg_args(const EmBatchArgs& b, int m) {
     EmArgs a;
     const int D = b.D;
     a.x = b.x + em_uniform64(md.x_off) * D;
-    a.par = b.par + (size_t)m * b.Kp * (2 * D + 1);
+    a.par = b.par + (size_t)m * b.par_stride;
     a.lse = b.lse + em_uniform64(md.lse_off);
     a.lse_part = b.lse_part + em_uniform64(md.lsep_off);
     a.part = b.part + em_uniform64(md.part_off);
@@ -535,7 +536,8 @@ using namespace ssp;
 
 // float64 parameters of one model -> the fp32 rows [Kp][2D+1] the EM kernels read (A = mu P, B = -P/2, c; padded rows c = -1e30).
 // par must be zeroed.  model >= 0: a batched call's model index, named in the messages.
-static int em_pack(int K, int D, int Kp, const double* weights, const double* means, const double* covars, float* par, int model) {
+static int em_pack(int K, int D, int Kp, const double* weights, const double* means, const double* covars, float* par, int model,
+                   const char* fn = "ssp_gmm_em_stats_batch") {
     const int W = 2 * D + 1;
     const double ln2pi = std::log(2.0 * M_PI);
     for (int k = 0; k < Kp; ++k) {
@@ -546,14 +548,14 @@ static int em_pack(int K, int D, int Kp, const double* weights, const double* me
         }
         if (!(weights[k] > 0.0)) {
             if (model < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive weight (mix %d)", k);
-            SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: non-positive weight (model %d, mix %d)", model, k);
+            SSP_FAIL(SSP_ERR_INVALID, "%s: non-positive weight (model %d, mix %d)", fn, model, k);
         }
         double c = std::log(weights[k]) - 0.5 * D * ln2pi;
         for (int d = 0; d < D; ++d) {
             const double cv = covars[(size_t)k * D + d], mu = means[(size_t)k * D + d];
             if (!(cv > 0.0)) {
                 if (model < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: non-positive covariance (mix %d)", k);
-                SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: non-positive covariance (model %d, mix %d)", model, k);
+                SSP_FAIL(SSP_ERR_INVALID, "%s: non-positive covariance (model %d, mix %d)", fn, model, k);
             }
             const double P = 1.0 / cv;
             w[d] = (float)(mu * P);
@@ -684,32 +686,36 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     return SSP_OK;
 }
 
-extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
-                                      const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off,
-                                      const int64_t* n_frames, double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out,
-                                      int where, float* kernel_ms) {
-    ssp::TraceRange trace_("ssp_gmm_em_stats_batch");
+// ssp_gmm_em_stats_batch and (shared) ssp_gmm_em_stats_shared: the second packs and uploads ONE parameter block that every model reads
+// (parameter stride 0); partition, kernels, launch groups and reduction are the same code, so its outputs are the bits of the first
+// called with the block repeated M times.  fn: the entry point's name for the messages.
+static int em_stats_batch_impl(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                               const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
+                               double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms,
+                               bool shared, const char* fn) {
+    ssp::TraceRange trace_(fn);
     SSP_TRY(use_ctx(ctx));
     if (kernel_ms) *kernel_ms = 0.f;
     if (M < 1 || K < 1 || D < 1 || !weights || !means || !covars || !row_off || !n_frames || !nk_out || !sx_out || !sxx_out ||
         !loglik_sum_out)
-        SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: bad shape or null array");
+        SSP_FAIL(SSP_ERR_INVALID, "%s: bad shape or null array", fn);
     const int W = 2 * D + 1, nct = (W + 31) / 32;
-    if (nct > 3) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: D=%d exceeds the batched path's feature dimension (47)", D);
-    if (n_rows < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: no frames");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: where");
+    if (nct > 3) SSP_FAIL(SSP_ERR_UNSUPPORTED, "%s: D=%d exceeds the batched path's feature dimension (47)", fn, D);
+    if (n_rows < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "%s: no frames", fn);
+    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", fn);
     for (int m = 0; m < M; ++m) {
-        if (n_frames[m] < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: model %d has no frames", m);
+        if (n_frames[m] < 1) SSP_FAIL(SSP_ERR_INVALID, "%s: model %d has no frames", fn, m);
         if (row_off[m] < 0 || row_off[m] > n_rows - n_frames[m])
-            SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats_batch: model %d: rows [%lld, %lld) outside the %lld feature rows", m,
+            SSP_FAIL(SSP_ERR_INVALID, "%s: model %d: rows [%lld, %lld) outside the %lld feature rows", fn, m,
                      (long long)row_off[m], (long long)(row_off[m] + n_frames[m]), (long long)n_rows);
     }
     const int Kp = (K + EM_KC - 1) / EM_KC * EM_KC, chunks = Kp / EM_KC;
     const bool fuse = chunks == 1;  // K <= 64: the fused kernel, bit-identical to ssp_gmm_em_stats per model
     const int64_t cols = (int64_t)Kp * W;
-    std::vector<float> par((size_t)M * Kp * W, 0.f);
-    for (int m = 0; m < M; ++m)
-        SSP_TRY(em_pack(K, D, Kp, weights + (size_t)m * K, means + (size_t)m * K * D, covars + (size_t)m * K * D, par.data() + (size_t)m * Kp * W, m));
+    const int n_par = shared ? 1 : M;  // parameter blocks packed and uploaded
+    std::vector<float> par((size_t)n_par * Kp * W, 0.f);
+    for (int m = 0; m < n_par; ++m)
+        SSP_TRY(em_pack(K, D, Kp, weights + (size_t)m * K, means + (size_t)m * K * D, covars + (size_t)m * K * D, par.data() + (size_t)m * Kp * W, m, fn));
     // partition: K <= 64 as the single call (G = min(tiles, 2 CUs' worth)); K > 64: G capped so that G x chunks <= 2 x num_cu
     // workgroups per model (bounded partials: 4 G Kp (2D+1) floats)
     const int64_t gcap = fuse ? 2 * (int64_t)ctx->num_cu : std::max<int64_t>(1, 2 * (int64_t)ctx->num_cu / chunks);
@@ -725,7 +731,7 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
     int64_t lse_tot = 0, lsep_tot = 0, cur = 0, part_max = 0;
     for (int m = 0; m < M; ++m) {
         const int64_t nt = (n_frames[m] + EM_TF - 1) / EM_TF;
-        if (nt > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: too many frames (model %d)", m);
+        if (nt > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "%s: too many frames (model %d)", fn, m);
         const int G = (int)std::min<int64_t>(nt, gcap);
         const int64_t pf = 4 * (int64_t)G * cols;
         if (m == 0 || (cur > 0 && cur + pf > budget_f) || m - gstart.back() >= 65535) {
@@ -745,7 +751,7 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
     gstart.push_back(M);
     wstart.push_back((int64_t)work.size());
     if ((int64_t)tiles.size() > INT32_MAX || (int64_t)work.size() > INT32_MAX)
-        SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats_batch: too many frames");
+        SSP_FAIL(SSP_ERR_UNSUPPORTED, "%s: too many frames", fn);
     hipStream_t s = ctx->stream;
     DevBuf &d_par = ctx->scratch[0], &d_lse = ctx->scratch[1], &d_lsep = ctx->scratch[2], &d_part = ctx->scratch[3],
            &d_out = ctx->scratch[4], &d_tab = ctx->scratch[5];
@@ -769,7 +775,7 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
     const EmModel* d_models = (const EmModel*)d_tab.p;
     const int2* d_work = (const int2*)((char*)d_tab.p + tab_models);
     const int2* d_tiles = (const int2*)((char*)d_tab.p + tab_models + tab_work);
-    EmBatchArgs b{d_x, d_par.as<float>(), d_lse.as<float>(), d_lsep.as<float>(), d_part.as<float>(), d_models, d_work, D, K, Kp};
+    EmBatchArgs b{d_x, d_par.as<float>(), d_lse.as<float>(), d_lsep.as<float>(), d_part.as<float>(), d_models, d_work, D, K, Kp, shared ? (int64_t)0 : (int64_t)Kp * W};
     const size_t lds_acc = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + (size_t)EM_TF * 65 + 256) * sizeof(float);
     const size_t lds_lse = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + 256) * sizeof(float);
     const void* acc_k = nullptr;
@@ -808,7 +814,7 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
                                s, b, gstart[gi], cols, fuse ? 1 : 0, d_out.as<double>());
         }
         if (hipGetLastError() != hipSuccess) {
-            set_error("ssp_gmm_em_stats_batch: kernel launch failed");
+            set_error("%s: kernel launch failed", fn);
             rc = SSP_ERR_HIP;
         }
     }
@@ -820,7 +826,7 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
     std::vector<double> host((size_t)M * (cols + 1));
     hipError_t he = hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
-    if (he != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "ssp_gmm_em_stats_batch: result copy failed: %s", hipGetErrorString(he));
+    if (he != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "%s: result copy failed: %s", fn, hipGetErrorString(he));
     for (int m = 0; m < M; ++m) {
         const double* o = host.data() + (size_t)m * (cols + 1);
         for (int k = 0; k < K; ++k) {
@@ -834,4 +840,20 @@ extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_
         loglik_sum_out[m] = o[cols];
     }
     return SSP_OK;
+}
+
+extern "C" int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                                      const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off,
+                                      const int64_t* n_frames, double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out,
+                                      int where, float* kernel_ms) {
+    return em_stats_batch_impl(ctx, M, K, D, weights, means, covars, feats, n_rows, row_off, n_frames, nk_out, sx_out, sxx_out, loglik_sum_out,
+                               where, kernel_ms, false, "ssp_gmm_em_stats_batch");
+}
+
+extern "C" int ssp_gmm_em_stats_shared(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
+                                       const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off,
+                                       const int64_t* n_frames, double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out,
+                                       int where, float* kernel_ms) {
+    return em_stats_batch_impl(ctx, M, K, D, weights, means, covars, feats, n_rows, row_off, n_frames, nk_out, sx_out, sxx_out, loglik_sum_out,
+                               where, kernel_ms, true, "ssp_gmm_em_stats_shared");
 }

@@ -472,3 +472,82 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
         gm.precisions_cholesky_ = 1.0 / np.sqrt(gm.covariances_)
         gm.precisions_ = gm.precisions_cholesky_ ** 2
     return gms
+
+
+def map_adapt(ubm, Xs, relevance_factor=16.0, adapt='m', ctx=None):
+    """MAP adaptation of a fitted UBM to every array of ``Xs`` (Reynolds, Quatieri, Dunn 2000) — an extension: the reference trains each
+    speaker's mixture independently (GMM_UBM.py:158-170).  ONE ssp_gmm_em_stats_shared call gives every speaker's n = nk, Ex = sx / n,
+    Exx = sxx / n under the UBM; then in float64, with alpha = n / (n + relevance_factor) per mixture:
+      'm'  means        alpha Ex + (1 - alpha) mu
+      'w'  weights      alpha n / T + (1 - alpha) w, renormalised to sum 1
+      'v'  covariances  alpha Exx + (1 - alpha) (sigma^2 + mu^2) - (new mean)^2, floored at the UBM's reg_covar
+    ``adapt``: any non-empty combination of these letters; what is not adapted is the UBM's array, element for element (with 'm' alone
+    the models are what api.MapScorer takes).  A mixture with n = 0 keeps the UBM's values.  Returns one GaussianMixture per array, every
+    sklearn attribute set (converged_ = True, n_iter_ = 1).  ValueError as sklearn raises it: a non-finite row (the message names the
+    speaker and row), mismatched feature widths, an unfitted ubm."""
+    for name in ("weights_", "means_", "covariances_"):
+        if not hasattr(ubm, name):
+            raise ValueError("This GaussianMixture instance is not fitted yet: the UBM has no %s" % name)
+    if not isinstance(adapt, str) or not adapt or set(adapt) - set("mwv"):
+        raise ValueError("adapt must be a non-empty combination of 'm', 'w' and 'v'")
+    r = float(relevance_factor)
+    if not r >= 0.0:
+        raise ValueError("relevance_factor must be >= 0")
+    w = np.asarray(ubm.weights_, dtype=np.float64)
+    mu = np.asarray(ubm.means_, dtype=np.float64)
+    cv = np.asarray(ubm.covariances_, dtype=np.float64)
+    if mu.ndim != 2 or cv.shape != mu.shape or w.shape != mu.shape[:1]:
+        raise ValueError("only covariance_type='diag' UBMs are supported")
+    K, D = mu.shape
+    Xs = list(Xs)
+    if not Xs:
+        return []
+    hosts = [_host_f32(X) for X in Xs]
+    for X in hosts:
+        if X.shape[1] != D:
+            raise ValueError("X has %d features, but the UBM is expecting %d features as input." % (X.shape[1], D))
+        if X.shape[0] < 1:
+            raise ValueError("Found array with 0 sample(s) while a minimum of 1 is required.")
+    ctx = ctx or getattr(ubm, "_ctx", None) or api.default_context()
+    ns = np.array([X.shape[0] for X in hosts], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    import torch
+    feats = torch.from_numpy(np.concatenate(hosts)).to("cuda:%d" % ctx.device)
+    torch.cuda.synchronize()
+    bad = _first_bad_row(feats)
+    if bad is not None:
+        m = int(np.searchsorted(offs, bad, side="right")) - 1
+        raise ValueError(_nonfinite_message(" of speaker %d" % m, bad - int(offs[m])))
+    st = api.gmm_em_stats_shared(ctx, w, mu, cv, feats, offs, ns)
+    w_new, mu_new, cv_new = _map_formulas(w, mu, cv, st["nk"], st["sx"], st["sxx"], ns, r, adapt, float(getattr(ubm, "reg_covar", 1e-6)))
+    out = []
+    for s in range(len(hosts)):
+        gm = GaussianMixture(n_components=K, covariance_type='diag', reg_covar=float(getattr(ubm, "reg_covar", 1e-6)), ctx=ctx)
+        gm.weights_ = w_new[s] if 'w' in adapt else w
+        gm.means_ = mu_new[s] if 'm' in adapt else mu
+        gm.covariances_ = cv_new[s] if 'v' in adapt else cv
+        gm.precisions_cholesky_ = 1.0 / np.sqrt(gm.covariances_)
+        gm.precisions_ = gm.precisions_cholesky_ ** 2
+        gm.converged_, gm.n_iter_ = True, 1
+        gm.lower_bound_ = float(st["loglik_sum"][s] / ns[s])  # of the E step under the UBM, as the first EM iteration would record it
+        out.append(gm)
+    return out
+
+
+def _map_formulas(w, mu, cv, nk, sx, sxx, T, r, adapt, reg_covar):
+    """the adaptation arithmetic over a batch: nk (S,K), sx / sxx (S,K,D), T (S,) frames -> (weights (S,K), means, covariances (S,K,D));
+    every quantity is computed whatever ``adapt`` says (the caller picks)"""
+    n = nk[:, :, None]
+    has = n > 0.0
+    safe = np.where(has, n, 1.0)
+    Ex = np.where(has, sx / safe, mu[None])
+    Exx = np.where(has, sxx / safe, (cv + mu * mu)[None])
+    alpha = np.where(has, n / (n + r) if r > 0.0 else 1.0, 0.0) if np.isfinite(r) else np.zeros_like(n)
+    m_new = alpha * Ex + (1.0 - alpha) * mu[None]
+    m_used = m_new if 'm' in adapt else np.broadcast_to(mu[None], m_new.shape)
+    a1 = alpha[:, :, 0]
+    w_new = a1 * nk / np.asarray(T, dtype=np.float64)[:, None] + (1.0 - a1) * w[None]
+    w_new = w_new / w_new.sum(axis=1, keepdims=True)
+    v_new = np.maximum(alpha * Exx + (1.0 - alpha) * (cv + mu * mu)[None] - m_used ** 2, reg_covar)
+    v_new = np.where(has, v_new, cv[None])  # (n = 0 keeps the UBM's values exactly: (cv + mu^2) - mu^2 rounds)
+    return w_new, m_new, v_new
