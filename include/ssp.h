@@ -59,6 +59,7 @@ typedef struct ssp_segments ssp_segments;
 typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_gmm_map ssp_gmm_map;
+typedef struct ssp_ivector ssp_ivector;   /* a UBM and a total-variability matrix packed for i-vector extraction and the E-step */
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
@@ -453,6 +454,51 @@ int ssp_gmm_map_score(ssp_gmm_map* map, const float* feats, const ssp_segments* 
                       int32_t* argmax_out, int32_t* idx_out, int where, float* kernel_ms);
 int ssp_gmm_map_score_list(ssp_gmm_map* map, const void* const* rows, int row_type, int32_t dim, const ssp_segments* frame_seg, int32_t C,
                            float* diff_out, float* ubm_out, int32_t* argmax_out, int32_t* idx_out, float* kernel_ms);
+
+/* ---- i-vector extraction and the E-step of total-variability training (Dehak et al. 2011, after Kenny 2005).  An EXTENSION and
+ *      UNPINNED: the reference has no factor analysis; sidekit, the package it imports its features from, ships this model as
+ *      FactorAnalyser.total_variability / extract_ivectors.  The yardstick is a float64 restatement (tests/ivector_oracle.py).  It joins
+ *      the two scoring halves: ssp_gmm_em_stats_shared's statistics go in, a fixed-length embedding comes out, and that is what
+ *      ssp_centroids / ssp_cosine_identify / ssp_l2_normalize take. ----
+ * Definition.  A diagonal UBM with means mu (K x D) and covariances cv (K x D), a total-variability matrix T (K x D x R), and per
+ * utterance u the statistics nk[u] (K) and sx[u] (K x D) as ssp_gmm_em_stats_shared returns them:
+ *   f[u,k,:] = sx[u,k,:] - nk[u,k] mu[k,:]          (formed in float64, then rounded to fp32 once: sx and nk mu cancel)
+ *   P_k = T_k' diag(1/cv_k) T_k  (R x R),   G = diag(1/cv) T  (K D x R)          (float64, rounded once)
+ *   L_u = I + sum_k nk[u,k] P_k,   b_u = G' f_u,   w_u = L_u^-1 b_u  (the i-vector),   logdet_u = log|L_u|,   quad_u = b_u' w_u
+ *   objective of a batch = sum_u (-logdet_u / 2 + quad_u / 2): the marginal log-likelihood up to a constant in T; EM never decreases it
+ *   E-step accumulators  A_k = sum_u nk[u,k] (L_u^-1 + w_u w_u'),   C = sum_u f_u w_u'  (K x D x R);   M-step (the caller's)  T_k = C_k A_k^-1
+ * No covariance update, no minimum-divergence step, no PLDA / WCCN / LDA back end.
+ * Every array is a HOST array: the statistics arrive on the host from ssp_gmm_em_stats_shared (device-resident statistics are a
+ * follow-up).  ubm_means / ubm_covars double[K x D], T double[K x D x R]; nk double[U x K], sx double[U x K x D]; w_out float[U x R],
+ * logdet_out / quad_out float[U] (nullable); A_out double[K x R x R] (full, symmetric), C_out double[K x D x R], objective_out (nullable).
+ * SSP_ERR_INVALID, each found before any GPU work: K, D, R or U < 1, a covariance that is not positive and finite, a non-finite T or
+ * mean.  SSP_ERR_UNSUPPORTED: R > 256 (the packed triangle of L_u lives in one workgroup's LDS).  The ctx stays usable after either.
+ * Work per call: the device is fp32 with exact-fp32 MFMA.  sum_k nk P_k is one GEMM against the K packed lower triangles of P (row i,
+ * column j <= i at i (i + 1) / 2 + j), b one GEMM against G; one workgroup per utterance then factors L_u in LDS (Cholesky), solves,
+ * and for the E-step goes on in place to L_u^-1; the accumulators are two more GEMMs (N' S and f' W).  ssp_ivector_set_t re-packs P
+ * and G on the device from the uploaded float64 T.  A large batch runs in slabs of whole utterances under the workspace cap
+ * (ssp_ivector_set_workspace, default 1 GiB, counts what grows with the slab; one utterance always runs; ssp_ivector_last_slab: the
+ * utterances per slab of the last call); the E-step's accumulators are added over the slabs in slab order in float64.
+ * Contracts.  An utterance's w_out, logdet_out and quad_out bits do not depend on U, on the slab size or on its place in the batch.
+ * An utterance with every nk = 0 (and sx = 0) gives w = 0, logdet = 0, quad = 0 exactly.  No floating-point atomics, every sum has a
+ * fixed shape: the same call gives the same bits every time.
+ * Non-finite statistics.  An utterance whose nk or sx holds a non-finite entry (or one too large for fp32) gives NaN in its own w_out,
+ * logdet_out and quad_out only; every other utterance is BIT-IDENTICAL to the same call with that utterance's statistics replaced by
+ * zeros.  ssp_ivector_estep on such a batch returns NaN accumulators and a NaN objective.  No error is reported; the Python layer
+ * raises ValueError naming the utterance.
+ * kernel_ms: the device time of the kernels, copies excluded; ssp_ivector_last_stages then holds its split, float[5]: the precision
+ * GEMM, the right-hand-side GEMM, the Cholesky kernel, and for the E-step the A and the C accumulator GEMMs. */
+int ssp_ivector_create(ssp_ctx* ctx, int32_t K, int32_t D, int32_t R, const double* ubm_means, const double* ubm_covars,
+                       const double* T, ssp_ivector** out);
+int ssp_ivector_destroy(ssp_ivector* iv);
+int ssp_ivector_set_t(ssp_ivector* iv, const double* T);
+int ssp_ivector_set_workspace(ssp_ivector* iv, size_t bytes);
+int ssp_ivector_last_slab(const ssp_ivector* iv, int64_t* utterances);
+int ssp_ivector_last_stages(const ssp_ivector* iv, float* ms);
+int ssp_ivector_extract(ssp_ivector* iv, const double* nk, const double* sx, int64_t U, float* w_out, float* logdet_out, float* quad_out,
+                        float* kernel_ms);
+int ssp_ivector_estep(ssp_ivector* iv, const double* nk, const double* sx, int64_t U, double* A_out, double* C_out, double* objective_out,
+                      float* kernel_ms);
 
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with

@@ -93,6 +93,14 @@ SIGNATURES = {
     "ssp_gmm_map_destroy": (C.c_int, [_P]),
     "ssp_gmm_map_score": (C.c_int, [_P, _F32P, _P, C.c_int32, _F32P, _F32P, _P, _P, C.c_int, _MSP]),
     "ssp_gmm_map_score_list": (C.c_int, [_P, _P, C.c_int, C.c_int32, _P, C.c_int32, _F32P, _F32P, _P, _P, _MSP]),
+    "ssp_ivector_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
+    "ssp_ivector_destroy": (C.c_int, [_P]),
+    "ssp_ivector_set_t": (C.c_int, [_P, _P]),
+    "ssp_ivector_set_workspace": (C.c_int, [_P, C.c_size_t]),
+    "ssp_ivector_last_slab": (C.c_int, [_P, _I64P]),
+    "ssp_ivector_last_stages": (C.c_int, [_P, _MSP]),
+    "ssp_ivector_extract": (C.c_int, [_P, _P, _P, C.c_int64, _F32P, _F32P, _F32P, _MSP]),
+    "ssp_ivector_estep": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(C.c_double), _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

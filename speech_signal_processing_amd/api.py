@@ -1008,6 +1008,121 @@ class MapScorer:
             pass
 
 
+IVECTOR_MAX_R = 256  # ssp_ivector_create's largest rank (include/ssp.h)
+IVECTOR_STAGES = ("gemm_L", "gemm_b", "cholesky", "gemm_A", "gemm_C")  # ssp_ivector_last_stages
+
+
+class IvectorExtractor:
+    """i-vector extraction and the E-step of total-variability training (ssp_ivector; an extension the reference does not have).
+    ubm_mu (K,D), ubm_cv (K,D), T (K,D,R) float64.  Statistics nk (U,K), sx (U,K,D) float64 on the host, as gmm_em_stats_shared returns
+    them; include/ssp.h has the definitions."""
+
+    def __init__(self, ctx: Context, ubm_mu, ubm_cv, T):
+        mu = np.ascontiguousarray(ubm_mu, dtype=np.float64)
+        cv = np.ascontiguousarray(ubm_cv, dtype=np.float64)
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if mu.ndim != 2 or mu.shape != cv.shape or T.ndim != 3 or T.shape[:2] != mu.shape:
+            raise ValueError("expected ubm_mu (K,D), ubm_cv (K,D), T (K,D,R)")
+        self.K, self.D = mu.shape
+        self.R = int(T.shape[2])
+        if self.R < 1:
+            raise ValueError("T (K,D,R): the rank R must be at least 1")
+        if self.R > IVECTOR_MAX_R:
+            raise NotImplementedError("R=%d exceeds the supported rank (%d)" % (self.R, IVECTOR_MAX_R))
+        self.ctx = ctx
+        self._lib = ctx._lib
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_ivector_create(ctx._h, self.K, self.D, self.R, mu.ctypes.data, cv.ctypes.data, T.ctypes.data, C.byref(h)))
+        self._h = h
+
+    def set_T(self, T) -> "IvectorExtractor":
+        """replace T (K,D,R): P and G are packed again on the device"""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.shape != (self.K, self.D, self.R):
+            raise ValueError("T must be (%d, %d, %d)" % (self.K, self.D, self.R))
+        _lib.check(self._lib.ssp_ivector_set_t(self._h, T.ctypes.data))
+        return self
+
+    def set_workspace(self, nbytes: int) -> "IvectorExtractor":
+        """cap of the workspace that grows with the slab; larger batches run in slabs of whole utterances (same bits per utterance)"""
+        _lib.check(self._lib.ssp_ivector_set_workspace(self._h, C.c_size_t(int(nbytes))))
+        return self
+
+    @property
+    def last_slab(self) -> int:
+        n = C.c_int64(0)
+        _lib.check(self._lib.ssp_ivector_last_slab(self._h, C.byref(n)))
+        return n.value
+
+    @property
+    def last_stages(self) -> dict:
+        """device milliseconds per stage of the last call made with timing=True"""
+        ms = (C.c_float * len(IVECTOR_STAGES))()
+        _lib.check(self._lib.ssp_ivector_last_stages(self._h, ms))
+        return dict(zip(IVECTOR_STAGES, [float(v) for v in ms]))
+
+    def _stats(self, nk, sx, check):
+        nk = np.ascontiguousarray(nk, dtype=np.float64)
+        sx = np.ascontiguousarray(sx, dtype=np.float64)
+        if nk.ndim != 2 or nk.shape[1] != self.K or sx.shape != (nk.shape[0], self.K, self.D):
+            raise ValueError("expected nk (U, %d) and sx (U, %d, %d)" % (self.K, self.K, self.D))
+        if nk.shape[0] < 1:
+            raise ValueError("at least one utterance is needed")
+        if check:
+            ok = np.isfinite(nk).all(axis=1) & np.isfinite(sx).all(axis=(1, 2))
+            if not ok.all():
+                raise ValueError("the statistics of utterance %d contain NaN or infinity" % int(np.argmin(ok)))
+        return nk, sx
+
+    def extract(self, nk, sx, logdet: bool = False, quad: bool = False, timing: bool = False, check: bool = True):
+        """-> w (U, R) float32, or a dict with "w" and the requested "logdet" / "quad" (U,) [and "kernel_ms"].  ValueError names the first
+        utterance with a non-finite statistic; check=False hands such a batch to the library, which answers that utterance with NaN."""
+        nk, sx = self._stats(nk, sx, check)
+        U = int(nk.shape[0])
+        w = np.empty((U, self.R), dtype=np.float32)
+        ld = np.empty(U, dtype=np.float32) if logdet else None
+        qd = np.empty(U, dtype=np.float32) if quad else None
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.ssp_ivector_extract(self._h, nk.ctypes.data, sx.ctypes.data, U, w.ctypes.data, ld.ctypes.data if logdet else None,
+                                                 qd.ctypes.data if quad else None, C.byref(ms) if timing else None))
+        if not (logdet or quad or timing):
+            return w
+        res = {"w": w}
+        if logdet:
+            res["logdet"] = ld
+        if quad:
+            res["quad"] = qd
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def estep(self, nk, sx, timing: bool = False, check: bool = True) -> dict:
+        """-> {"A" (K,R,R), "C" (K,D,R), "objective"} float64 [and "kernel_ms"]: the accumulators of one EM iteration under the current T"""
+        nk, sx = self._stats(nk, sx, check)
+        U = int(nk.shape[0])
+        A = np.empty((self.K, self.R, self.R), dtype=np.float64)
+        Cm = np.empty((self.K, self.D, self.R), dtype=np.float64)
+        obj = C.c_double(0.0)
+        ms = C.c_float(0.0)
+        _lib.check(self._lib.ssp_ivector_estep(self._h, nk.ctypes.data, sx.ctypes.data, U, A.ctypes.data, Cm.ctypes.data, C.byref(obj),
+                                               C.byref(ms) if timing else None))
+        res = {"A": A, "C": Cm, "objective": obj.value}
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_ivector_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def centroids(ctx: Context, X, labels, num: int):
     """avg[s] = mean(X[labels == s]) (float64 accumulator, row order) — d_vector.py:310-313."""
     keep, ptr, where = _as_f32(X, "X")

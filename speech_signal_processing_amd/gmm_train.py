@@ -474,6 +474,45 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
     return gms
 
 
+def _check_fitted_ubm(ubm):
+    for name in ("weights_", "means_", "covariances_"):
+        if not hasattr(ubm, name):
+            raise ValueError("This GaussianMixture instance is not fitted yet: the UBM has no %s" % name)
+
+
+def _diag_ubm_arrays(ubm):
+    """-> float64 weights (K,), means (K,D), covariances (K,D) of a fitted diagonal UBM"""
+    w = np.asarray(ubm.weights_, dtype=np.float64)
+    mu = np.asarray(ubm.means_, dtype=np.float64)
+    cv = np.asarray(ubm.covariances_, dtype=np.float64)
+    if mu.ndim != 2 or cv.shape != mu.shape or w.shape != mu.shape[:1]:
+        raise ValueError("only covariance_type='diag' UBMs are supported")
+    return w, mu, cv
+
+
+def _shared_stats(w, mu, cv, Xs, ctx):
+    """the statistics of every array of the non-empty list ``Xs`` under one model, in ONE ssp_gmm_em_stats_shared call, with sklearn's
+    input validation (widths, empty arrays, non-finite rows: the message names the speaker and row) -> (ctx, frames per array, statistics)"""
+    D = mu.shape[1]
+    hosts = [_host_f32(X) for X in Xs]
+    for X in hosts:
+        if X.shape[1] != D:
+            raise ValueError("X has %d features, but the UBM is expecting %d features as input." % (X.shape[1], D))
+        if X.shape[0] < 1:
+            raise ValueError("Found array with 0 sample(s) while a minimum of 1 is required.")
+    ctx = ctx or api.default_context()
+    ns = np.array([X.shape[0] for X in hosts], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    import torch
+    feats = torch.from_numpy(np.concatenate(hosts)).to("cuda:%d" % ctx.device)
+    torch.cuda.synchronize()
+    bad = _first_bad_row(feats)
+    if bad is not None:
+        m = int(np.searchsorted(offs, bad, side="right")) - 1
+        raise ValueError(_nonfinite_message(" of speaker %d" % m, bad - int(offs[m])))
+    return ctx, ns, api.gmm_em_stats_shared(ctx, w, mu, cv, feats, offs, ns)
+
+
 def map_adapt(ubm, Xs, relevance_factor=16.0, adapt='m', ctx=None):
     """MAP adaptation of a fitted UBM to every array of ``Xs`` (Reynolds, Quatieri, Dunn 2000) — an extension: the reference trains each
     speaker's mixture independently (GMM_UBM.py:158-170).  ONE ssp_gmm_em_stats_shared call gives every speaker's n = nk, Ex = sx / n,
@@ -485,43 +524,21 @@ def map_adapt(ubm, Xs, relevance_factor=16.0, adapt='m', ctx=None):
     the models are what api.MapScorer takes).  A mixture with n = 0 keeps the UBM's values.  Returns one GaussianMixture per array, every
     sklearn attribute set (converged_ = True, n_iter_ = 1).  ValueError as sklearn raises it: a non-finite row (the message names the
     speaker and row), mismatched feature widths, an unfitted ubm."""
-    for name in ("weights_", "means_", "covariances_"):
-        if not hasattr(ubm, name):
-            raise ValueError("This GaussianMixture instance is not fitted yet: the UBM has no %s" % name)
+    _check_fitted_ubm(ubm)
     if not isinstance(adapt, str) or not adapt or set(adapt) - set("mwv"):
         raise ValueError("adapt must be a non-empty combination of 'm', 'w' and 'v'")
     r = float(relevance_factor)
     if not r >= 0.0:
         raise ValueError("relevance_factor must be >= 0")
-    w = np.asarray(ubm.weights_, dtype=np.float64)
-    mu = np.asarray(ubm.means_, dtype=np.float64)
-    cv = np.asarray(ubm.covariances_, dtype=np.float64)
-    if mu.ndim != 2 or cv.shape != mu.shape or w.shape != mu.shape[:1]:
-        raise ValueError("only covariance_type='diag' UBMs are supported")
-    K, D = mu.shape
+    w, mu, cv = _diag_ubm_arrays(ubm)
+    K = mu.shape[0]
     Xs = list(Xs)
     if not Xs:
         return []
-    hosts = [_host_f32(X) for X in Xs]
-    for X in hosts:
-        if X.shape[1] != D:
-            raise ValueError("X has %d features, but the UBM is expecting %d features as input." % (X.shape[1], D))
-        if X.shape[0] < 1:
-            raise ValueError("Found array with 0 sample(s) while a minimum of 1 is required.")
-    ctx = ctx or getattr(ubm, "_ctx", None) or api.default_context()
-    ns = np.array([X.shape[0] for X in hosts], dtype=np.int64)
-    offs = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
-    import torch
-    feats = torch.from_numpy(np.concatenate(hosts)).to("cuda:%d" % ctx.device)
-    torch.cuda.synchronize()
-    bad = _first_bad_row(feats)
-    if bad is not None:
-        m = int(np.searchsorted(offs, bad, side="right")) - 1
-        raise ValueError(_nonfinite_message(" of speaker %d" % m, bad - int(offs[m])))
-    st = api.gmm_em_stats_shared(ctx, w, mu, cv, feats, offs, ns)
+    ctx, ns, st = _shared_stats(w, mu, cv, Xs, ctx or getattr(ubm, "_ctx", None))
     w_new, mu_new, cv_new = _map_formulas(w, mu, cv, st["nk"], st["sx"], st["sxx"], ns, r, adapt, float(getattr(ubm, "reg_covar", 1e-6)))
     out = []
-    for s in range(len(hosts)):
+    for s in range(len(Xs)):
         gm = GaussianMixture(n_components=K, covariance_type='diag', reg_covar=float(getattr(ubm, "reg_covar", 1e-6)), ctx=ctx)
         gm.weights_ = w_new[s] if 'w' in adapt else w
         gm.means_ = mu_new[s] if 'm' in adapt else mu
