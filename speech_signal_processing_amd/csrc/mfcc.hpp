@@ -11,6 +11,18 @@ struct MfccChunk {
     int32_t pad;  // wave-stream kernel: extra frames of halo in front of the chunk (0, or 12: the chunk then reproduces the uncut utterance's bits)
 };
 
+// wave-stream kernel, fixed-geometry instances: everything a chunk's prologue derives from MfccChunk and the two offset tables, in one
+// 32-byte record (one wave-uniform load instead of a chain of three dependent ones).  Built and cached with the chunk table
+struct StreamChunkRec {
+    int64_t s0;      // first sample of the utterance (floats from MfccArgs::samples)
+    int64_t f0;      // first output row of the utterance
+    int32_t xbytes;  // bytes of the utterance's samples
+    int32_t T;       // frames of the utterance
+    int32_t t0;      // first frame of the chunk inside the utterance
+    int32_t n_pad;   // frames in the chunk (a stream chunk has at most 512) | MfccChunk::pad << 16
+};
+static_assert(sizeof(StreamChunkRec) == 32, "one s_load_dwordx8 per chunk");
+
 struct MfccArgs {
     // data
     const float* samples;
@@ -96,6 +108,8 @@ struct StreamArgs {
     int32_t table_bytes;      // workgroup-shared DCT operand table in front of the wave regions
     int32_t tstep;            // the instance has the transposed step form (scan kernel: without deltas one row per step tells)
     const float* dense_w;     // dense-band instances: [lane][6 bands][20] weights (16 bins of the lane's chunk, bin 256, pad), pscale folded in
+    const StreamChunkRec* chunk_rec;  // [n_chunks] beside MfccArgs::chunks (read by the fixed-geometry instances only; last member: the
+                                      // offsets of the others stay what the run-time-geometry instances were compiled with)
 };
 
 int launch_mfcc_generic(const MfccArgs& args, int n_chunks, size_t lds_bytes, int n_waves, int num_cu, hipStream_t stream);
@@ -131,6 +145,8 @@ struct ssp_mfcc_plan {
     std::vector<int32_t> cache_chunk_first;  // [n_utt + 1] first chunk of every utterance (chunks are laid out in utterance order): a
                                              // range of utterances is a range of chunks (the sliced host-fed path launches such ranges)
     ssp::DevBuf chunks;
+    ssp::DevBuf chunk_rec;  // one StreamChunkRec per chunk of the last wave-stream (variant 3) work table; a table built for another kernel
+                            // leaves it as it was, and only a launch of a variant-3 table reads it
     ssp::MfccArgs args{};
     // fused n_fft == 512 kernel
     bool fast_ready = false;

@@ -233,7 +233,17 @@ static int build_work(ssp_mfcc_plan* p, const ssp_segments* sseg, const ssp_segm
     if (chunks.size() > (size_t)INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc: too many chunks");
     p->cache_chunk_first[(size_t)fseg->n] = (int32_t)chunks.size();
     SSP_TRY(upload(p->chunks, chunks, p->ctx->stream));
-    SSP_HIP(hipStreamSynchronize(p->ctx->stream));  // `chunks` (host) dies at return
+    std::vector<StreamChunkRec> recs;
+    if (variant == 3) {  // (mfcc_stream_kernel.hpp: the fixed-geometry instances start a chunk from this record)
+        recs.reserve(chunks.size());
+        for (const MfccChunk& k : chunks) {
+            const int64_t s0 = sseg->host[(size_t)k.utt], N = sseg->host[(size_t)k.utt + 1] - s0;  // (N * 4 fits 32 bits: the launch checks fast_max_samples)
+            const int64_t f0 = fseg->host[(size_t)k.utt], T = fseg->host[(size_t)k.utt + 1] - f0;
+            recs.push_back(StreamChunkRec{s0, f0, (int32_t)std::min<int64_t>(N * 4, INT32_MAX), (int32_t)T, k.t0, k.n | (k.pad << 16)});
+        }
+        SSP_TRY(upload(p->chunk_rec, recs, p->ctx->stream));
+    }
+    SSP_HIP(hipStreamSynchronize(p->ctx->stream));  // `chunks` and `recs` (host) die at return
     p->fast_max_samples = sseg->max_len();
     p->cache_n_chunks = (int32_t)chunks.size();
     p->cache_chunk_frames = ch;

@@ -49,6 +49,24 @@ constexpr int PSH = SSP_S_PSHIFT;
 // (a piece read starts at a filter's first bin rounded down to 4 and spans at most 4 MELV <= 20 taps: it ends below dword 256 + 24 of the P
 //  row — with the shift still far below the lowest log-mel row, LM_OFF - 192, which a read must never reach: last quad's ln 0 = -inf there)
 static_assert(4 * (256 + 24) + PSH <= LM_OFF - 192, "shifted P row: piece reads must stay below the log-mel rows");
+// Work the fixed-geometry instances (GEO != 0) leave out because it computes nothing in their dialect, each behind a switch of its own
+// (-DSSP_S_...=0 puts the item back: tools/variant_flags.sh builds such a library, profiles/stream_noops.md has what each measured):
+//   SSP_S_NOFLOOR  the logarithm without the floor operations: these plans have floor_mode 0 (stream_fixed_geo), log_add = 0 and log_max = -inf,
+//                  so the add and the max in front of the log are identities (-0 + 0 = +0 has the same log; a NaN goes through max as -inf
+//                  and through the log as NaN either way)
+//   SSP_S_PUTSC    the pipelined loop's ring store under the scalar test q > 0: its frames ta + 4 (q - 1) + j always lie below tb
+//   SSP_S_AHEAD    the chunk's prologue from one 32-byte StreamChunkRec, claimed and loaded one chunk ahead, at the end of the chunk
+//                  before and behind its last stores, so that the record is not live across the quad loop (claimed behind the chunk's own
+//                  first sample DMA it is: nine more scalar registers there, measured slower than no record at all — not in the tree)
+#ifndef SSP_S_NOFLOOR
+#define SSP_S_NOFLOOR 1
+#endif
+#ifndef SSP_S_PUTSC
+#define SSP_S_PUTSC 1
+#endif
+#ifndef SSP_S_AHEAD
+#define SSP_S_AHEAD 1
+#endif
 #define SSP_STR_(x) #x
 #define SSP_STR(x) SSP_STR_(x)
 
@@ -177,6 +195,27 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
     // second kernel: the waves share the chunks' flags in blocks of 64 (no atomics: one flag per lane, a ballot, the set bits in turn)
     uint64_t wm = 0;
     int wblk = blockIdx.x * STREAM_WAVES + wave, wbase = 0;
+    // GEO, first kernel: a wave starts a chunk from the index and the StreamChunkRec it claimed before.  The claim comes from all lanes
+    // through a bounds-checked buffer atomic, every lane but lane 0 aimed out of range (no lane-0 block beside the loop's back edge:
+    // tools/microbench/lane0_loop.hip), and is waited for where it is issued, with the record load behind it: nothing of either is
+    // outstanding inside the quad loop, whose counted waits assume that.  A wave stops claiming at its first index past the table, so the
+    // counter over-runs n_chunks by one claim per wave, as it always has; the launch's memset resets it, nothing reads it as a count.
+    constexpr bool AHEAD = FIXG && !WALK && SSP_S_AHEAD;
+    typedef int rec_t __attribute__((ext_vector_type(8)));
+    int nx_cidx = 0;
+    rec_t nx_rec = rec_t{0, 0, 0, 0, 0, 0, 0, 0};
+    auto claim_ahead = [&]() {
+        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(sa.work_counter, 0, 4, 0x00020000);
+        int ol = lane;
+        asm volatile("" : "+v"(ol));
+        const int got = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, rc, ol == 0 ? 0 : 0x7ffffff0, 0, 0);
+        nx_cidx = __builtin_amdgcn_readfirstlane(got);
+        // (an index past the table reads the last record: the wave leaves at the top of the chunk loop and never uses it)
+        // (one scalar load, written out: left to the compiler the load of a pointer it cannot prove unwritten becomes a vector load)
+        const StreamChunkRec* rp = sa.chunk_rec + min(nx_cidx, sa.n_chunks - 1);
+        asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(nx_rec) : "s"(rp) : "memory");
+    };
+    if constexpr (AHEAD) claim_ahead();
     for (;;) {
         int cidx = 0;
         if constexpr (WALK) {
@@ -195,17 +234,34 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
             if (done) break;
             cidx = __builtin_amdgcn_readfirstlane(wbase + __builtin_ctzll(wm));
             wm &= wm - 1;
+        } else if constexpr (AHEAD) {
+            cidx = nx_cidx;
+            if (cidx >= sa.n_chunks) break;
         } else {
             if (lane == 0) cidx = atomicAdd(sa.work_counter, 1);
             cidx = __builtin_amdgcn_readfirstlane(cidx);
             if (cidx >= sa.n_chunks) break;
         }
-        const MfccChunk ch = a.chunks[cidx];
-        const int64_t s0 = a.sample_off[ch.utt];
-        const int64_t N = a.sample_off[ch.utt + 1] - s0;
-        const int64_t f0 = a.frame_off[ch.utt];
-        const int T = __builtin_amdgcn_readfirstlane((int)(a.frame_off[ch.utt + 1] - f0));
-        const int t0 = __builtin_amdgcn_readfirstlane(ch.t0), n = __builtin_amdgcn_readfirstlane(ch.n);
+        // (the run-time-geometry instances and the second kernel read the chunk table and the two offset tables, statement for statement as ever)
+        MfccChunk ch{};
+        int64_t s0, N = 0, f0;
+        int T, t0, n, rec_xbytes = 0;
+        if constexpr (AHEAD) {
+            s0 = (int64_t)(((uint64_t)(uint32_t)nx_rec[1] << 32) | (uint32_t)nx_rec[0]);
+            f0 = (int64_t)(((uint64_t)(uint32_t)nx_rec[3] << 32) | (uint32_t)nx_rec[2]);
+            rec_xbytes = nx_rec[4];
+            T = nx_rec[5];
+            t0 = nx_rec[6];
+            n = nx_rec[7] & 0xffff;
+            ch.pad = nx_rec[7] >> 16;
+        } else {
+            ch = a.chunks[cidx];
+            s0 = a.sample_off[ch.utt];
+            N = a.sample_off[ch.utt + 1] - s0;
+            f0 = a.frame_off[ch.utt];
+            T = __builtin_amdgcn_readfirstlane((int)(a.frame_off[ch.utt + 1] - f0));
+            t0 = __builtin_amdgcn_readfirstlane(ch.t0), n = __builtin_amdgcn_readfirstlane(ch.n);
+        }
         // halo: 4 frames either side (a multiple of 4 for every delta order: a frame meets the same 4-frame k-groups of the delta product
         // wherever its chunk starts).  The delta-delta product's k-groups are STRIDED over the 16-row step window, so its summation
         // order — the last bits — depends on where the step windows sit in the utterance: chunks cut with the same rule agree bit for
@@ -224,7 +280,7 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
 
         const uint64_t xaddr = reinterpret_cast<uint64_t>(a.samples + s0);
         const uint32_t xlo = __builtin_amdgcn_readfirstlane((uint32_t)xaddr), xhi = __builtin_amdgcn_readfirstlane((uint32_t)(xaddr >> 32));
-        const int xbytes = __builtin_amdgcn_readfirstlane((int)(N * 4));
+        const int xbytes = AHEAD ? rec_xbytes : __builtin_amdgcn_readfirstlane((int)(N * 4));
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             reinterpret_cast<float*>(((uint64_t)xhi << 32) | xlo), 0, xbytes, 0x00020000);
         const uint64_t oaddr = reinterpret_cast<uint64_t>(a.out + (size_t)f0 * Dd);
@@ -501,12 +557,17 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
             if (mel_ns > 2) SSP_SCAN_STEP(0x104 /*row_shl:4*/, xx(mk23))
             if (mel_ns > 3) SSP_SCAN_STEP(0x108 /*row_shl:8*/, yy(mk23))
 #undef SSP_SCAN_STEP
+            // (GEO: no floor in these plans — SSP_S_NOFLOOR above; the scale stays a multiply of its own: folded into the DCT operand it changes bits)
+            auto slog = [&](float v) -> float {
+                if constexpr (FIXG && SSP_S_NOFLOOR) return __builtin_amdgcn_logf(v) * f.log_k;
+                else return stream_log(f, v);
+            };
             if (mfid >= 0) {
                 float* lmf = reinterpret_cast<float*>(zbuf + LM_OFF) + mfid;
-                lmf[0 * (ZFRAME - 64) / 4] = stream_log(f, s01.x);
-                lmf[1 * (ZFRAME - 64) / 4] = stream_log(f, s01.y);
-                lmf[2 * (ZFRAME - 64) / 4] = stream_log(f, s23.x);
-                lmf[3 * (ZFRAME - 64) / 4] = stream_log(f, s23.y);
+                lmf[0 * (ZFRAME - 64) / 4] = slog(s01.x);
+                lmf[1 * (ZFRAME - 64) / 4] = slog(s01.y);
+                lmf[2 * (ZFRAME - 64) / 4] = slog(s23.x);
+                lmf[3 * (ZFRAME - 64) / 4] = slog(s23.y);
             }
 #endif
         };
@@ -552,6 +613,15 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
                 else *reinterpret_cast<v4f*>(ring + ((((qq + 6) % 6) * 4 + j) * RING_ROW) + g * 16) = cv;
             }
             if (FIXG) qrow = ring_wrap(qrow + QROW);
+        };
+        // GEO, pipelined loop: quad q - 1 <= nquads - 2 lies wholly inside the chunk, so the per-lane test of ring_put is the scalar q > 0
+        // and nothing is selected (at q == 0 nothing is stored: the prologue has just zeroed the ring).  The drain keeps ring_put
+        auto ring_put_inner = [&](v4f cq, bool on) {
+            int ol = lane;
+            asm volatile("" : "+v"(ol));
+            const int g = ol >> 4, j = ol & 15;
+            if (j < 4 && on) *reinterpret_cast<v4f*>(ring + qrow + j * RING_ROW + g * 16) = cq;
+            qrow = ring_wrap(qrow + QROW);
         };
         // ================= time step b: rows [16 b - 4, 16 b + 12) of (c, delta, delta-delta) leave =================
         typedef float cbarr_t[6];
@@ -924,7 +994,8 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 window_a(z, pf, pm, std::integral_constant<int, DENSE ? 2 : 0>{});
                 stage_read_b(pf, pm);
-                ring_put(q - 1, cq, q > 0);
+                if constexpr (FIXG && SSP_S_PUTSC) ring_put_inner(cq, q > 0);
+                else ring_put(q - 1, cq, q > 0);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the stage is in registers: the next quad may overwrite it
 #ifndef SSP_S_NODMA
                 prefetch(q + 1);                                     // flies under this whole iteration (past the end: zeros)
@@ -947,6 +1018,7 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
             }
 #endif
         }
+        if constexpr (AHEAD) claim_ahead();  // (behind the chunk's last stores: the claim's round trip is their wait)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetch (zeros) and every store have completed
         if (CM) {
             // ---- scaling pass: column statistics over the four lane groups, then the utterance's rows once more through L2
@@ -1094,7 +1166,8 @@ static inline bool stream_fixed_geo(const ssp_mfcc_cfg& c, const FastArgs& f, co
     if (getenv("SSP_MFCC_STREAM_RUNTIME_GEO")) return false;
     return c.win_len == 400 && c.hop == 160 && a.hop == 160 && c.n_filt == 24 && a.n_filt == 24 && c.n_ceps == 13 && c.spec_power == 2 &&
            c.preemph_mode != 0 && f.slen == 3 * 160 + 32 * 13 && f.melv >= 2 && f.melv <= 4 && a.delta_order >= 0 && a.delta_order <= 2 &&
-           a.d_out == 13 * (1 + a.delta_order);
+           a.d_out == 13 * (1 + a.delta_order) &&
+           (!SSP_S_NOFLOOR || (c.floor_mode == 0 && f.log_add == 0.f && f.log_max == -INFINITY));  // (a plan with a floor keeps the run-time-geometry instance)
 }
 
 // WALK = 0: the first kernel of a launch (mfcc_stream.hip instantiates these); WALK = 1: the second (mfcc_stream_walk.hip), same
@@ -1113,6 +1186,8 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
     if (f.lm_pad > 16 && f.melv != 0) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc(stream): %d filters leave more than 16 padded slots", c.n_filt);
     sa.dctA = p->s_dctA.as<float>();
     sa.dense_w = p->s_dense.as<float>();
+    // (the launch may cover a range of the cached table: run_launch)
+    sa.chunk_rec = (p->chunk_rec.p && args.chunks) ? p->chunk_rec.as<StreamChunkRec>() + (args.chunks - p->chunks.as<MfccChunk>()) : nullptr;
     // the trailing half piece of the sample stage only writes 512 B
     const int n_piece = (f.slen + 255) >> 8;
     const bool has_half = (f.slen & 255) != 0 && (f.slen & 255) <= 128;
@@ -1149,6 +1224,7 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
 #endif
     const int geo = (stream_fixed_geo(c, f, args) && KS == 6 && nz == 13 && sa.stage_bytes == 3 * 1024 + 512 && geo_inst &&
                      !stream_geo_excluded(f.melv, f.mel_ns <= 2 ? 2 : 4, cm, 1 + args.delta_order)) ? 1 + args.delta_order : 0;
+    if (!dry_run && !WALK && geo != 0 && SSP_S_AHEAD && !sa.chunk_rec) SSP_FAIL(SSP_ERR_INVALID, "mfcc(stream): the work table has no chunk records");
     bool launched = false;
 #define SSP_STREAM_CASE(NZ_, PW_, PR_, MV_, KS_, OCC_) SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, 0)
 #define SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_) SSP_STREAM_CASE_G(NZ_, PW_, PR_, MV_, KS_, OCC_, CM_, 0)
