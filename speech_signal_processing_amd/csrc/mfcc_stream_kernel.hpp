@@ -33,6 +33,8 @@ namespace {
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const volatile v2f* lds_cv2f_t;
 typedef __attribute__((address_space(3))) const volatile float* lds_cvf_t;
+typedef __attribute__((address_space(3))) const v2f* lds_c2f_t;
+typedef __attribute__((address_space(3))) v4f* lds_4f_t;
 constexpr int ZROW = 128;          // bytes per 16-complex row of a frame's transpose image (chunks XOR-swizzled, see mfcc_fast.hip)
 constexpr int ZFRAME = 16 * ZROW;  // 2048 B per frame
 constexpr int LM_OFF = 1792;       // log-mel row of frame g sits at LM_OFF - 64 g inside its image (behind the P row)
@@ -67,6 +69,23 @@ static_assert(4 * (256 + 24) + PSH <= LM_OFF - 192, "shifted P row: piece reads 
 #ifndef SSP_S_AHEAD
 #define SSP_S_AHEAD 1
 #endif
+// Values the fixed-geometry instances read instead of recomputing them every step / every quad (profiles/stream_lane_tables.md):
+//   SSP_S_WTAB     the B operands of the transposed time step — the regression weights phi1(d), phi2(d) of the frame distance d = -19 .. 19 —
+//                  from a 39-entry table of {phi1, phi2} pairs in LDS behind the four waves' regions (StreamArgs::table_bytes).  Every wave
+//                  fills all of it at kernel start with the expressions time_step_T forms, in their order: the same floats.  The waves
+//                  write the same values, and a wave reads only behind its own fill (LDS operations of a wave execute in order): no barrier
+//   SSP_S_LADDR    the lane parts of the DCT operand address, of the ring store (negative on the lanes that store nothing) and of the
+//                  sample DMA offset stay in three registers across the quad loop instead of being rebuilt from the lane id every quad
+//                  (the first-kernel instances without scaling; CM = 1 and WALK = 1 keep the recomputation)
+#ifndef SSP_S_WTAB
+#define SSP_S_WTAB 1
+#endif
+#ifndef SSP_S_LADDR
+#define SSP_S_LADDR 1
+#endif
+constexpr int STREAM_WTAB_N = 39, STREAM_WTAB_BYTES = STREAM_WTAB_N * 8;
+// (instances with the transposed step and at least one delta block: what time_step_T's products need)
+constexpr bool stream_wtab(int melv, int ns, int cm, int walk, int geo) { return SSP_S_WTAB && geo >= 2 && !walk && !cm && !(melv >= 4 && ns >= 4); }
 #define SSP_STR_(x) #x
 #define SSP_STR(x) SSP_STR_(x)
 
@@ -188,6 +207,27 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
     const int lm_pad = FIXG ? 0 : f.lm_pad;
     const float half_inv = 0.5f * a.delta_inv_denom;
     const uint32_t stage_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_ptr_t)stage);
+    // SSP_S_WTAB: entry d + 19 = {phi1(d), phi2(d)}, d = -19 .. 19 (time_step_T: d = g - 4 - j + 4 s), every wave the whole table
+    constexpr bool WTAB = FIXG && stream_wtab(MELV, NS, CM, WALK, GEO);
+    char* wtab = smem + STREAM_WAVES * sa.wave_bytes;
+    if constexpr (WTAB) {
+        const float inv = 2.f * half_inv, inv2 = inv * inv;
+        const float ds = (float)(lane - 19);
+        const float aw = __builtin_fabsf(ds);
+        const float w = __builtin_fmaf(aw, __builtin_fmaf(aw * aw, -1.f / 6.f, 37.f / 6.f), -10.f) * inv2;
+        if (lane < STREAM_WTAB_N) *reinterpret_cast<v2f*>(wtab + 8 * lane) = v2f{__builtin_fabsf(ds) <= 2.f ? ds * inv : 0.f, aw <= 4.f ? w : 0.f};
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    // SSP_S_LADDR: lane addresses of the quad loop, formed once (opaque: the compiler must not fold them back into the lane id)
+    // (not the scaling instances: their code stays what it was)
+    constexpr bool LADDR = FIXG && !WALK && !CM && SSP_S_LADDR;
+    int la_dct = 0, la_put = 0, la_pf = 0;
+    if constexpr (LADDR) {
+        la_dct = (int)(uintptr_t)(lds_ptr_t)(zbuf + (j & 3) * (ZFRAME - 64) + LM_OFF + g * (KS * 4));
+        la_put = j < 4 ? (int)(uintptr_t)(lds_ptr_t)(ring + j * RING_ROW + g * 16) : -1;
+        la_pf = lane * 16;
+        asm volatile("" : "+v"(la_dct), "+v"(la_put), "+v"(la_pf));
+    }
 
 #ifdef SSP_S_CLOCK  // diagnostic build: shader clock (s_memtime) against the 100 MHz constant clock (s_memrealtime) over the kernel's life
     const unsigned long long ck0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
@@ -294,14 +334,14 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
         //  at a time between the window and FFT phases instead — three placements, profiles/stream_fixed_geometry.md — they change nothing)
         auto prefetch = [&](int q) {
             int ol = lane;
-            if (FIXG) asm volatile("" : "+v"(ol));  // (opaque: or the offset becomes an induction variable — one more register live across the loop)
-            const int vo = (ta + 4 * q) * hop * 4 + ol * 16;
+            if (FIXG && !LADDR) asm volatile("" : "+v"(ol));  // (opaque: or the offset becomes an induction variable — one more register live across the loop)
+            const int vo = (ta + 4 * q) * hop * 4 + (LADDR ? la_pf : ol * 16);
             const lds_ptr_t lp = (lds_ptr_t)(uintptr_t)stage_lds;
             if (FIXG) {
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 0, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 1024, 0);
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 2048, 0);
-                if (lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 3072, 0);
+                if (LADDR ? la_pf < 512 : lane < 32) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 3072, 0);  // (lanes 0..31)
                 return;
             }
             if (n_full > 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lp, 16, vo, 0, 0, 0);
@@ -578,13 +618,13 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
             // (lane-derived addresses are recomputed from an opaque copy of the lane id: hoisted out of the loop they would
             //  sit in registers the FFT phases need)
             int ol = lane;
-            asm volatile("" : "+v"(ol));
+            if (!LADDR) asm volatile("" : "+v"(ol));
             const int g = ol >> 4, j = ol & 15;
             const char* lmrow = zbuf + (j & 3) * (ZFRAME - 64) + LM_OFF + g * (KS * 4);
             float lb[KS];
 #pragma unroll
             for (int s = 0; s < KS; s += 2) {
-                const v2f v = *reinterpret_cast<const v2f*>(lmrow + 4 * s);
+                const v2f v = LADDR ? *(lds_c2f_t)(uintptr_t)(uint32_t)(la_dct + 4 * s) : *reinterpret_cast<const v2f*>(lmrow + 4 * s);
                 lb[s] = v.x;
                 lb[s + 1] = v.y;
             }
@@ -620,7 +660,11 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
             int ol = lane;
             asm volatile("" : "+v"(ol));
             const int g = ol >> 4, j = ol & 15;
-            if (j < 4 && on) *reinterpret_cast<v4f*>(ring + qrow + j * RING_ROW + g * 16) = cq;
+            if constexpr (LADDR) {
+                if (la_put >= 0 && on) *(lds_4f_t)(uintptr_t)(uint32_t)(la_put + qrow) = cq;
+            } else {
+                if (j < 4 && on) *reinterpret_cast<v4f*>(ring + qrow + j * RING_ROW + g * 16) = cq;
+            }
             qrow = ring_wrap(qrow + QROW);
         };
         // ================= time step b: rows [16 b - 4, 16 b + 12) of (c, delta, delta-delta) leave =================
@@ -775,12 +819,22 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
                 }
                 store(c, 0);
             }
+            // SSP_S_WTAB: the weights of this lane's six k-steps, entries g - j + 15 + 4 s of the table (the delta-only instances read phi1 alone)
+            v2f wt[6] = {};
+            if constexpr (WTAB) {
+                const char* wl = wtab + 8 * (g - j + 15);
+#pragma unroll
+                for (int s = 0; s < 6; ++s) {
+                    if constexpr (GEO >= 3) wt[s] = *reinterpret_cast<const v2f*>(wl + 32 * s);
+                    else wt[s].x = *reinterpret_cast<const float*>(wl + 32 * s);
+                }
+            }
             if (dord >= 1) {
                 v4f d = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s = 0; s < 6; ++s) {
                     const float ds = ef + (float)(4 * s);
-                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(cb[s], __builtin_fabsf(ds) <= 2.f ? ds * inv : 0.f, d, 0, 0, 0);
+                    d = __builtin_amdgcn_mfma_f32_16x16x4f32(cb[s], WTAB ? wt[s].x : (__builtin_fabsf(ds) <= 2.f ? ds * inv : 0.f), d, 0, 0, 0);
                 }
                 store(d, 1);
             }
@@ -791,7 +845,7 @@ __device__ __forceinline__ void mfcc_stream512_body(const MfccArgs& a, const Fas
                 for (int s = 0; s < 6; ++s) {
                     const float a = __builtin_fabsf(ef + (float)(4 * s));
                     const float w = __builtin_fmaf(a, __builtin_fmaf(a * a, -1.f / 6.f, 37.f / 6.f), -10.f) * inv2;
-                    q = __builtin_amdgcn_mfma_f32_16x16x4f32(cb[s], a <= 4.f ? w : 0.f, q, 0, 0, 0);
+                    q = __builtin_amdgcn_mfma_f32_16x16x4f32(cb[s], WTAB ? wt[s].y : (a <= 4.f ? w : 0.f), q, 0, 0, 0);
                 }
                 store(q, 2);
             }
@@ -1193,7 +1247,7 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
     const bool has_half = (f.slen & 255) != 0 && (f.slen & 255) <= 128;
     sa.stage_bytes = has_half ? (n_piece - 1) * 1024 + 512 : n_piece * 1024;
     sa.wave_bytes = 4 * ZFRAME + sa.stage_bytes + RING_FRAMES * RING_ROW;
-    sa.table_bytes = 0;
+    sa.table_bytes = 0;  // (the weight table of SSP_S_WTAB: below, once the instance is known)
     sa.n_chunks = n_chunks;
     if (!dry_run) {
         // one buffer: a 64-byte head ([0] next chunk to claim, [1] a chunk was flagged) + one flag per chunk, all zeroed by the first
@@ -1205,6 +1259,7 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
     size_t lds = (size_t)sa.table_bytes + (size_t)STREAM_WAVES * sa.wave_bytes;
     if (const char* e = getenv("SSP_MFCC_LDS_PAD")) lds = std::min<size_t>(160 * 1024, lds + (size_t)atoi(e));  // diagnostic: caps the workgroups per CU
     if (lds > 160 * 1024) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc(stream): LDS footprint %zu B exceeds 160 KiB", lds);
+    const size_t lds_waves = lds;  // (what the occupancy choice below is cut for; the weight table comes on top of it)
     if ((int64_t)p->fast_max_samples * 4 > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc(stream): utterance too long for 32-bit offsets");
     const int nz = c.win_len <= 416 ? 13 : 16, pw = c.spec_power, pr = c.preemph_mode ? 1 : 0;
     // three workgroups per CU (52 KiB each, 168 VGPRs) when the stage and the operands allow it, two otherwise
@@ -1213,7 +1268,7 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
     const int cm = args.cmvn != 0 ? 1 : 0;  // (the plan only leaves cmvn set when mfcc_stream_fuses_cmvn and every utterance is one chunk)
     // (the 102 weights per lane of the dense-band instance need the registers of two waves per SIMD)
     // (scaling instances keep three waves per SIMD only where the seven extra registers of the column sums fit without a spill)
-    const int occ = (nz == 13 && KS == 6 && lds <= 53248 && f.melv != 0 && (!cm || (f.melv <= 3 && f.mel_ns <= 2))) ? 3 : 2;
+    const int occ = (nz == 13 && KS == 6 && lds_waves <= 53248 && f.melv != 0 && (!cm || (f.melv <= 3 && f.mel_ns <= 2))) ? 3 : 2;
     const int wg_waves = STREAM_WAVES;
     // geometry as template constants where such an instance exists (the non-scaling ones at three waves per SIMD only); the answer is
     // the same for a dry run and for the launch, and the same in both translation units
@@ -1224,6 +1279,12 @@ int launch_mfcc_stream_impl(const MfccArgs& args, ssp_mfcc_plan* p, int n_chunks
 #endif
     const int geo = (stream_fixed_geo(c, f, args) && KS == 6 && nz == 13 && sa.stage_bytes == 3 * 1024 + 512 && geo_inst &&
                      !stream_geo_excluded(f.melv, f.mel_ns <= 2 ? 2 : 4, cm, 1 + args.delta_order)) ? 1 + args.delta_order : 0;
+    // the weight table behind the wave regions, for both kernels of the launch (same arguments, same LDS): 312 B, and three workgroups
+    // of 53 248 + 312 B still fit the CU's 160 KiB
+    if (stream_wtab(f.melv, f.mel_ns <= 2 ? 2 : 4, cm, 0, geo)) {
+        sa.table_bytes = STREAM_WTAB_BYTES;
+        lds = std::min<size_t>(160 * 1024, lds + (size_t)sa.table_bytes);
+    }
     if (!dry_run && !WALK && geo != 0 && SSP_S_AHEAD && !sa.chunk_rec) SSP_FAIL(SSP_ERR_INVALID, "mfcc(stream): the work table has no chunk records");
     bool launched = false;
 #define SSP_STREAM_CASE(NZ_, PW_, PR_, MV_, KS_, OCC_) SSP_STREAM_CASE_CM(NZ_, PW_, PR_, MV_, KS_, OCC_, 0)
