@@ -60,6 +60,7 @@ typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_gmm_map ssp_gmm_map;
 typedef struct ssp_ivector ssp_ivector;   /* a UBM and a total-variability matrix packed for i-vector extraction and the E-step */
+typedef struct ssp_plda ssp_plda;         /* enrolled speakers of a diagonalised PLDA model packed for the MFMA log-likelihood-ratio sweep */
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
@@ -467,7 +468,7 @@ int ssp_gmm_map_score_list(ssp_gmm_map* map, const void* const* rows, int row_ty
  *   L_u = I + sum_k nk[u,k] P_k,   b_u = G' f_u,   w_u = L_u^-1 b_u  (the i-vector),   logdet_u = log|L_u|,   quad_u = b_u' w_u
  *   objective of a batch = sum_u (-logdet_u / 2 + quad_u / 2): the marginal log-likelihood up to a constant in T; EM never decreases it
  *   E-step accumulators  A_k = sum_u nk[u,k] (L_u^-1 + w_u w_u'),   C = sum_u f_u w_u'  (K x D x R);   M-step (the caller's)  T_k = C_k A_k^-1
- * No covariance update, no minimum-divergence step, no PLDA / WCCN / LDA back end.
+ * No covariance update, no minimum-divergence step.  The back end (LDA, length normalisation, PLDA) is the ssp_plda block below.
  * Every array is a HOST array: the statistics arrive on the host from ssp_gmm_em_stats_shared (device-resident statistics are a
  * follow-up).  ubm_means / ubm_covars double[K x D], T double[K x D x R]; nk double[U x K], sx double[U x K x D]; w_out float[U x R],
  * logdet_out / quad_out float[U] (nullable); A_out double[K x R x R] (full, symmetric), C_out double[K x D x R], objective_out (nullable).
@@ -499,6 +500,70 @@ int ssp_ivector_extract(ssp_ivector* iv, const double* nk, const double* sx, int
                         float* kernel_ms);
 int ssp_ivector_estep(ssp_ivector* iv, const double* nk, const double* sx, int64_t U, double* A_out, double* C_out, double* objective_out,
                       float* kernel_ms);
+
+/* ---- PLDA back end for fixed-length embeddings: class statistics, and log-likelihood-ratio scoring of a diagonalised two-covariance
+ *      model (Ioffe 2006; Prince & Elder 2007; the two-covariance form of Sizov, Lee & Kinnunen 2014; EM after Kaldi's PldaEstimator;
+ *      length normalisation after Garcia-Romero & Espy-Wilson 2011).  An EXTENSION and UNPINNED: the reference has no back end; sidekit
+ *      and Kaldi ship this chain.  The yardstick is a float64 restatement (tests/plda_oracle.py).  It ends the chain that
+ *      ssp_ivector_extract and the d-vector networks begin: embeddings go in, speaker log-likelihood ratios come out. ----
+ * Model.  x = mu + y_s + e,  y_s ~ N(0, B),  e ~ N(0, W);  vectors of dimension q.
+ * Class statistics of rows X (N x q) with labels in [0, S)   (ssp_plda_stats):
+ *   n_s = rows of speaker s;   sum_s = their sum, in float64 IN ROW ORDER (as ssp_centroids);   m_s = sum_s / n_s   (float64)
+ *   mu = (sum_0 + sum_1 + ... + sum_{S-1}) / N, the class sums added in ascending s in float64: the mean of all rows
+ *   S_w = sum_i (x_i - m_{s(i)}) (x_i - m_{s(i)})':  each row is centred in float64 and rounded to fp32 ONCE; S_w is then a transposed-A
+ *   GEMM on exact-fp32 MFMA in k-chunks of 1024 rows, each chunk ONE k-ordered chain, the chunks added in float64 in ascending order.
+ *   A class without rows has count 0 and a zero sum and takes no part in S_w.  No floating-point atomics: same call, same bits.
+ * EM (the caller's, on the host in float64; speech_signal_processing_amd/plda.py) needs only S_w, m_s and n_s.  From W = B = I, per
+ * iteration, with the classes grouped by their distinct count c (k_c classes):  F_c = sum_{s: n_s = c} (m_s - mu)(m_s - mu)',
+ *   V_c = (B^-1 + c W^-1)^-1,  G_c = c V_c W^-1,  H_c = I - G_c,
+ *   B <- [sum_c (k_c V_c + G_c F_c G_c')] / S,    W <- [S_w + sum_c c (k_c V_c + H_c F_c H_c')] / N
+ *   objective (of the W, B the iteration started from; EM never decreases it)
+ *     = sum_s -1/2 [(n_s - 1) log|W| + log|B + W/n_s| + (m_s - mu)' (B + W/n_s)^-1 (m_s - mu)] - 1/2 tr(W^-1 S_w)
+ * Diagonalisation.  W = L L' (Cholesky);  L^-1 B L^-T = U diag(psi) U', psi descending;  A = U' L^-1, so A W A' = I and
+ *   A B A' = diag(psi).  Sign: the largest-magnitude entry of each row of A is positive.
+ * Scoring.  With e_s = A (m_s^enrol - mu) the transformed mean of n_s enrolment vectors and t = A (x - mu):
+ *   mean_{s,d} = n_s psi_d e_{s,d} / (n_s psi_d + 1),    var_{s,d} = 1 + psi_d / (n_s psi_d + 1)
+ *   LLR(t, s) = -1/2 sum_d [log var_{s,d} + (t_d - mean_{s,d})^2 / var_{s,d}] + 1/2 sum_d [log(1 + psi_d) + t_d^2 / (1 + psi_d)]
+ *   packed (ssp_plda_pack, float64 rounded once):  LLR = sum_d beta_{s,d} t_d - 1/2 sum_d alpha_{s,d} t_d^2 + c_s,
+ *   beta = mean / var,   alpha = 1 / var - 1 / (1 + psi),   c_s = -1/2 sum_d [log var - log(1 + psi) + mean^2 / var]
+ *   alpha depends on s only through n_s: speakers with the same count share one alpha row (G distinct counts).
+ * LDA (optional, before PLDA; the caller's, float64): the top p <= min(q, S - 1) generalised eigenvectors of S_b v = lambda S_w v,
+ *   S_b = sum_s n_s (m_s - mu)(m_s - mu)', normalised to v' S_w v = 1, the sign convention of A.
+ * Length normalisation x <- x / |x| comes after centring and LDA and before A.  Centring, projection and normalisation need no entry
+ *   point of their own: ssp_dense_forward (weights = the projection P, bias = -P mu) and ssp_l2_normalize.
+ *
+ * ssp_plda_stats.  X float[N x q], labels int32[N] on the side `where` names (any 4-byte alignment); N >= 1, 1 <= q <= 256 (else
+ *   SSP_ERR_UNSUPPORTED), S >= 1.  The outputs are HOST arrays: sum_out double[S x q], count_out int64[S], mean_out double[q] (mu),
+ *   sw_out double[q x q], full and EXACTLY symmetric.  A label outside [0, S): SSP_ERR_INVALID (found on the device; nothing is
+ *   written).  A non-finite row is not singled out: the outputs are then non-finite, and the Python layer raises ValueError naming the
+ *   row.  With device pointers the kernels queue on the ctx stream; the outputs being host arrays, the call waits ONCE at its end.
+ * ssp_plda_pack.  psi double[q], enrol_mean double[S x q] ALREADY transformed by A, enrol_count int32[S] (HOST arrays).  Forms beta,
+ *   -alpha / 2 and c in float64, rounds each once, lays beta out as MFMA tile images of 32 speakers (cos_pack_kernel's layout),
+ *   de-duplicates alpha into G class rows and a per-speaker class index.  SSP_ERR_INVALID before any GPU work: q or S < 1, a count < 1,
+ *   psi not finite or < 0, a non-finite mean.  SSP_ERR_UNSUPPORTED: q > 256.  flags bit 0 (SSP_PLDA_NO_CLASS_PATH): never use the
+ *   class-shared path below.
+ * ssp_plda_info.  What the pack decided: the number G of distinct enrolment counts, and whether ssp_plda_score takes the class-shared path.
+ * ssp_plda_score.  T float[N x q], ALREADY transformed, on the side `where` names (any 4-byte alignment); llr_out float[N x S]
+ *   (nullable), argmax_out int32[N], max_out float[N] (each nullable).  A wave keeps its 32 test vectors in registers as the MFMA B
+ *   operand; speaker tiles stream through an LDS ring by LDS-DMA; v_mfma_f32_32x32x2_f32, one k-ordered chain per output; the
+ *   epilogue adds c_s and keeps a running (max, first index).  The t^2 term: (a) class-shared, G <= 32: ONE tile of the G alpha rows
+ *   against the squared operand first, parked in a 4 KiB per-wave LDS table that every speaker's epilogue reads at its class; (b)
+ *   general, any G: every speaker tile is followed by its alpha tile against the squared operand into the same accumulator.  Both meet
+ *   the same tolerance; they are not bit-equal to each other.
+ *   Contracts.  A row's llr_out, argmax_out and max_out bits depend on neither N nor the row's place in the batch.  Arg-max ties go
+ *   to the first index; max_out is llr[argmax] bit for bit.  A test row with a non-finite entry gives NaN in its own llr_out row and
+ *   in max_out, and -1 in argmax_out; every other row is BIT-IDENTICAL to the same call with that row replaced by zeros.  No atomics
+ *   on floats.  With device pointers the call is stream-ordered and never waits on the host; SSP_HOST stages the inputs and waits for
+ *   the results.  N == 0 is a no-op.  kernel_ms: device time of the kernels, copies excluded (asking for it waits). */
+#define SSP_PLDA_NO_CLASS_PATH 1
+int ssp_plda_stats(ssp_ctx* ctx, const float* X, const int32_t* labels, int64_t N, int32_t q, int32_t S, double* sum_out,
+                   int64_t* count_out, double* mean_out, double* sw_out, int where, float* kernel_ms);
+int ssp_plda_pack(ssp_ctx* ctx, int32_t q, const double* psi, int32_t S, const double* enrol_mean, const int32_t* enrol_count,
+                  int32_t flags, ssp_plda** out);
+int ssp_plda_destroy(ssp_plda* plda);
+int ssp_plda_info(const ssp_plda* plda, int32_t* n_classes, int32_t* class_shared);
+int ssp_plda_score(ssp_plda* plda, const float* T, int64_t N, float* llr_out, int32_t* argmax_out, float* max_out, int where,
+                   float* kernel_ms);
 
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with

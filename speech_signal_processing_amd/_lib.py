@@ -12,6 +12,7 @@ HOST, DEVICE = 0, 1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 VAD_ZCR_UNGATED = 1
+PLDA_NO_CLASS_PATH = 1
 
 
 class SspError(RuntimeError):
@@ -101,6 +102,11 @@ SIGNATURES = {
     "ssp_ivector_last_stages": (C.c_int, [_P, _MSP]),
     "ssp_ivector_extract": (C.c_int, [_P, _P, _P, C.c_int64, _F32P, _F32P, _F32P, _MSP]),
     "ssp_ivector_estep": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(C.c_double), _MSP]),
+    "ssp_plda_stats": (C.c_int, [_P, _F32P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int, _MSP]),
+    "ssp_plda_pack": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(_P)]),
+    "ssp_plda_destroy": (C.c_int, [_P]),
+    "ssp_plda_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ssp_plda_score": (C.c_int, [_P, _F32P, C.c_int64, _F32P, _P, _F32P, C.c_int, _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

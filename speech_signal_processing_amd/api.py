@@ -1123,6 +1123,111 @@ class IvectorExtractor:
             pass
 
 
+PLDA_MAX_Q = 256  # largest dimension of ssp_plda_stats / ssp_plda_pack (include/ssp.h)
+PLDA_NO_CLASS_PATH = _lib.PLDA_NO_CLASS_PATH  # PldaScorer flags bit 0: never use the class-shared path of the t^2 term
+
+
+def _as_labels(labels, where, n):
+    """-> (int32 array kept alive, raw address) on the side ``where`` names; one label per row"""
+    if where == _lib.DEVICE:
+        import torch
+        if not _is_torch(labels):
+            labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.int32), device="cuda")
+        lab = labels.to(torch.int32).contiguous()
+        ptr = lab.data_ptr()
+    else:
+        lab = np.ascontiguousarray(labels.cpu().numpy() if _is_torch(labels) else labels, dtype=np.int32)
+        ptr = lab.ctypes.data
+    if lab.ndim != 1 or int(lab.shape[0]) != n:
+        raise ValueError("one label per row of X")
+    return lab, ptr
+
+
+def plda_stats(ctx: Context, X, labels, S: int, timing: bool = False) -> dict:
+    """Class statistics for PLDA / LDA training (ssp_plda_stats; include/ssp.h has the definitions).  X (N, q) numpy or torch CUDA
+    tensor, labels (N,) in [0, S).  Returns HOST arrays: "sum" (S, q) float64 (row order), "count" (S,) int64, "mean" (q,) float64 (of
+    all rows), "sw" (q, q) float64, exactly symmetric.  ValueError for a label outside [0, S); q > 256: NotImplementedError.  A
+    non-finite row makes the outputs non-finite (plda.class_stats names the row)."""
+    keep, ptr, where = _as_f32(X, "X")
+    if keep.ndim != 2:
+        raise ValueError("X must be (N, q)")
+    N, q, S = int(keep.shape[0]), int(keep.shape[1]), int(S)
+    lab, lptr = _as_labels(labels, where, N)
+    sm = np.zeros((max(S, 0), q), dtype=np.float64)
+    cnt = np.zeros(max(S, 0), dtype=np.int64)
+    mean = np.zeros(q, dtype=np.float64)
+    sw = np.zeros((q, q), dtype=np.float64)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_plda_stats(ctx._h, ptr, lptr, N, q, S, sm.ctypes.data, cnt.ctypes.data, mean.ctypes.data, sw.ctypes.data, where,
+                                           C.byref(ms) if timing else None))
+    del keep, lab
+    res = {"sum": sm, "count": cnt, "mean": mean, "sw": sw}
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
+class PldaScorer:
+    """Enrolled speakers of a diagonalised PLDA model packed for the log-likelihood-ratio sweep (ssp_plda; an extension the reference
+    does not have).  psi (q,) float64 >= 0, enrol_mean (S, q) float64 ALREADY transformed by A (the mean of each speaker's transformed
+    enrolment vectors), enrol_count (S,) >= 1.  flags: PLDA_NO_CLASS_PATH keeps the t^2 term off the class-shared path."""
+
+    def __init__(self, ctx: Context, psi, enrol_mean, enrol_count, flags: int = 0):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        psi = np.ascontiguousarray(psi, dtype=np.float64)
+        em = np.ascontiguousarray(enrol_mean, dtype=np.float64)
+        ec = np.ascontiguousarray(enrol_count, dtype=np.int32)
+        if psi.ndim != 1 or em.ndim != 2 or em.shape[1] != psi.shape[0] or ec.shape != (em.shape[0],):
+            raise ValueError("expected psi (q,), enrol_mean (S, q), enrol_count (S,)")
+        self.q, self.S = int(psi.shape[0]), int(em.shape[0])
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_plda_pack(ctx._h, self.q, psi.ctypes.data, self.S, em.ctypes.data, ec.ctypes.data, int(flags), C.byref(h)))
+        self._h = h
+        g, shared = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.ssp_plda_info(h, C.byref(g), C.byref(shared)))   # what the pack decided, from the handle
+        self.n_classes, self.class_shared = g.value, bool(shared.value)
+
+    def score(self, T, llr: bool = False, argmax: bool = True, maxval: bool = True, timing: bool = False) -> dict:
+        """T (N, q) ALREADY transformed, numpy or torch CUDA tensor.  Returns a dict of the same kind of arrays: "argmax" (N,) int32 (first
+        index of the row's maximum; -1 for a non-finite test vector), "max" (N,) float32 = llr[argmax] and, with llr=True, "llr" (N, S)
+        float32.  A device call returns without a host wait."""
+        keep, ptr, where = _as_f32(T, "T")
+        if keep.ndim != 2 or keep.shape[1] != self.q:
+            raise ValueError("T must be (N, %d)" % self.q)
+        N = int(keep.shape[0])
+        lr = self.ctx._empty((N, self.S), where) if llr else None
+        am = self.ctx._empty((N,), where, "int32") if argmax else None
+        mx = self.ctx._empty((N,), where) if maxval else None
+        ms = C.c_float(0.0)
+
+        def p(x):
+            return None if x is None else _raw_ptr(x, where)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_plda_score(self._h, ptr, N, p(lr), p(am), p(mx), where,
+                                                C.byref(ms) if timing else None))
+        del keep
+        res = {}
+        for name, v in (("argmax", am), ("max", mx), ("llr", lr)):
+            if v is not None:
+                res[name] = v
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_plda_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def centroids(ctx: Context, X, labels, num: int):
     """avg[s] = mean(X[labels == s]) (float64 accumulator, row order) — d_vector.py:310-313."""
     keep, ptr, where = _as_f32(X, "X")

@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "reg_sweep.hpp"  // f4u, the operand staging and the LDS-DMA of the register-resident sweep
 
 namespace ssp {
 
@@ -19,10 +20,6 @@ constexpr int BM = 128;  // centroid rows per block step
 constexpr int BN = 128;  // embedding columns per workgroup
 constexpr int BK = 32;   // k-chunk
 constexpr int CPL = 128 * 4 + 4;  // floats per (q, h) plane of the operand image (+4 pad: conflict-free staging stores, csrc/dense.hip)
-
-struct __attribute__((packed, aligned(4))) f4u {  // 16-byte load at dword alignment (rows of any length)
-    float x, y, z, w;
-};
 
 struct CosArgs {
     const float* X;    // [N x d]
@@ -220,8 +217,6 @@ __global__ __launch_bounds__(256) void cosine_kernel(CosArgs a) {
 // (32 columns) stay in registers as the MFMA B operand for the whole sweep, the pre-normalised centroids stream through
 // LDS as 32-row A tiles by LDS-DMA (double buffered), so the MFMA pipe sees one ds_read_b128 per 4 MFMAs and no barrier
 // inside a tile.  Same epilogue as above.
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 
 // centroid image: [tile][q][h][row 32][e 4] = c_hat[tile*32 + row][8q + 2e + h]  (unit-norm rows, zero padded)
 __global__ __launch_bounds__(256) void cos_pack_kernel(const float* __restrict__ C, int S, int d, int nq, float* __restrict__ img,
@@ -273,57 +268,16 @@ __global__ __launch_bounds__(256, 3) void cosine_reg_kernel(CosRegArgs a) {
     const int64_t Nn = a.n_dev ? (int64_t)*a.n_dev : a.N;
     if ((int64_t)blockIdx.x * 128 >= Nn) return;  // (whole workgroup: before any barrier)
 
-    // ---- B operand: b[q][e] = x[col][8q + 2e + h]; staged through LDS in 64-wide k chunks so HBM reads stay coalesced
+    // ---- B operand: b[q][e] = x[col][8q + 2e + h] (reg_sweep.hpp), and the squared norm on the way
     float b[NQ][4];
     float ss = 0.f;
-    {
-        float* xs = wbuf + wave * (32 * 65);  // [32 rows][64 + 1 pad]
-#pragma unroll
-        for (int kc = 0; kc < NQ / 8; ++kc) {
-            // 32 rows x 64 floats of this chunk = 512 float4: 8 per lane, all in flight together (a dword per iteration with a
-            // wait after each, as the first version had it, cost a memory latency 128 times per workgroup)
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int idx = lane + 64 * u, r = idx >> 4, k = kc * 64 + 4 * (idx & 15);
-                const int64_t gc = col0 + r;
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (gc < Nn) {
-                    const float* __restrict__ p = a.X + (a.rows ? (int64_t)a.rows[gc] : gc) * d + k;
-                    if (k + 3 < d) {
-                        const f4u t4 = *reinterpret_cast<const f4u*>(p);
-                        v[u] = make_float4(t4.x, t4.y, t4.z, t4.w);
-                    } else {
-                        if (k < d) v[u].x = p[0];
-                        if (k + 1 < d) v[u].y = p[1];
-                        if (k + 2 < d) v[u].z = p[2];
-                        if (k + 3 < d) v[u].w = p[3];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int idx = lane + 64 * u, r = idx >> 4, c = 4 * (idx & 15);
-                float* dst = xs + r * 65 + c;
-                dst[0] = v[u].x;
-                dst[1] = v[u].y;
-                dst[2] = v[u].z;
-                dst[3] = v[u].w;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int q8 = 0; q8 < 8; ++q8)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float v = xs[fl * 65 + 8 * q8 + 2 * e + h];
-                    b[kc * 8 + q8][e] = v;
-                    ss = fmaf(v, v, ss);
-                }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    sweep_load_operand<NQ>(
+        b, wbuf + wave * SWEEP_XS_FLOATS, lane, d,
+        [&](int r) -> const float* {
+            const int64_t gc = col0 + r;
+            return gc < Nn ? a.X + (a.rows ? (int64_t)a.rows[gc] : gc) * d : nullptr;
+        },
+        [&](float v) { ss = fmaf(v, v, ss); });
     ss += __shfl_xor(ss, 32);
     const float ix = 1.0f / sqrtf(ss);
     __syncthreads();  // staging area is about to be overwritten by tile 0
@@ -332,16 +286,7 @@ __global__ __launch_bounds__(256, 3) void cosine_reg_kernel(CosRegArgs a) {
     // workgroup, so three workgroups share a CU and three waves a SIMD's matrix pipe (two full-tile buffers = 64 KiB allowed two)
     constexpr int HALF = TILE_FLOATS / 2;
     const int n_steps = 2 * a.n_tiles;
-    auto stage = [&](int step, int slot) {
-        const float* src = a.img + (size_t)step * HALF;
-        float* dst = wbuf + slot * HALF;
-#pragma unroll
-        for (int p = 0; p < (NQ / 2 + 3) / 4; ++p) {
-            const int piece = wave + 4 * p;
-            if (piece < NQ / 2)
-                __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + piece * 256 + lane * 4), (lds_ptr_t)(dst + piece * 256), 16, 0, 0);
-        }
-    };
+    auto stage = [&](int step, int slot) { sweep_stage_half<NQ>(a.img + (size_t)step * HALF, wbuf + slot * HALF, wave, lane); };
     stage(0, 0);
     stage(1, 1);
     __syncthreads();

@@ -10,6 +10,13 @@ The two halves joined — enrol on i-vectors with the centroid kernel, identify 
     E = tv.transform(enrol_feats, normalize=True)                                    # (U, 64) float32
     cent = api.centroids(api.default_context(), E, enrol_labels, n_speakers)         # ssp_centroids
     who = d_vector.identify(tv.transform(test_feats, normalize=True), cent)          # ssp_cosine_identify
+
+Raw cosine is the weakest way to score i-vectors; the usual chain ends in a PLDA back end (plda.py: LDA, length normalisation, PLDA):
+
+    from speech_signal_processing_amd import plda
+    back = plda.Plda(n_iter=10, lda_dim=48).fit(tv.transform(train_feats), train_labels)       # ssp_plda_stats + host EM
+    scorer = back.enroll(tv.transform(enrol_feats), enrol_labels, n_speakers)                   # ssp_centroids, ssp_plda_pack
+    who = back.identify(scorer, tv.transform(test_feats))                                       # ssp_plda_score
 """
 from __future__ import annotations
 
