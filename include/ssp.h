@@ -565,6 +565,53 @@ int ssp_plda_info(const ssp_plda* plda, int32_t* n_classes, int32_t* class_share
 int ssp_plda_score(ssp_plda* plda, const float* T, int64_t N, float* llr_out, int32_t* argmax_out, float* max_out, int where,
                    float* kernel_ms);
 
+/* ---- Score normalisation against a cohort (S-norm, adaptive S-norm, T-norm, Z-norm) and detection-error counts over a threshold
+ *      grid, for any score matrix: ssp_plda_score's ratios, 1 - ssp_cosine_identify's distances.  An EXTENSION and UNPINNED: the
+ *      reference has neither (its only open-set decision is a fixed cosine threshold); Kaldi, sidekit, SpeechBrain and wespeaker ship
+ *      both.  The yardstick is a restatement (tests/snorm_oracle.py).  Added to ABI 4 without a version step. ----
+ * ssp_topn_stats.  scores float[rows x cols], row-major with leading dimension ld >= cols, on the side `where` names (any 4-byte
+ *   alignment).  axis = 1: one result per row, over its cols entries; axis = 0: one result per column, over its rows entries (read at
+ *   stride ld).  For a line of length L let m = min(n, L) and v_1 >= ... >= v_m its m largest entries as a multiset (ties make the set
+ *   of indices ambiguous, not the values):
+ *     kth = v_m, bit for bit an entry of the line (-0.0 and +0.0 compare equal: either may be returned)
+ *     mean = kth + (1/m) sum_i (v_i - kth)          std = sqrt((1/m) sum_i (v_i - mean)^2)   (population form; the square sum is
+ *     taken about the mean in a second pass, never as E[v^2] - mean^2; a constant line has std exactly 0)
+ *   One wave per line: order-preserving 32-bit keys, the m-th largest key by bisection over the 32 key bits (exact), then sums of a
+ *   fixed shape in fp32 (lane l adds entries l, l + 64, ... in that order, then a butterfly over the lanes; the copies of kth that
+ *   complete the multiset are added last).  Lines up to 4096 entries stay in registers, longer ones are read again per pass.
+ *   mean_out, std_out, kth_out float[rows] (axis 1) or float[cols] (axis 0), each nullable.
+ *   A line with a non-finite entry gives NaN in its own mean, std and kth; every other line is BIT-IDENTICAL to the same call with
+ *   that line replaced by zeros.  A line's bits depend on neither the number of lines nor its place.  No atomics: same call, same bits.
+ *   SSP_ERR_INVALID before any GPU work: n < 1, rows < 0, cols < 1, ld < cols, axis not 0 or 1.  SSP_ERR_UNSUPPORTED: lines longer
+ *   than 65536 (cols for axis 1, rows for axis 0).  rows == 0 is a no-op.
+ * ssp_snorm_apply.  scores float[N x S] (ld >= S).  In fp32, operation by operation, IEEE division, no contraction:
+ *     z[t,s] = 0.5f * ((x - col_mean[s]) / max(col_std[s], std_floor) + (x - row_mean[t]) / max(row_std[t], std_floor))
+ *   row_mean / row_std float[N] are the test side (T-norm), col_mean / col_std float[S] the enrolment side (Z-norm); either PAIR may be
+ *   NULL, the other term is then the whole result without the 0.5.  Both NULL, or half a pair: SSP_ERR_INVALID.  std_floor must be
+ *   finite and > 0.  max is numpy's: a NaN deviation gives NaN.  out float[N x S] (ld_out >= S; nullable) may be `scores` itself with
+ *   ld_out == ld.  argmax_out int32[N], max_out float[N] (each nullable): over the entries of the row that are not NaN, ties to the
+ *   first index, max_out = z[argmax] bit for bit; a row without such an entry gives -1 and NaN.  A NaN in one row's statistics touches
+ *   that row only, one in a column's statistics that column only.  N == 0 is a no-op.
+ * ssp_det_counts.  scores float[N x S] (ld >= S) and target int32[N] on the side `where` names: target[t] is the enrolled speaker row t
+ *   belongs to, -1 for none (every trial of the row is then a non-target); anything else outside [0, S): SSP_ERR_INVALID (found on the
+ *   device; nothing is written).  thresholds: HOST float[M], ascending and finite, 0 <= M <= 4096 (else SSP_ERR_INVALID before any GPU
+ *   work).  Bin of a score: b(x) = #{j : thresholds[j] <= x} in [0, M] (numpy.searchsorted, side = "right").  Outputs, all HOST arrays:
+ *   tar_hist / non_hist int64[M + 1]: target and non-target trials per bin; nan_count int64[2]: NaN scores (target, non-target), counted
+ *   apart; range_out float[4]: minimum and maximum of the target scores that are not NaN, then of the non-target ones (+inf / -inf
+ *   where there is none).  Thresholds and per-workgroup histograms sit in LDS (integer LDS adds), one 64-bit integer add per bin and
+ *   workgroup follows: the counts are exact.  M = 0 gives the totals and the ranges only.
+ * Contracts of all three, as ssp_plda_score: device pointers at any 4-byte alignment; with device pointers ssp_topn_stats and
+ *   ssp_snorm_apply are stream-ordered and never wait on the host, ssp_det_counts (host outputs) waits ONCE at its end; SSP_HOST stages
+ *   the inputs and waits for the results.  An error leaves the ctx usable.  kernel_ms: device time of the kernels, copies excluded
+ *   (asking for it waits). */
+int ssp_topn_stats(ssp_ctx* ctx, const float* scores, int64_t rows, int32_t cols, int64_t ld, int32_t axis, int32_t n, float* mean_out,
+                   float* std_out, float* kth_out, int where, float* kernel_ms);
+int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int64_t ld, const float* row_mean, const float* row_std,
+                    const float* col_mean, const float* col_std, float std_floor, float* out, int64_t ld_out, int32_t* argmax_out,
+                    float* max_out, int where, float* kernel_ms);
+int ssp_det_counts(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int64_t ld, const int32_t* target, const float* thresholds,
+                   int32_t M, int64_t* tar_hist, int64_t* non_hist, int64_t* nan_count, float* range_out, int where, float* kernel_ms);
+
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with
  * the random numbers handed in.  feats: float[n_rows x D] on the side `where` names (any 4-byte alignment).  Problem p has n_sel[p] rows:

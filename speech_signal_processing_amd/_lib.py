@@ -107,6 +107,10 @@ SIGNATURES = {
     "ssp_plda_destroy": (C.c_int, [_P]),
     "ssp_plda_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ssp_plda_score": (C.c_int, [_P, _F32P, C.c_int64, _F32P, _P, _F32P, C.c_int, _MSP]),
+    "ssp_topn_stats": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, _F32P, C.c_int, _MSP]),
+    "ssp_snorm_apply": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int64, _F32P, _F32P, _F32P, _F32P, C.c_float, _F32P, C.c_int64, _P, _F32P,
+                                  C.c_int, _MSP]),
+    "ssp_det_counts": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int, _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

@@ -1228,6 +1228,122 @@ class PldaScorer:
             pass
 
 
+TOPN_MAX_LINE = 65536  # longest line of ssp_topn_stats (include/ssp.h)
+DET_MAX_THRESHOLDS = 4096  # most thresholds of ssp_det_counts
+
+
+def _as_matrix(x, name):
+    """-> (array kept alive, raw address, where, leading dimension) of a 2-D float32 matrix.  A view whose rows are contiguous and at
+    least one row apart (a column slice of a wider matrix) is passed as it is, with its row stride as the leading dimension."""
+    if getattr(x, "ndim", 0) != 2:
+        raise ValueError("%s must be a matrix" % name)
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    if _is_torch(x):
+        import torch
+        if x.is_cuda and x.dtype == torch.float32 and cols >= 1 and x.stride(1) == 1 and (rows <= 1 or x.stride(0) >= cols):
+            return x, x.data_ptr(), _lib.DEVICE, (int(x.stride(0)) if rows > 1 else cols)
+    elif isinstance(x, np.ndarray) and x.dtype == np.float32 and cols >= 1 and x.strides[1] == 4 and (
+            rows <= 1 or (x.strides[0] >= 4 * cols and x.strides[0] % 4 == 0)):
+        return x, x.ctypes.data, _lib.HOST, (x.strides[0] // 4 if rows > 1 else cols)
+    keep, ptr, where = _as_f32(x, name)
+    return keep, ptr, where, max(cols, 1)
+
+
+def _as_vector(x, name, n, where):
+    """-> (float32 array kept alive, raw address) of n entries on the side ``where`` names"""
+    keep, ptr, w = _as_f32(x, name)
+    if w != where:
+        raise ValueError("%s must live where the scores live (numpy with numpy, torch CUDA with torch CUDA)" % name)
+    if keep.ndim != 1 or int(keep.shape[0]) != n:
+        raise ValueError("%s must have %d entries" % (name, n))
+    return keep, ptr
+
+
+def topn_stats(ctx: Context, scores, n: int, axis: int = 1, timing: bool = False) -> dict:
+    """Mean, population deviation and smallest member of the ``n`` largest entries of every row (axis=1) or column (axis=0) of a score
+    matrix (ssp_topn_stats; include/ssp.h has the definitions): the cohort statistics of adaptive score normalisation.  scores (rows,
+    cols) numpy or torch CUDA tensor (a row-strided view is read in place).  Returns "mean", "std", "kth", float32, one entry per line,
+    of the same kind of array.  A line with a non-finite entry gives NaN.  A device call returns without a host wait."""
+    keep, ptr, where, ld = _as_matrix(scores, "scores")
+    rows, cols = int(keep.shape[0]), int(keep.shape[1])
+    lines = rows if axis == 1 else cols
+    out = [ctx._empty((max(lines, 0),), where) for _ in range(3)]
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_topn_stats(ctx._h, ptr, rows, cols, ld, int(axis), int(n), *[_raw_ptr(o, where) for o in out], where,
+                                           C.byref(ms) if timing else None))
+    del keep
+    res = dict(zip(("mean", "std", "kth"), out))
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
+def snorm_apply(ctx: Context, scores, row_mean=None, row_std=None, col_mean=None, col_std=None, std_floor: float = 1e-6, out=True,
+                argmax: bool = True, maxval: bool = True, timing: bool = False) -> dict:
+    """z = 0.5 ((x - col_mean) / max(col_std, floor) + (x - row_mean) / max(row_std, floor)) and its row-wise decision (ssp_snorm_apply).
+    Row statistics alone give T-norm, column statistics alone Z-norm (no 0.5 then).  out: True — a new matrix; False — no matrix, only
+    the decision; a float32 matrix of scores' kind and shape — written in place (``scores`` itself is allowed).  Returns {"argmax" (N,)
+    int32 over the entries that are not NaN, first index on ties, -1 for none; "max" (N,) = z[argmax]; "scores" (N, S)}."""
+    keep, ptr, where, ld = _as_matrix(scores, "scores")
+    N, S = int(keep.shape[0]), int(keep.shape[1])
+    if (row_mean is None) != (row_std is None) or (col_mean is None) != (col_std is None):
+        raise ValueError("a mean needs its deviation")
+    rm = rs = cm = cs = (None, None)
+    if row_mean is not None:
+        rm, rs = _as_vector(row_mean, "row_mean", N, where), _as_vector(row_std, "row_std", N, where)
+    if col_mean is not None:
+        cm, cs = _as_vector(col_mean, "col_mean", S, where), _as_vector(col_std, "col_std", S, where)
+    z, zp, ldz = None, None, S
+    if out is True:
+        z = ctx._empty((N, S), where)
+        zp = _raw_ptr(z, where)
+    elif out is not False and out is not None:
+        z, zp, zwhere, ldz = _as_matrix(out, "out")
+        if z is not out or zwhere != where or tuple(z.shape) != (N, S):
+            raise ValueError("out must be a float32 matrix of scores' shape and kind with contiguous rows")
+    am = ctx._empty((N,), where, "int32") if argmax else None
+    mx = ctx._empty((N,), where) if maxval else None
+    ms = C.c_float(0.0)
+
+    def p(x):
+        return None if x is None else _raw_ptr(x, where)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_snorm_apply(ctx._h, ptr, N, S, ld, rm[1], rs[1], cm[1], cs[1], float(std_floor), zp, ldz, p(am), p(mx), where,
+                                            C.byref(ms) if timing else None))
+    del keep, rm, rs, cm, cs
+    res = {}
+    for name, v in (("argmax", am), ("max", mx), ("scores", z)):
+        if v is not None:
+            res[name] = v
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
+def det_counts(ctx: Context, scores, target, thresholds=(), timing: bool = False) -> dict:
+    """Target and non-target trials per threshold bin (ssp_det_counts): scores (N, S) numpy or torch CUDA tensor, target (N,) the enrolled
+    speaker each row belongs to (-1: none), thresholds ascending float32, at most 4096 (none: totals and ranges only).  Returns HOST
+    arrays: "tar_hist" / "non_hist" (M + 1,) int64 with bin = searchsorted(thresholds, x, "right"), "nan_count" (2,) int64, "range" (4,)
+    float32 (min, max of the target scores, then of the non-target scores) and "thresholds".  ValueError for a target outside [-1, S)."""
+    keep, ptr, where, ld = _as_matrix(scores, "scores")
+    N, S = int(keep.shape[0]), int(keep.shape[1])
+    lab, lptr = _as_labels(target, where, N)
+    th = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+    M = int(th.shape[0])
+    tar, non = np.zeros(M + 1, dtype=np.int64), np.zeros(M + 1, dtype=np.int64)
+    nan, rng = np.zeros(2, dtype=np.int64), np.zeros(4, dtype=np.float32)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_det_counts(ctx._h, ptr, N, S, ld, lptr, th.ctypes.data, M, tar.ctypes.data, non.ctypes.data, nan.ctypes.data,
+                                           rng.ctypes.data, where, C.byref(ms) if timing else None))
+    del keep, lab
+    res = {"tar_hist": tar, "non_hist": non, "nan_count": nan, "range": rng, "thresholds": th}
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 def centroids(ctx: Context, X, labels, num: int):
     """avg[s] = mean(X[labels == s]) (float64 accumulator, row order) — d_vector.py:310-313."""
     keep, ptr, where = _as_f32(X, "X")
