@@ -612,6 +612,58 @@ int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int
 int ssp_det_counts(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int64_t ld, const int32_t* target, const float* thresholds,
                    int32_t M, int64_t* tar_hist, int64_t* non_hist, int64_t* nan_count, float* range_out, int where, float* kernel_ms);
 
+/* ---- Speaker diarization: the scores of all segment pairs of a recording and agglomerative hierarchical clustering (AHC) of them, for
+ *      a batch of recordings ("who spoke when" for speakers that are not enrolled: Kaldi's diarization/ recipe — short windows, one
+ *      embedding each, PLDA or cosine scores of all pairs, AHC to a threshold or a known speaker count).  An EXTENSION and UNPINNED:
+ *      the reference has no diarization; Kaldi, sidekit, SpeechBrain and wespeaker ship it on the same chain.  The yardstick is a
+ *      restatement (tests/diarize_oracle.py), corroborated by SciPy's linkage.  Added to ABI 4 without a version step. ----
+ * Layout.  seg holds R recordings; recording r owns rows offsets[r] .. offsets[r + 1] of the embedding matrix, n_r of them.  Score
+ *   matrices are packed: recording r's n_r x n_r row-major dense block starts at float offset sq_off[r] = sum_{k < r} n_k^2.
+ *   ssp_pairwise_size returns sum_r n_r^2.
+ * ssp_pairwise_scores.  X float[offsets[R] x q] on the side `where` names; g, h HOST float[q] (NULL: ones / zeros).  For i, j of the
+ *   same recording:   S[i,j] = sum_d g_d x_id x_jd - (r_i + r_j) + c0,   r_i = sum_d h_d x_id^2.
+ *   Cosine: g = h = NULL, c0 = 0 on rows that went through ssp_l2_normalize.  PLDA: with the diagonalised model's psi and ONE enrolment
+ *   vector (n_s = 1 in the scoring formulas above) the log-likelihood ratio of two projected vectors is symmetric and has this form with
+ *     g = psi / (2 psi + 1),   h = 1/2 psi^2 / ((psi + 1)(2 psi + 1)),   c0 = -1/2 sum_d log((2 psi_d + 1) / (psi_d + 1)^2).
+ *   Blocks of 64 x 64 pairs on or above the diagonal, four waves with one 32 x 32 tile each on v_mfma_f32_32x32x2_f32 (the tile below the
+ *   diagonal of a diagonal block is not computed), ONE k-ordered chain per output, ascending d; q is walked in panels of 32 through LDS;
+ *   g scales the first operand (rounded once per entry); r_i is summed in float64 and rounded once; the epilogue takes
+ *   acc - (r_i + r_j) + c0 and writes the one value to [i][j] and [j][i].
+ *   Contracts.  Every block of out is EXACTLY symmetric.  A block's bits depend on neither R nor the recording's place in the batch.  A
+ *   non-finite entry in row i makes row i and column i of its block NaN; every other entry is BIT-IDENTICAL to the same call with that
+ *   row zeroed.  No float atomics: same call, same bits.  R == 0 or a recording with n_r == 0 is a no-op.
+ *   SSP_ERR_INVALID before any GPU work: q < 1, g / h / c0 not finite.  SSP_ERR_UNSUPPORTED: q > 1024, a recording with n_r > 4096.
+ * ssp_ahc_cluster.  scores: packed as above, not modified; only the entries [i][j] with i < j are read.  Per recording:
+ *   Start: the n segments are clusters of size 1, s(i, j) = scores[i][j] for i < j.
+ *   lo = n_speakers[r] if n_speakers is given and n_speakers[r] > 0, else max(1, min_clusters);  thr = -inf in the first case, else
+ *   threshold.  While the cluster count > lo: take the live pair (a, b), a < b, with the largest s, ties to the smallest a, then the
+ *   smallest b; stop unless s(a,b) >= thr; merge b into a (the cluster keeps index a) and for every other live k
+ *     linkage 0 (average):  s(a,k) = (fa s(a,k) + fb s(b,k)) / (fa + fb) in fp32, fa = (float)size_a, fb = (float)size_b, every multiply,
+ *                           add and divide rounded (no contraction, IEEE division)
+ *     linkage 1 (complete): min(s(a,k), s(b,k))          linkage 2 (single): max(s(a,k), s(b,k))
+ *   Outputs.  labels_out int32[offsets[R]]: the rank of the segment's cluster among the final clusters ordered by their smallest member;
+ *   n_clusters_out int32[R]; merge m of recording r writes (a, b) to row offsets[r] + m of merge_pair_out int32[offsets[R] x 2] and
+ *   s(a,b) to merge_score_out float[offsets[R]] (each nullable); unused rows get (-1, -1) and NaN.  n = 0 writes nothing; n = 1 gives
+ *   label 0 and count 1.  An n_speakers[r] above n_r simply means no merge.  n_speakers is a HOST array.
+ *   Non-finite scores.  A recording with a non-finite entry above its diagonal gets label -1 on all segments, count -1 and every merge
+ *   row unused; every other recording is unaffected, bit for bit.
+ *   Kernel.  One 256-thread workgroup per recording, the longest first, no communication between workgroups, no spin or claim loops;
+ *   every loop has a trip count known on entry (at most n - 1 merges).  The working copy sits in LDS up to n = 192 (row stride n | 1)
+ *   and in a workspace the ctx owns above that.  A per-row best (order-preserving key, lowest column) over the live columns j > i sits in
+ *   LDS; the arg-max of a merge is one 64-bit integer max over (key << 32 | ~row).  After a merge row a and the rows whose best pointed at
+ *   a or b are rescanned, the others compare their one changed entry (an equal entry wins if its column is lower).  -0.0 counts as +0.0.
+ *   SSP_ERR_INVALID before any GPU work: linkage not 0..2, a NaN threshold (+-inf are allowed), min_clusters < 1, an n_speakers[r] < 0.
+ *   SSP_ERR_UNSUPPORTED: a recording with n_r > 4096.
+ * Contracts of both, as ssp_plda_score: device pointers at any 4-byte alignment; with device pointers the calls are stream-ordered and
+ *   never wait on the host (once the ctx's tables and workspace have grown to the batch); SSP_HOST stages the inputs and waits for the
+ *   results.  An error leaves the ctx usable.  kernel_ms: device time of the kernels, copies excluded (asking for it waits). */
+int ssp_pairwise_size(const ssp_segments* seg, int64_t* total_out);
+int ssp_pairwise_scores(ssp_ctx* ctx, const float* X, const ssp_segments* seg, int32_t q, const float* g, const float* h, float c0,
+                        float* out, int where, float* kernel_ms);
+int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, int32_t linkage, float threshold, int32_t min_clusters,
+                    const int32_t* n_speakers, int32_t* labels_out, int32_t* n_clusters_out, int32_t* merge_pair_out,
+                    float* merge_score_out, int where, float* kernel_ms);
+
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with
  * the random numbers handed in.  feats: float[n_rows x D] on the side `where` names (any 4-byte alignment).  Problem p has n_sel[p] rows:

@@ -111,6 +111,9 @@ SIGNATURES = {
     "ssp_snorm_apply": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int64, _F32P, _F32P, _F32P, _F32P, C.c_float, _F32P, C.c_int64, _P, _F32P,
                                   C.c_int, _MSP]),
     "ssp_det_counts": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int, _MSP]),
+    "ssp_pairwise_size": (C.c_int, [_P, _I64P]),
+    "ssp_pairwise_scores": (C.c_int, [_P, _F32P, _P, C.c_int32, _P, _P, C.c_float, _F32P, C.c_int, _MSP]),
+    "ssp_ahc_cluster": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, C.c_int32, _P, _P, _P, _P, _F32P, C.c_int, _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

@@ -1344,6 +1344,120 @@ def det_counts(ctx: Context, scores, target, thresholds=(), timing: bool = False
     return res
 
 
+PAIRWISE_MAX_Q = 1024   # largest dimension of ssp_pairwise_scores (include/ssp.h)
+AHC_MAX_SEGMENTS = 4096  # most segments of one recording (ssp_pairwise_scores, ssp_ahc_cluster)
+AHC_N_LDS = 192          # recordings up to this many segments are clustered in LDS, longer ones in the context's workspace
+AHC_LINKAGES = {"average": 0, "complete": 1, "single": 2}
+
+
+def _as_recordings(ctx: Context, seg_or_counts) -> Segments:
+    """a Segments object as it is, anything else as the segments per recording"""
+    if isinstance(seg_or_counts, Segments):
+        return seg_or_counts
+    counts = np.asarray(seg_or_counts, dtype=np.int64).reshape(-1)
+    if counts.size and counts.min() < 0:
+        raise ValueError("a recording with a negative number of segments")
+    return Segments.from_lengths(ctx, counts)
+
+
+def pairwise_size(seg: Segments) -> int:
+    """sum of n_r^2 over the recordings (ssp_pairwise_size): the floats of a packed batch of score matrices"""
+    t = C.c_int64()
+    _lib.check(seg._lib.ssp_pairwise_size(seg._h, C.byref(t)))
+    return t.value
+
+
+def pairwise_offsets(seg: Segments) -> np.ndarray:
+    """int64[R + 1]: float offset of every recording's block in a packed batch of score matrices"""
+    n = np.diff(seg.offsets)
+    out = np.zeros(seg.n + 1, dtype=np.int64)
+    np.cumsum(n * n, out=out[1:])
+    return out
+
+
+def pairwise_scores(ctx: Context, X, seg_or_counts, g=None, h=None, c0: float = 0.0, out=None, timing: bool = False):
+    """S[i,j] = sum_d g_d x_id x_jd - (r_i + r_j) + c0, r_i = sum_d h_d x_id^2, for every pair of rows of the same recording
+    (ssp_pairwise_scores; include/ssp.h has the definition).  X (total, q) numpy or torch CUDA tensor; seg_or_counts a Segments object
+    or the rows per recording; g, h host vectors of q entries (None: ones / zeros): g = h = None on L2-normalised rows is the cosine,
+    plda.Plda.pairwise_coeffs() gives the PLDA log-likelihood ratio.  Returns the packed blocks as one flat float32 array of X's kind
+    (recording r's n_r x n_r block at pairwise_offsets(seg)[r]); out: such an array to write into.  A device call given a Segments
+    object returns without a host wait (counts make one per call, which uploads and waits)."""
+    keep, ptr, where = _as_f32(X, "X")
+    if keep.ndim != 2:
+        raise ValueError("X must be (total, q)")
+    seg = _as_recordings(ctx, seg_or_counts)
+    q = int(keep.shape[1])
+    if int(keep.shape[0]) != seg.total:
+        raise ValueError("X has %d rows, the recordings %d" % (int(keep.shape[0]), seg.total))
+    vec = []
+    for name, v in (("g", g), ("h", h)):
+        if v is None:
+            vec.append(None)
+            continue
+        v = np.ascontiguousarray(v.cpu().numpy() if _is_torch(v) else v, dtype=np.float32).reshape(-1)
+        if v.shape[0] != q:
+            raise ValueError("%s must have %d entries" % (name, q))
+        vec.append(v)
+    total = pairwise_size(seg)
+    if out is None:
+        out = ctx._empty((total,), where)
+    else:
+        ok = (_is_torch(out) and where == _lib.DEVICE and out.is_cuda and str(out.dtype) == "torch.float32" and out.is_contiguous()) or (
+            isinstance(out, np.ndarray) and where == _lib.HOST and out.dtype == np.float32 and out.flags.c_contiguous)
+        if not ok or int(np.prod(out.shape)) != total:
+            raise ValueError("out must be a contiguous float32 array of X's kind with %d entries" % total)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_pairwise_scores(ctx._h, ptr, seg._h, q, None if vec[0] is None else vec[0].ctypes.data,
+                                                None if vec[1] is None else vec[1].ctypes.data, float(c0), _raw_ptr(out, where), where,
+                                                C.byref(ms) if timing else None))
+    del keep
+    return (out, ms.value) if timing else out
+
+
+def ahc_cluster(ctx: Context, scores, seg_or_counts, linkage: str = "average", threshold: float = 0.0, min_clusters: int = 1,
+                n_speakers=None, merges: bool = False, timing: bool = False) -> dict:
+    """Agglomerative hierarchical clustering of every recording of a packed batch of score matrices, one workgroup per recording
+    (ssp_ahc_cluster; include/ssp.h has the definition).  scores: what pairwise_scores returns, numpy or torch CUDA tensor.  Merging
+    goes on while the best pair scores >= threshold and more than min_clusters clusters are left; n_speakers (one entry per recording,
+    0 = not known) fixes the count of a recording instead.  Returns "labels" (total,) int32 — clusters numbered by their smallest
+    member; -1 for a recording with a non-finite score — and "n_clusters" (R,) int32, with merges=True also "merge_pair" (total, 2)
+    int32 and "merge_score" (total,) float32: merge m of recording r in row offsets[r] + m, unused rows (-1, -1) and NaN.  The arrays
+    are of scores' kind; a device call given a Segments object returns without a host wait."""
+    if linkage not in AHC_LINKAGES:
+        raise ValueError("linkage must be one of %s" % sorted(AHC_LINKAGES))
+    keep, ptr, where = _as_f32(scores, "scores")
+    seg = _as_recordings(ctx, seg_or_counts)
+    if int(np.prod(keep.shape)) != pairwise_size(seg):
+        raise ValueError("scores has %d entries, the recordings' blocks %d" % (int(np.prod(keep.shape)), pairwise_size(seg)))
+    ns = None
+    if n_speakers is not None:
+        ns = np.ascontiguousarray(n_speakers, dtype=np.int32).reshape(-1)
+        if ns.shape[0] != seg.n:
+            raise ValueError("n_speakers must have one entry per recording")
+    total = seg.total
+    lab = ctx._empty((total,), where, "int32")
+    cnt = ctx._empty((seg.n,), where, "int32")
+    cnt[...] = 0   # (a recording without segments is not written)
+    mp = ctx._empty((total, 2), where, "int32") if merges else None
+    msc = ctx._empty((total,), where) if merges else None
+    ms = C.c_float(0.0)
+
+    def p(x):
+        return None if x is None else _raw_ptr(x, where)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_ahc_cluster(ctx._h, ptr, seg._h, AHC_LINKAGES[linkage], float(threshold), int(min_clusters),
+                                            None if ns is None else ns.ctypes.data, p(lab), p(cnt), p(mp), p(msc), where,
+                                            C.byref(ms) if timing else None))
+    del keep
+    res = {"labels": lab, "n_clusters": cnt}
+    if merges:
+        res["merge_pair"], res["merge_score"] = mp, msc
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 def centroids(ctx: Context, X, labels, num: int):
     """avg[s] = mean(X[labels == s]) (float64 accumulator, row order) — d_vector.py:310-313."""
     keep, ptr, where = _as_f32(X, "X")

@@ -145,6 +145,10 @@ struct ssp_ctx {
     // input projection of the GRU layer that is running (gru.hip): grow-only, shared by the layers of a network, which run one after
     // the other on the ctx stream
     ssp::DevBuf gru_proj;
+    // diarization (diarize.hip): the per-call tables and their host image, the row terms of ssp_pairwise_scores, and the working copies of
+    // the recordings ssp_ahc_cluster cannot keep in LDS; grow-only
+    ssp::DevBuf diar_tab, diar_r, diar_ws;
+    std::vector<char> diar_host;
     mutable ssp::StagePool stage;  // staging buffers of SSP_HOST calls
     int32_t* pinned_words = nullptr;  // 64 bytes of pinned host memory for small read-backs (precision-auto pilots)
     ssp::HostPipe* pipe = nullptr;  // slots / streams of the sliced host-fed MFCC path (staging.hpp; made on first use)

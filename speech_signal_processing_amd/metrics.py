@@ -10,6 +10,8 @@ apart and excluded from both totals.
     counts = metrics.det_counts(scores, target)          # scores (N, S), target (N,) in [0, S) or -1
     rate, threshold = metrics.eer(counts)
     cost = metrics.min_dcf(counts, p_target=0.01)
+
+diarization_error(ref, hyp) is the frame-level diarization error of two label sequences (host only; diarize.py produces such labels).
 """
 from __future__ import annotations
 
@@ -73,3 +75,32 @@ def min_dcf(counts, p_target=0.01, c_miss=1.0, c_fa=1.0):
         return float("nan")
     cost = c_miss * p_target * miss + c_fa * (1.0 - p_target) * fa
     return float(np.min(cost) / min(c_miss * p_target, c_fa * (1.0 - p_target)))
+
+
+def diarization_error(ref, hyp) -> dict:
+    """Frame-level diarization error, no collar, on the host: ref and hyp are integer label arrays of one entry per frame, -1 for
+    silence.  The hypothesis speakers are mapped one-to-one onto the reference speakers so that the frames on which both agree are as
+    many as possible (scipy.optimize.linear_sum_assignment).  -> {"miss", "false_alarm", "confusion", "der"}: reference speech
+    frames the hypothesis calls silence, hypothesis speech frames the reference calls silence, frames both call speech but of
+    different (mapped) speakers, and their sum, each divided by the number of reference speech frames (NaN when there is none)."""
+    ref = np.asarray(ref).reshape(-1).astype(np.int64)
+    hyp = np.asarray(hyp).reshape(-1).astype(np.int64)
+    if ref.shape != hyp.shape:
+        raise ValueError("ref and hyp must have one label per frame each")
+    if (ref < -1).any() or (hyp < -1).any():
+        raise ValueError("labels must be >= 0, or -1 for silence")
+    rs, hs = ref >= 0, hyp >= 0
+    miss, fa, both = int((rs & ~hs).sum()), int((~rs & hs).sum()), rs & hs
+    matched = 0
+    if both.any():
+        from scipy.optimize import linear_sum_assignment   # (host-only helper: imported where it is needed, as VAD.py does)
+        ru, ri = np.unique(ref[both], return_inverse=True)
+        hu, hi = np.unique(hyp[both], return_inverse=True)
+        agree = np.zeros((ru.size, hu.size), dtype=np.int64)
+        np.add.at(agree, (ri, hi), 1)
+        rows, cols = linear_sum_assignment(agree, maximize=True)
+        matched = int(agree[rows, cols].sum())
+    conf = int(both.sum()) - matched
+    n_ref = int(rs.sum())
+    den = np.float64(n_ref) if n_ref else np.float64("nan")
+    return {"miss": float(miss / den), "false_alarm": float(fa / den), "confusion": float(conf / den), "der": float((miss + fa + conf) / den)}

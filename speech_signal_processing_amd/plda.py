@@ -110,6 +110,17 @@ def diagonalise(W, B):
     return A, np.maximum(psi, 0.0)
 
 
+def pairwise_coeffs(psi):
+    """Plda.pairwise_coeffs for a given psi (q,) >= 0"""
+    psi = np.asarray(psi, dtype=np.float64)
+    if psi.ndim != 1 or not np.isfinite(psi).all() or (psi < 0).any():
+        raise ValueError("psi must be a finite vector >= 0")
+    g = psi / (2.0 * psi + 1.0)
+    h = 0.5 * psi * psi / ((psi + 1.0) * (2.0 * psi + 1.0))
+    c0 = -0.5 * float(np.sum(np.log(2.0 * psi + 1.0) - 2.0 * np.log1p(psi)))
+    return g.astype(np.float32), h.astype(np.float32), float(np.float32(c0))
+
+
 class Lda:
     """Linear discriminant analysis from the device's class statistics: the top ``n_components`` generalised eigenvectors of
     S_b v = lambda S_w v, v' S_w v = 1.  ``mean_`` (q,), ``components_`` (q, p) and ``eigenvalues_`` (p,) are set by fit."""
@@ -222,6 +233,14 @@ class Plda:
     def project(self, X):
         self._check_fitted()
         return _affine(self.ctx, self._front(X), self.transform_, -(self.transform_ @ self.plda_mean_))
+
+    def pairwise_coeffs(self):
+        """-> (g, h, c0) of api.pairwise_scores for the log-likelihood ratio of two PROJECTED vectors, one of them the single enrolment
+        vector of a speaker (symmetric in the two):  LLR = sum_d g_d x_d y_d - sum_d h_d (x_d^2 + y_d^2) + c0 with
+        g = psi / (2 psi + 1), h = psi^2 / (2 (psi + 1)(2 psi + 1)), c0 = -1/2 sum_d log((2 psi_d + 1) / (psi_d + 1)^2); formed in
+        float64 and rounded once: g, h float32 (q,), c0 a float"""
+        self._check_fitted()
+        return pairwise_coeffs(self.psi_)
 
     def enroll(self, X, labels, n_speakers, flags=0):
         """-> api.PldaScorer of ``n_speakers`` speakers: the means of their projected vectors (ssp_centroids) and their counts"""
