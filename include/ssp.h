@@ -1004,14 +1004,21 @@ int ssp_cosine_identify(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, cons
 /* the same with a choice of arithmetic.  precision 0: fp32-input MFMA (the parity path; ssp_cosine_identify).  precision 1: the sweep on
  * bf16 MFMA with every operand split hi + lo (three products per k-step, fp32 accumulation) keeping each embedding's two largest
  * cosines; rows whose two best are closer than twice a PROVEN bound on |cos(bf16x3) - cos(fp32 path)| for unit vectors
- * (3.01 * 2^-18 + 4 d 2^-23 + (d + 8) 2^-24, the last term for the two paths' different normalisation roundings: cosine.hip cos_band),
+ * (3.01 * 2^-16 + 4 d 2^-23 1.02 + (d + 8) 2^-24 = 5.5e-5 at d = 16, 1.9e-4 at d = 256: bf16 rounds to nearest with unit roundoff u = 2^-8, a
+ * two-term split leaves u^2 = 2^-16 of each operand behind and three such terms reach the product; then worst-case fp32 accumulation on
+ * both paths; the last term for the two paths' different normalisation roundings: the derivation stands at cosine.hip cos_band),
  * and every row that meets a NaN or a zero norm, are scored again by the fp32 kernel from a device-side list (no host round trip in
  * between; with device pointers the call is asynchronous on the ctx stream — its scratch lives on the ctx — and the diagnostics
  * below fetch their counts when asked).  argmin_out is therefore the fp32 path's on EVERY row; min_out is within the bound
  * of it (exact on the re-scored rows).  precision 2: a cascade — a sweep on the hi parts alone (one product per k-step, bound
- * 2.01 * 2^-9 + 2 d 2^-23 + (d + 8) 2^-24 = 4e-3) first, its close calls to the bf16x3 sweep, that one's to fp32: the same arg-min guarantee, three times
- * fewer matrix instructions on well-separated data (how many rows each later stage takes depends on the data); min_out is then only within
- * 4e-3 of the fp32 path's on rows the first sweep decided.  Arg-min / minimum only: dist_out must be NULL; d <= 256. */
+ * 2.01 * 2^-8 + 2 d 2^-23 1.01 + (d + 8) 2^-24 = 7.9e-3: each operand is off by u = 2^-8, cosine.hip cos_band1) first, its close calls to the
+ * bf16x3 sweep, that one's to fp32: the same arg-min guarantee, three times fewer matrix instructions on well-separated data (how many rows
+ * each later stage takes depends on the data); min_out is then only within 7.9e-3 of the fp32 path's on rows the first sweep decided.
+ * Arg-min / minimum only: dist_out must be NULL; d <= 256.
+ * Norms: every path normalises in float32 before anything else, so the result does not depend on the scale of a row or a centroid as long
+ * as its sum of squares is a normal float32: norms between 2^-40 and 2^40 are tested against float64 (tests/test_cosine_instances_gpu.py)
+ * and the result is specified for norms between 2^-60 and 2^60.  Beyond that the sum of squares loses precision, underflows to 0 or
+ * overflows, and the row (or the centroid's column) is unspecified: it may come back as the NaN of a zero-norm or infinite row. */
 int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, const float* C, int32_t S, float* dist_out,
                          int32_t* argmin_out, float* min_out, int where, int precision, float* kernel_ms);
 /* diagnostics: rows the last precision >= 1 call scored again in fp32; rows its precision-2 cascade handed to the bf16x3 sweep

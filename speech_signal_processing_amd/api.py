@@ -2213,9 +2213,11 @@ def cosine_identify(ctx: Context, X, Cn, dist: bool = False, argmin: bool = True
                     timing: bool = False, precision: int = 0, counts: bool = True) -> dict:
     """dist[i,j] = clip(1 - cos(X[i], C[j]), 0, 2); argmin over j (first index on ties) — d_vector.py:315-319.
     precision 0: fp32 MFMA (parity path).  precision 1: bf16x3 MFMA sweep + fp32 re-scoring of the rows whose two best cosines are
-    closer than a proven error bound — the arg-min of the fp32 path on every row, about 3x faster; no distance matrix (dist=False);
-    the result then carries "rescored" (rows that went through fp32 again).  precision 2: a bf16 sweep in front (bound 4e-3), its close
-    calls to the bf16x3 sweep: same arg-min guarantee, the minimum only within 4e-3 on rows the first sweep decided.
+    closer than twice a proven error bound (3.01 * 2^-16 + 4 d 2^-23 1.02 + (d + 8) 2^-24: 1.9e-4 at d = 256; bf16's unit roundoff is
+    2^-8) — the arg-min of the fp32 path on every row, about 3x faster; no distance matrix (dist=False); the result then carries
+    "rescored" (rows that went through fp32 again).  precision 2: a bf16 sweep in front (bound 2.01 * 2^-8 + 2 d 2^-23 1.01 +
+    (d + 8) 2^-24 = 7.9e-3), its close calls to the bf16x3 sweep: same arg-min guarantee, the minimum only within 7.9e-3 on rows the
+    first sweep decided.
     precision 3 or "auto": the fp32 path's arg-min at the cost of the cheapest of 2, 1 and 0 — a pilot on the first ~2 % of the rows
     reads how many each sweep would hand on (one host wait); the result carries "auto" (what it chose and saw).
     ``counts=False`` skips the "rescored" / "split_rows" diagnostics: with CUDA tensors the call then returns without waiting for the GPU."""

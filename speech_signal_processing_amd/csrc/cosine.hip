@@ -455,8 +455,8 @@ struct Cos16Args {
     float band2b;
 };
 
-// SPLIT = 3: hi + lo operands, three products per k-step (error 1.3e-4 at d = 256); SPLIT = 1: the hi parts alone, one product per k-step
-// (error 4e-3): the first sweep of the cascade (ssp_cosine_identify2 precision 2), whose close calls the SPLIT = 3 sweep takes over
+// SPLIT = 3: hi + lo operands, three products per k-step (bound 1.9e-4 at d = 256); SPLIT = 1: the hi parts alone, one product per k-step
+// (bound 7.9e-3): the first sweep of the cascade (ssp_cosine_identify2 precision 2), whose close calls the SPLIT = 3 sweep takes over
 template <int NK, int SPLIT>  // k-steps of 16: d <= 16 NK
 __global__ __launch_bounds__(256, 3) void cosine_bf16x3_kernel(Cos16Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -725,18 +725,24 @@ static int launch_cos16_nk(int nk, const Cos16Args& a, hipStream_t s) {
     }
 }
 
-// bound on |cos(bf16 x 3) - cos(fp32 path)| for unit vectors of dimension d.  x = hi + lo + r with |x - hi| <= 2^-9 |x| and
-// |r| <= 2^-18 |x| (two round-to-nearest bf16 steps), likewise c: the products the split path leaves out (lo.lo, every r term) sum to at
-// most 3.01 2^-18 sum |x_k| |c_k| <= 3.01 2^-18 (Cauchy-Schwarz, unit vectors).  Products of bf16 numbers are exact in fp32; the
-// accumulation of 3 d terms whose absolute sum is <= 1 + 2^-7 rounds (or truncates: the matrix core's internal order is not documented, so
-// the bound assumes the worst, 2^-23 per term) at most 3 d 2^-23 in total; the fp32 path's own sweep over d terms at most d 2^-23.
+// bound on |cos(bf16 x 3) - cos(fp32 path)| for unit vectors of dimension d.  bf16 has an 8-bit significand: round to nearest leaves
+// |x - hi| <= u |x| with u = 2^-8 (half an ulp of a number whose ulp is 2^-7 of its binade).  That half ulp is itself a bf16 number and
+// rounding is monotone, so lo = bf16(x - hi) has |lo| <= u |x| too, and r = x - hi - lo, the second step's error, |r| <= u |x - hi| <=
+// u^2 |x| = 2^-16 |x|.  Likewise c.  With s = hi + lo:  x c = s_x s_c + x r_c + r_x c - r_x r_c, and of s_x s_c the split path leaves out
+// lo_x lo_c: per component it drops at most (u^2 + u^2 + u^2 + u^4) |x_k| |c_k|, in all <= 3.01 2^-16 sum |x_k| |c_k| <= 3.01 2^-16
+// (Cauchy-Schwarz, unit vectors).  Products of bf16 numbers are exact in fp32; the accumulation of 3 d terms whose absolute sum is
+// <= (1 + u)^2 + 2 u (1 + u) < 1 + 2^-6 rounds (or truncates: the matrix core's internal order is not documented, so the bound assumes
+// the worst, 2^-23 per term) at most 3 d 2^-23 (1 + 2^-6) in total; the fp32 path's own sweep over d terms at most d 2^-23: together
+// <= 4 d 2^-23 1.02.
 // The two paths also NORMALISE differently: the row norm is summed in another lane / k order (1 / |x| differs by up to d 2^-24 relative),
 // and x / |x|, C / |c| and the final acc / |x| round once each on either path — (d + 8) 2^-24 covers all of it for cosines <= 1.
+// (Until the cosine instance suite the leading terms read 3.01 2^-18 and 2.01 2^-9: u taken for 2^-9.  tests/test_cosine_instances_host.py
+// holds both bands against an emulation of the two sweeps and searches for a row they would settle the wrong way.)
 static float cos_norm_slack(int d) { return (float)(d + 8) * 0x1p-24f; }
-static float cos_band(int d) { return 3.01f * 0x1p-18f + 4.0f * (float)d * 0x1p-23f * 1.01f + cos_norm_slack(d); }
-// ... of the hi parts alone: x = hi + r, |r| <= 2^-9 |x|, |hi| <= (1 + 2^-9) |x|: what hi.hi' leaves out is at most
-// (2 2^-9 (1 + 2^-9) + 2^-18) sum |x_k| |c_k| <= 2.01 2^-9; d exact products accumulated (2^-23 each, worst case) + the fp32 path's d
-static float cos_band1(int d) { return 2.01f * 0x1p-9f + 2.0f * (float)d * 0x1p-23f * 1.01f + cos_norm_slack(d); }
+static float cos_band(int d) { return 3.01f * 0x1p-16f + 4.0f * (float)d * 0x1p-23f * 1.02f + cos_norm_slack(d); }
+// ... of the hi parts alone: x = hi + e, |e| <= u |x|: x c - hi_x hi_c = e_x c + x e_c - e_x e_c, at most (2 u + u^2) sum |x_k| |c_k|
+// <= 2.01 2^-8; d exact products of absolute sum <= (1 + u)^2 accumulated (2^-23 each, worst case) + the fp32 path's d: 2 d 2^-23 1.01
+static float cos_band1(int d) { return 2.01f * 0x1p-8f + 2.0f * (float)d * 0x1p-23f * 1.01f + cos_norm_slack(d); }
 
 // d_vector.py:310-313 — one workgroup per speaker, rows summed IN ROW ORDER into a float64 accumulator (fixed summation order, like
 // numpy's mean on the reference's float64 `avg`).  The label array is scanned 2048 rows at a time with independent coalesced loads;
@@ -999,7 +1005,7 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
     if (precision >= 1) {
         // split-precision sweep(s) keeping the two best cosines per embedding, then the fp32 kernel on the rows whose call is closer than
         // the error bound — device-side lists and counts: nothing comes back to the host in between.  precision 2 puts a hi-parts-only
-        // sweep (one MFMA per k-step, bound 4e-3) in front: its close calls go to the bf16 x 3 sweep, that one's to fp32
+        // sweep (one MFMA per k-step, bound 7.9e-3) in front: its close calls go to the bf16 x 3 sweep, that one's to fp32
         const int nk = d <= 64 ? 4 : (d <= 128 ? 8 : (d <= 192 ? 12 : 16)), nq = 2 * nk;
         const int n_tiles = (S + 31) / 32;
         DevBuf &img16 = ctx->cos_img16, &list1 = ctx->cos_list1, &list2 = ctx->cos_list2, &count = ctx->cos_count;

@@ -2357,8 +2357,9 @@ def test_cosine_precision_auto(ssp):
     Cn = torch.randn((S, d), generator=g, device="cuda")
     lab = torch.randint(0, S, (N,), generator=g, device="cuda")
     Z = torch.randn((N, d), generator=g, device="cuda")
-    # near-duplicate centroid pairs (2e-3 apart): the two best cosines of every row are a pair — inside the bf16 sweep's band (8e-3),
-    # mostly outside the bf16x3 sweep's (2.7e-4): the first sweep would hand on nearly every row, so the bf16x3 sweep runs alone
+    # near-duplicate centroid pairs (2e-3 apart): the two best cosines of every row are a pair — inside twice the bf16 sweep's band
+    # (1.6e-2), many outside twice the bf16x3 sweep's (3.7e-4): the first sweep would hand on nearly every row, so the bf16x3 sweep runs
+    # alone, or fp32 where most rows would be scored again (tests/test_cosine_instances_gpu.py pins the choice on data 5e-2 apart)
     Cpairs = torch.cat([Cn[:200], Cn[:200] + 2e-3 * torch.randn((200, d), generator=g, device="cuda")])
     for Cx, labx, want in ((Cn, lab, (2,)), (Cpairs, lab % 200, (1, 0))):
         X = Cx[labx] + 0.5 * Z
