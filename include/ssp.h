@@ -691,7 +691,14 @@ int ssp_kmeanspp_seed(ssp_ctx* ctx, int32_t P, int32_t K, int32_t D, const float
 /* ---- DTW template matching: replaces the distance_dtw double loop of MFCC_DTW.py:57-108,187-217
  *      (dtw.accelerated_dtw(x, y, dist='euclidean'), warp 1) for every (query, template) pair ---- */
 /* xq: float[total query rows x dim] with q_seg row offsets; xt, t_seg likewise for the templates (dim = 1: the reference's
- * flattened _MFCC sequences).  dist_out: float[n_q x n_t] = D1[r-1][c-1]; normalize != 0 divides by (r + c) (dtw <= 1.3.3). */
+ * flattened _MFCC sequences).  dist_out: float[n_q x n_t] = D1[r-1][c-1]; normalize != 0 divides by (r + c) (dtw <= 1.3.3).
+ * Empty sequences: a pair whose query or template has no row (or both) scores +inf, with normalize too (the package would fail); the
+ * other pairs of the call are not affected.
+ * Non-finite input: a pair scores what the float64 recurrence with NaN-propagating minima (numpy's np.minimum) gives, wherever in the
+ * sequence the bad element sits: NaN if either sequence holds a NaN, or both hold the same infinity in the same coordinate (inf - inf);
+ * otherwise +inf if either holds an infinity; pairs of finite sequences keep their bits.  normalize does not change a NaN or +inf.
+ * (The dtw package's own Python min() depends on the order of its operands when one is NaN; it is not followed.)
+ * Finite input: float32 arithmetic, |dist - float64| <= 1.01 (r + c + k) 2^-24 dist with k = 1 at dim 1 and dim + 3 above. */
 int ssp_dtw_distances(ssp_ctx* ctx, const float* xq, const ssp_segments* q_seg, const float* xt, const ssp_segments* t_seg,
                       int32_t dim, int32_t normalize, float* dist_out, int where, float* kernel_ms);
 

@@ -1481,7 +1481,8 @@ def centroids(ctx: Context, X, labels, num: int):
 
 def dtw_distances(ctx: Context, queries, templates, normalize: bool = False, timing: bool = False):
     """All-pairs DTW distances (ssp_dtw_distances).  queries / templates: lists of arrays, each (L,) (the reference's
-    flattened MFCCs) or (L, dim).  Returns the (n_q, n_t) float32 matrix (numpy)."""
+    flattened MFCCs) or (L, dim).  Returns the (n_q, n_t) float32 matrix (numpy).  A pair with an empty sequence scores +inf; a pair
+    with a NaN or an infinity scores what the float64 recurrence gives, NaN or +inf (include/ssp.h)."""
     def pack(seqs):
         arrs = [np.asarray(s, dtype=np.float32) for s in seqs]
         arrs = [a.reshape(-1, 1) if a.ndim == 1 else a for a in arrs]
@@ -1493,6 +1494,8 @@ def dtw_distances(ctx: Context, queries, templates, normalize: bool = False, tim
         return np.ascontiguousarray(flat), Segments.from_lengths(ctx, [a.shape[0] for a in arrs]), dim
     q, qs, dq = pack(queries)
     t, ts, dt = pack(templates)
+    if q.shape[0] == 0 or t.shape[0] == 0:   # a side without a single row has no dimension of its own: every pair is +inf
+        dq = dt = dt if q.shape[0] == 0 else dq
     if dq != dt:
         raise ValueError("queries and templates must share the feature dimension")
     out = np.empty((qs.n, ts.n), dtype=np.float32)

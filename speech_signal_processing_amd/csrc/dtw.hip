@@ -27,6 +27,43 @@ struct DtwArgs {
     int32_t n_q, n_t, dim, normalize, max_r;
 };
 
+// Non-finite input of the all-pairs matcher (include/ssp.h, ssp_dtw_distances): the answer is the float64 recurrence's with NaN-propagating
+// minima.  The sweeps below step past a NaN (fminf and `<` both drop it) and restart from the +inf border, so what they would leave for a
+// polluted pair depends on where the bad element sits, and a per-cell test would cost the dim-1 loop a third of its instructions.  The
+// recurrence's answer needs no sweep: a cost is NaN iff one of its operands is NaN or both hold the same infinity in one coordinate, a NaN
+// cell reaches D[r-1][c-1], and an infinite row or column is crossed by every path.  So a wave first reads its two sequences once
+// ((r + c) dim elements in front of r c cells: one FMA each) and leaves with the rule's answer if it met a bad element.
+
+// any NaN or infinity among p[0 .. n)?  All 64 lanes call it; v * 0 is 0 for a finite v and NaN otherwise.
+__device__ __forceinline__ bool dtw_any_nonfinite(const float* __restrict__ p, int64_t n, int lane) {
+    float s = 0.f;
+    for (int64_t k = lane; k < n; k += 64) s = fmaf(p[k], 0.f, s);
+    return __any(s != s) != 0;
+}
+
+__device__ __forceinline__ uint32_t dtw_wave_or(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+
+// the rare path: NaN or +inf by the rule, coordinate by coordinate (bit 0: a NaN, bit 1: +inf, bit 2: -inf); all 64 lanes call it.
+// A function of its own: its selects and cross-lane moves stay out of the kernels' bodies (tests/test_isa_guards.py counts the selects of
+// dtw1_kernel); it needs no stack, and no instance with W >= 8 takes a register more than it did without it.
+__device__ __noinline__ float dtw_nonfinite_result(const float* __restrict__ x, int r, const float* __restrict__ y, int c, int dim, int lane) {
+    auto cls = [](float v) -> uint32_t { return v != v ? 1u : v == INFINITY ? 2u : v == -INFINITY ? 4u : 0u; };
+    uint32_t any = 0, both = 0;
+    for (int e = 0; e < dim; ++e) {
+        uint32_t fx = 0, fy = 0;
+        for (int i = lane; i < r; i += 64) fx |= cls(x[(size_t)i * dim + e]);
+        for (int j = lane; j < c; j += 64) fy |= cls(y[(size_t)j * dim + e]);
+        fx = dtw_wave_or(fx);
+        fy = dtw_wave_or(fy);
+        any |= fx | fy;
+        both |= fx & fy;
+    }
+    return __uint_as_float(((any & 1u) | (both & 6u)) ? 0x7fc00000u : 0x7f800000u);
+}
+
 // T = float: the all-pairs matcher.  T = double, STORE: the single-pair variant that also leaves D1 for the traceback
 // (generate_template needs the warping path; float64 like the reference, so that ties break the same way).
 template <int W, typename T, bool STORE>
@@ -41,6 +78,13 @@ __global__ __launch_bounds__(256) void dtw_kernel(DtwArgs a) {
     const float* __restrict__ y = a.xt + a.t_off[p] * dim;
     T* __restrict__ bnd = static_cast<T*>(a.bnd) + wave_id * a.max_r;
     T* __restrict__ dmat = static_cast<T*>(a.dmat);
+    if constexpr (!STORE) {  // (ssp_dtw_path keeps what its sweep leaves)
+        if (r > 0 && c > 0 && (dtw_any_nonfinite(x, (int64_t)r * dim, lane) || dtw_any_nonfinite(y, (int64_t)c * dim, lane))) {
+            const float v = dtw_nonfinite_result(x, r, y, c, dim, lane);
+            if (lane == 0) static_cast<float*>(a.out)[wave_id] = v;  // (normalize leaves NaN and +inf what they are)
+            return;
+        }
+    }
     const T INF = (T)INFINITY;
     T result = INF;  // empty sequences: the package would fail; report +inf
     if (r > 0 && c > 0) {
@@ -140,6 +184,11 @@ __global__ __launch_bounds__(256) void dtw1_kernel(DtwArgs a) {
     const float* __restrict__ x = a.xq + a.q_off[q];
     const float* __restrict__ y = a.xt + a.t_off[p];
     float* __restrict__ bnd = static_cast<float*>(a.bnd) + wave_id * a.max_r;
+    if (r > 0 && c > 0 && (dtw_any_nonfinite(x, r, lane) || dtw_any_nonfinite(y, c, lane))) {
+        const float v = dtw_nonfinite_result(x, r, y, c, 1, lane);
+        if (lane == 0) static_cast<float*>(a.out)[wave_id] = v;  // (normalize leaves NaN and +inf what they are)
+        return;
+    }
     float result = INFINITY;
     if (r > 0 && c > 0) {
         for (int cb0 = 0; cb0 < c; cb0 += 64 * W) {

@@ -14,6 +14,8 @@ other tests never reach the second branch.  Here every array is a view at a chos
 Skewed inputs go through the public api with torch views; api allocates its own outputs (except MfccPlan.run(out=)), so skewed outputs
 are called through the C-ABI (ctx._lib.ssp_*, where = SSP_DEVICE).  Skews: float32 / int32 4, 8, 12 bytes; int16 2, 6 (odd samples) and
 8; uint8 1 and 3.  Arrays whose base decides a code path take every skew, the others 4 bytes.
+
+ssp_dtw_distances with where = SSP_DEVICE has its skewed, guarded case in tests/test_dtw_instances_gpu.py.
 """
 import ctypes as C
 import os

@@ -24,7 +24,7 @@ cannot differ are listed at ``CANNOT_FAIL_WITHOUT_ORDERING`` below with the reas
 that owns its stream) every borrowed-stale case and the four d_vector tests failed and everything else passed.
 
 Context.allgather / allreduce_sum_ are covered: a world of one is initialised in-process (ctx.comm_init(0, 1, uid), as
-tests/test_gpu_multirank.py does).
+tests/test_gpu_multirank.py does).  ssp_dtw_distances on device pointers has its race in tests/test_dtw_instances_gpu.py.
 """
 import ctypes as C
 import os
