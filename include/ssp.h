@@ -734,14 +734,22 @@ int ssp_dtw_templates(ssp_ctx* ctx, const double* x, const int64_t* seq_off, int
 /* ---- d-vector network forward: one Dense layer Y = act(X W + b) of the speaker network the reference runs with
  *      spkModel.predict (d_vector.py:171-189 builds Dense(256) x 4 with ReLU between; predict at d_vector.py:298-299,327,348) ---- */
 /* X: float[N x d_in]; Wt: float[units x d_in] = the Keras kernel (d_in x units) TRANSPOSED; bias: float[units] (nullable);
- * relu != 0 applies max(0, .); Y: float[N x units].  All four arrays live on the side `where` names. */
+ * relu != 0 applies max(0, .); Y: float[N x units].  All four arrays live on the side `where` names.
+ * Non-finite input.  A NaN stays a NaN through ReLU (numpy's maximum, Keras; not C's fmaxf): Y[n][u] is NaN, +inf or -inf exactly
+ * where the float64 evaluation of the same float32 operands is, so a NaN anywhere in sample n makes row n NaN, and +-inf propagates
+ * by IEEE arithmetic (inf - inf and 0 * inf are NaN).  No other sample's row moves by a bit.
+ * A sample's output bits do not depend on the batch it is in (N, its position, its neighbours).
+ * Error against float64: |Y - ref| <= 1.01 (d_in + 1) 2^-23 (sum_k |x_k| |w_ku| + |b_u|) per element (tests/dense_cases.py). */
 int ssp_dense_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t d_in, const float* Wt, const float* bias,
                       int32_t units, int32_t relu, float* Y, int where, float* kernel_ms);
 
 /* The whole network as one object: n_layers Dense layers, layer l = (Wt[l]: HOST float[dims[l+1] x dims[l]] = Keras kernel transposed,
  * bias[l]: HOST float[dims[l+1]] or NULL, relu[l]).  ssp_dnn_forward = spkModel.predict: X float[N x dims[0]] -> Y float[N x dims[n_layers]].
  * Layers whose input and output widths are <= 256 (the reference's three hidden-to-hidden / output layers) run inside one kernel with
- * the activations kept in registers between layers; wider layers in front of them (the 1274-input layer) run one GEMM launch each. */
+ * the activations kept in registers between layers; wider layers in front of them (the 1274-input layer) run one GEMM launch each.
+ * Non-finite input: ssp_dense_forward's rule, layer by layer.  A NaN passes every ReLU; +-inf reaches the output as the float64
+ * evaluation carries it.  The zero padding of a layer narrower than 256 takes no part: a padded unit leaves its layer as exactly 0
+ * whatever the sample holds (never 0 * inf = NaN).  A sample's output bits do not depend on the batch it is in. */
 int ssp_dnn_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const float* const* Wt, const float* const* bias,
                    const int32_t* relu, ssp_dnn** out);
 int ssp_dnn_destroy(ssp_dnn* dnn);

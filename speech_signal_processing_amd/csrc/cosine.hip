@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256, 3) void cosine_reg_kernel(CosRegArgs a) {
                         float y = acc[i4 * 4 + e];
                         if (row + e < a.S) {
                             if (a.bias) y += a.bias[row + e];
-                            if (a.relu) y = fmaxf(y, 0.f);
+                            if (a.relu) y = y <= 0.f ? 0.f : y;  // (not fmaxf: a NaN stays a NaN; -0 -> +0 as before)
                         }
                         v[e] = y;
                     }

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(DenseArgs a) {
                         float t = acc[rt][ct][i4 * 4 + e];
                         if (row + e < a.units) {
                             if (a.bias) t += a.bias[row + e];
-                            if (a.relu) t = fmaxf(t, 0.f);
+                            if (a.relu) t = t <= 0.f ? 0.f : t;  // (not fmaxf: a NaN stays a NaN, as under np.maximum; -0 -> +0 as before)
                         }
                         v[e] = t;
                     }

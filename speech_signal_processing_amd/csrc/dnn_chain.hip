@@ -36,6 +36,7 @@ struct ChainArgs {
     int64_t N;
     int32_t n_layers, d_in, d_out;
     int32_t relu[CH_MAXL];
+    int32_t width[CH_MAXL];  // units of each chained layer: the padded units beyond it leave the layer as exactly 0
 };
 
 __global__ __launch_bounds__(256, 3) void dnn_chain_kernel(ChainArgs a) {
@@ -90,6 +91,7 @@ __global__ __launch_bounds__(256, 3) void dnn_chain_kernel(ChainArgs a) {
     for (int l = 0; l < a.n_layers; ++l) {
         const bool last = l + 1 == a.n_layers;
         const bool relu = a.relu[l] != 0;
+        const int width = a.width[l];
         float nb[64];
 #pragma unroll
         for (int tp = 0; tp < 16; ++tp) {
@@ -107,9 +109,21 @@ __global__ __launch_bounds__(256, 3) void dnn_chain_kernel(ChainArgs a) {
             }
             const f32x4 bv = *reinterpret_cast<const f32x4*>(s_bias + l * CH_W + 16 * tp + 4 * kq);
             f32x4 v = (acc0 + acc1) + bv;
-            if (relu) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+            const int u = 16 * tp + 4 * kq;
+            // ReLU by a select, not fmaxf: a NaN stays a NaN (np.maximum, Keras); -0 -> +0 as fmaxf gave it
+            if (relu) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = v[r] <= 0.f ? 0.f : v[r];
+            }
+            // A padded unit (zero weight rows, zero bias) holds 0 * x: NaN for a sample with an inf or a NaN in it, which a linear
+            // layer would hand on to every real unit of the next layer as 0 * NaN.  It leaves the layer as exactly 0 instead.
+            // (A wave-uniform branch: tiles that lie inside the layer, all of them at width 256, skip it.)
+            if (16 * tp + 16 > width) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (u + r >= width) v[r] = 0.f;
+            }
             if (last) {
-                const int u = 16 * tp + 4 * kq;
                 if (row < a.N && u < a.d_out) {
                     float* y = a.Y + row * a.d_out + u;
                     if (u + 3 < a.d_out && (a.d_out & 3) == 0 && (reinterpret_cast<uintptr_t>(a.Y) & 15) == 0) {
@@ -280,7 +294,10 @@ int ssp_dnn_forward(ssp_dnn* dnn, const float* X, int64_t N, float* Y, int where
         a.n_layers = L - from;
         a.d_in = dnn->dims[(size_t)from];
         a.d_out = dnn->dims[(size_t)L];
-        for (int l = from; l < L; ++l) a.relu[l - from] = dnn->relu[(size_t)l];
+        for (int l = from; l < L; ++l) {
+            a.relu[l - from] = dnn->relu[(size_t)l];
+            a.width[l - from] = dnn->dims[(size_t)l + 1];
+        }
         const size_t lds = (size_t)(3 * CH_TILE + (L - from) * CH_W) * sizeof(float);
         if (lds > 64 * 1024)
             SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dnn_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

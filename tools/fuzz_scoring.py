@@ -6,6 +6,9 @@ from oracle import ref_cpu as O
 # the derived bound of a float32 DTW against float64 (tests/dtw_cases.py band(), restated: this tool imports nothing from tests/;
 # tests/test_dtw_instances_host.py holds the two to each other)
 dtw_band = lambda r, c, dim, ref: 1.01 * (r + c + (1 if dim == 1 else dim + 3)) * 2.0 ** -24 * abs(ref)
+# the derived bound of one float32 dense layer against float64, per output element (tests/dense_cases.py band_of(), restated for one
+# layer; tests/test_dense_instances_host.py holds that one): d_in accumulations and the bias add, 2^-23 each, on sum |x| |w| + |b|
+dense_band = lambda X, W, b: 1.01 * (W.shape[0] + 1) * 2.0 ** -23 * (np.abs(X.astype(np.float64)) @ np.abs(W.astype(np.float64)) + np.abs(b.astype(np.float64)))
 
 ctx = api.default_context()
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
@@ -108,8 +111,10 @@ for case in range(n_cases):
     Xd = rng.standard_normal((Nn, di)).astype(np.float32)
     Wd = (rng.standard_normal((di, un)) / np.sqrt(di)).astype(np.float32)
     bd = rng.standard_normal(un).astype(np.float32)
-    yd = api.dense_forward(ctx, Xd, np.ascontiguousarray(Wd.T), bd, relu=bool(rng.integers(0, 2)) and False)
-    assert np.abs(yd - O.dense_net_forward(Xd, [(Wd, bd, 'linear')])).max() < 1e-4 * max(1.0, np.abs(yd).max()), (case, "dense")
+    relu_d = bool(rng.integers(0, 2))
+    yd = api.dense_forward(ctx, Xd, np.ascontiguousarray(Wd.T), bd, relu=relu_d)
+    err_d = np.abs(yd - O.dense_net_forward(Xd, [(Wd, bd, 'relu' if relu_d else 'linear')]))
+    assert (err_d <= dense_band(Xd, Wd, bd)).all(), (case, "dense", Nn, di, un, relu_d, float((err_d / dense_band(Xd, Wd, bd)).max()))
     # ---- EM statistics
     Ke, De, ne = int(rng.choice([1, 3, 64, 65, 130])), int(rng.choice([1, 5, 13, 39, 47, 48, 64])), int(rng.choice([1, 63, 64, 65, 1000, 5000]))
     if verbose:
