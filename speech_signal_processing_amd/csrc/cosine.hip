@@ -856,25 +856,20 @@ int ssp_centroids(ssp_ctx* ctx, const float* X, const int32_t* labels, int64_t N
     ssp::TraceRange trace_("ssp_centroids");
     SSP_TRY(use_ctx(ctx));
     if (N < 0 || d < 1 || S < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_centroids: bad shape");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_centroids: where");
+    SSP_TRY(check_where(where, "ssp_centroids"));
     if (!out || (N > 0 && (!X || !labels))) SSP_FAIL(SSP_ERR_INVALID, "ssp_centroids: null pointer");
     if (kernel_ms) *kernel_ms = 0.f;
-    Staged sx, sl, so;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    float* dO = (float*)so.out(ctx, out, (size_t)S * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)N * d * sizeof(float));
+    const int32_t* dL = st.in(labels, (size_t)N * sizeof(int32_t));
+    float* dO = st.out(out, (size_t)S * d * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     hipLaunchKernelGGL(centroid_kernel, dim3((unsigned)S), dim3(256), 0, ctx->stream, dX, dL, N, d, dO);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(so.back(ctx, out, (size_t)S * d * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_cosine_identify(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, const float* C, int32_t S, float* dist_out,
@@ -925,7 +920,7 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
     ssp::TraceRange trace_("ssp_cosine_identify");
     SSP_TRY(use_ctx(ctx));
     if (N < 0 || d < 1 || S < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_cosine_identify: bad shape N=%lld d=%d S=%d", (long long)N, d, S);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_cosine_identify: where");
+    SSP_TRY(check_where(where, "ssp_cosine_identify"));
     if (precision < 0 || precision > 3)
         SSP_FAIL(SSP_ERR_INVALID, "ssp_cosine_identify: precision must be 0 (fp32 MFMA), 1 (bf16x3 MFMA + fp32 re-scoring of close calls), 2 (bf16 sweep, "
                                   "then bf16x3, then fp32 on the respective close calls) or 3 (auto: 2, 1 or 0, whichever a pilot on the first rows predicts to be fastest)");
@@ -944,18 +939,15 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
     if (!X || !C) SSP_FAIL(SSP_ERR_INVALID, "ssp_cosine_identify: null input");
     if (N > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_cosine_identify: more than 2^31 - 1 embeddings in one call");
     hipStream_t s = ctx->stream;
-    Staged sx, sc, sd, sa, sm;
-    int rc;
+    StageScope st(ctx, where);
     // Host-fed arg-min / minimum on the parity path above two slices of embeddings (d_vector.py:315-319 hands host arrays): the rows go
     // through the ctx's ring, copied in ahead of the sweep that scores them (feed_rows, staging.hpp): a call costs its PCIe time
     // instead of PCIe + sweep.  Rows are independent: bits equal to the one-piece path.
     if (where == SSP_HOST && precision == 0 && !dist_out && d <= 256 && N >= 2 && (size_t)N * d * sizeof(float) >= 2 * host_slice_bytes()) {
-        const float* dC = (const float*)sc.in(ctx, C, (size_t)S * d * sizeof(float), where, &rc);
-        SSP_TRY(rc);
-        int32_t* dA = (int32_t*)sa.out(ctx, argmin_out, (size_t)N * sizeof(int32_t), where, &rc);
-        SSP_TRY(rc);
-        float* dM = (float*)sm.out(ctx, min_out, (size_t)N * sizeof(float), where, &rc);
-        SSP_TRY(rc);
+        const float* dC = st.in(C, (size_t)S * d * sizeof(float));
+        int32_t* dA = st.out(argmin_out, (size_t)N * sizeof(int32_t));
+        float* dM = st.out(min_out, (size_t)N * sizeof(float));
+        SSP_TRY(st.status());
         const int nq = d <= 64 ? 8 : (d <= 128 ? 16 : (d <= 192 ? 24 : 32));
         const int n_tiles = (S + 31) / 32;
         DevBuf& img = ctx->cos_img;
@@ -981,21 +973,13 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
             }
         }));
         SSP_TRY(tms.stop(s, kernel_ms));
-        SSP_TRY(sa.back(ctx, argmin_out, (size_t)N * sizeof(int32_t), where));
-        SSP_TRY(sm.back(ctx, min_out, (size_t)N * sizeof(float), where));
-        SSP_HIP(hipStreamSynchronize(s));
-        return SSP_OK;
+        return st.finish();
     }
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dC = (const float*)sc.in(ctx, C, (size_t)S * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dD = (float*)sd.out(ctx, dist_out, (size_t)N * S * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    int32_t* dA = (int32_t*)sa.out(ctx, argmin_out, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    float* dM = (float*)sm.out(ctx, min_out, (size_t)N * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    const float *dX = st.in(X, (size_t)N * d * sizeof(float)), *dC = st.in(C, (size_t)S * d * sizeof(float));
+    float* dD = st.out(dist_out, (size_t)N * S * sizeof(float));
+    int32_t* dA = st.out(argmin_out, (size_t)N * sizeof(int32_t));
+    float* dM = st.out(min_out, (size_t)N * sizeof(float));
+    SSP_TRY(st.status());
     // (scratch lives on the ctx, grow-only: no allocation and no implicit synchronisation per call; calls on one ctx are stream-ordered)
     DevBuf &inc = ctx->cos_inc, &img = ctx->cos_img;
     Timer tm;
@@ -1096,10 +1080,10 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
                 default: SSP_TRY(launch_cos_reg<32>(ra, s)); break;
             }
             SSP_TRY(tm.stop(s, kernel_ms));
-            SSP_TRY(sa.back(ctx, argmin_out, (size_t)N * sizeof(int32_t), where));
-            SSP_TRY(sm.back(ctx, min_out, (size_t)N * sizeof(float), where));
+            SSP_TRY(st.copy_back());
             ctx->cos_counts_pending = true;  // (ssp_cosine_last_rescored / _split_rows fetch them)
             if (where == SSP_HOST) SSP_TRY(cos_fetch_counts(ctx));  // (host outputs: the call waits for its copies anyway)
+            st.waited();
             return SSP_OK;
         }
         // (the pilot chose the fp32 sweep: it follows, inside the same timed region)
@@ -1132,11 +1116,7 @@ int ssp_cosine_identify2(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, con
         SSP_HIP(hipGetLastError());
         SSP_TRY(tm.stop(s, kernel_ms));
     }
-    SSP_TRY(sd.back(ctx, dist_out, (size_t)N * S * sizeof(float), where));
-    SSP_TRY(sa.back(ctx, argmin_out, (size_t)N * sizeof(int32_t), where));
-    SSP_TRY(sm.back(ctx, min_out, (size_t)N * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));  // (device pointers: asynchronous on the ctx stream, like every other entry point)
-    return SSP_OK;
+    return st.finish();  // (device pointers: asynchronous on the ctx stream, like every other entry point)
 }
 
 }  // extern "C"

@@ -184,30 +184,23 @@ extern "C" int ssp_dense_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_
     if (kernel_ms) *kernel_ms = 0.f;
     if (N < 0 || d_in < 1 || units < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_dense_forward: bad shape");
     if (d_in > (1 << 21)) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dense_forward: d_in above 2^21 (32-bit offsets inside a 128-row block)");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_dense_forward: where");
+    SSP_TRY(check_where(where, "ssp_dense_forward"));
     if (N == 0) return SSP_OK;
     if (!X || !Wt || !Y) SSP_FAIL(SSP_ERR_INVALID, "ssp_dense_forward: null array");
     const int64_t grid = (N + DBN - 1) / DBN;
     if (grid > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dense_forward: too many samples");
     hipStream_t s = ctx->stream;
-    Staged sx, sw, sb, sy;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * d_in * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dW = (const float*)sw.in(ctx, Wt, (size_t)units * d_in * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dB = (const float*)sb.in(ctx, bias, (size_t)units * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dY = (float*)sy.out(ctx, Y, (size_t)N * units * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float *dX = st.in(X, (size_t)N * d_in * sizeof(float)), *dW = st.in(Wt, (size_t)units * d_in * sizeof(float));
+    const float* dB = st.in(bias, (size_t)units * sizeof(float));
+    float* dY = st.out(Y, (size_t)N * units * sizeof(float));
+    SSP_TRY(st.status());
     if (d_in <= 256 && !getenv("SSP_DENSE_NO_REG")) {  // samples held in registers, weight tiles streamed (cosine.hip): the network's hidden layers
         Timer tr;
         SSP_TRY(tr.start(kernel_ms != nullptr, s));
         SSP_TRY(launch_dense_reg(ctx, dX, N, d_in, dW, dB, units, relu ? 1 : 0, dY, s));
         SSP_TRY(tr.stop(s, kernel_ms));
-        SSP_TRY(sy.back(ctx, Y, (size_t)N * units * sizeof(float), where));
-        if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-        return SSP_OK;
+        return st.finish();
     }
     DenseArgs a{dX, dW, dB, dY, N, d_in, units, relu ? 1 : 0};
     constexpr size_t lds = (size_t)4 * (DBK / 8) * 2 * DPL * sizeof(float);  // two slabs of two operand images: 66 KB
@@ -217,7 +210,5 @@ extern "C" int ssp_dense_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_
     hipLaunchKernelGGL(dense_kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sy.back(ctx, Y, (size_t)N * units * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }

@@ -383,7 +383,7 @@ int ssp_pairwise_scores(ssp_ctx* ctx, const float* X, const ssp_segments* seg, i
     if (!ctx) SSP_FAIL(SSP_ERR_INVALID, "null ssp_ctx");
     if (!seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_pairwise_scores: null segments");
     if (q < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_pairwise_scores: q=%d", q);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_pairwise_scores: where");
+    SSP_TRY(check_where(where, "ssp_pairwise_scores"));
     if (!std::isfinite(c0)) SSP_FAIL(SSP_ERR_INVALID, "ssp_pairwise_scores: c0 is not finite");
     for (int d = 0; d < q && d < DZ_MAX_Q; ++d)
         if ((g && !std::isfinite(g[d])) || (h && !std::isfinite(h[d]))) SSP_FAIL(SSP_ERR_INVALID, "ssp_pairwise_scores: g or h is not finite at %d", d);
@@ -419,12 +419,10 @@ int ssp_pairwise_scores(ssp_ctx* ctx, const float* X, const ssp_segments* seg, i
     SSP_TRY(ctx->diar_tab.reserve(blob.size()));
     SSP_TRY(ctx->diar_r.reserve((size_t)rows * sizeof(float)));
     SSP_HIP(hipMemcpyAsync(ctx->diar_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-    Staged sx, so;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)rows * (size_t)q * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dO = (float*)so.out(ctx, out, (size_t)total_sq * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)rows * (size_t)q * sizeof(float));
+    float* dO = st.out(out, (size_t)total_sq * sizeof(float));
+    SSP_TRY(st.status());
     const char* tab = ctx->diar_tab.as<char>();
     const int64_t row0 = seg->host.front();
     PairArgs a{dX, g ? reinterpret_cast<const float*>(tab + at_g) : nullptr, ctx->diar_r.as<float>(), dO,
@@ -436,9 +434,7 @@ int ssp_pairwise_scores(ssp_ctx* ctx, const float* X, const ssp_segments* seg, i
     hipLaunchKernelGGL(diar_pair_kernel, dim3((unsigned)(tiles.size() / 2)), dim3(256), 0, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(so.back(ctx, out, (size_t)total_sq * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, int32_t linkage, float threshold, int32_t min_clusters,
@@ -450,7 +446,7 @@ int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, 
     if (linkage < 0 || linkage > 2) SSP_FAIL(SSP_ERR_INVALID, "ssp_ahc_cluster: linkage=%d (0 average, 1 complete, 2 single)", linkage);
     if (threshold != threshold) SSP_FAIL(SSP_ERR_INVALID, "ssp_ahc_cluster: the threshold is NaN");
     if (min_clusters < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_ahc_cluster: min_clusters=%d", min_clusters);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_ahc_cluster: where");
+    SSP_TRY(check_where(where, "ssp_ahc_cluster"));
     for (int64_t r = 0; n_speakers && r < seg->n; ++r)
         if (n_speakers[r] < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_ahc_cluster: n_speakers[%lld]=%d", (long long)r, n_speakers[r]);
     SSP_TRY(check_recordings(seg, "ssp_ahc_cluster"));
@@ -494,26 +490,20 @@ int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, 
     SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(diar_ahc_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)ahc_lds_bytes(DZ_MAX_N, false)));
     SSP_HIP(hipMemcpyAsync(ctx->diar_tab.p, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-    Staged sc, sl, sn, sp, sm;
-    int rc;
-    const float* dS = (const float*)sc.in(ctx, scores, (size_t)total_sq * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    int32_t* dL = (int32_t*)sl.out(ctx, labels_out, (size_t)rows * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    int32_t* dN = (int32_t*)sn.out(ctx, n_clusters_out, (size_t)R * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    int32_t* dP = (int32_t*)sp.out(ctx, merge_pair_out, (size_t)rows * 2 * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    float* dM = (float*)sm.out(ctx, merge_score_out, (size_t)rows * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    if (where == SSP_HOST) {  // what no workgroup writes (counts of empty recordings, rows before offsets[0]) keeps the caller's bytes
-        SSP_HIP(hipMemcpyAsync(dN, n_clusters_out, (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        if (seg->host.front() > 0) {
-            const size_t lead = (size_t)seg->host.front();
-            SSP_HIP(hipMemcpyAsync(dL, labels_out, lead * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            if (dP) SSP_HIP(hipMemcpyAsync(dP, merge_pair_out, lead * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            if (dM) SSP_HIP(hipMemcpyAsync(dM, merge_score_out, lead * sizeof(float), hipMemcpyHostToDevice, s));
-        }
+    // what no workgroup writes (counts of empty recordings, rows before offsets[0]) keeps the caller's bytes: the counts are pre-loaded
+    // whole, of the per-row outputs the `lead` rows
+    StageScope st(ctx, where);
+    const float* dS = st.in(scores, (size_t)total_sq * sizeof(float));
+    int32_t* dL = st.out(labels_out, (size_t)rows * sizeof(int32_t));
+    int32_t* dN = st.out(n_clusters_out, (size_t)R * sizeof(int32_t), true);
+    int32_t* dP = st.out(merge_pair_out, (size_t)rows * 2 * sizeof(int32_t));
+    float* dM = st.out(merge_score_out, (size_t)rows * sizeof(float));
+    SSP_TRY(st.status());
+    if (where == SSP_HOST && seg->host.front() > 0) {
+        const size_t lead = (size_t)seg->host.front();
+        SSP_HIP(hipMemcpyAsync(dL, labels_out, lead * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (dP) SSP_HIP(hipMemcpyAsync(dP, merge_pair_out, lead * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (dM) SSP_HIP(hipMemcpyAsync(dM, merge_score_out, lead * sizeof(float), hipMemcpyHostToDevice, s));
     }
     const DiarRec* dRecs = reinterpret_cast<const DiarRec*>(ctx->diar_tab.as<char>() + at_recs);
     Timer tm;
@@ -530,12 +520,7 @@ int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, 
     }
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sl.back(ctx, labels_out, (size_t)rows * sizeof(int32_t), where));
-    SSP_TRY(sn.back(ctx, n_clusters_out, (size_t)R * sizeof(int32_t), where));
-    SSP_TRY(sp.back(ctx, merge_pair_out, (size_t)rows * 2 * sizeof(int32_t), where));
-    SSP_TRY(sm.back(ctx, merge_score_out, (size_t)rows * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

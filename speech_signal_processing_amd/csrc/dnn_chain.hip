@@ -253,19 +253,17 @@ int ssp_dnn_forward(ssp_dnn* dnn, const float* X, int64_t N, float* Y, int where
     ssp_ctx* ctx = dnn->ctx;
     SSP_TRY(use_ctx(ctx));
     if (kernel_ms) *kernel_ms = 0.f;
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_forward: where");
+    SSP_TRY(check_where(where, "ssp_dnn_forward"));
     if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_forward: N < 0");
     if (N == 0) return SSP_OK;
     if (!X || !Y) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_forward: null array");
     if ((N + 63) / 64 > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dnn_forward: too many samples");
     hipStream_t s = ctx->stream;
     const int L = dnn->n_layers, from = dnn->chain_from;
-    Staged sx, sy;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * dnn->dims[0] * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dY = (float*)sy.out(ctx, Y, (size_t)N * dnn->dims[(size_t)L] * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)N * dnn->dims[0] * sizeof(float));
+    float* dY = st.out(Y, (size_t)N * dnn->dims[(size_t)L] * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
     // layers in front of the chain: one GEMM launch each (ssp_dense_forward's kernels), activations through a scratch pair
@@ -305,9 +303,7 @@ int ssp_dnn_forward(ssp_dnn* dnn, const float* X, int64_t N, float* Y, int where
         SSP_HIP(hipGetLastError());
     }
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sy.back(ctx, Y, (size_t)N * dnn->dims[(size_t)L] * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

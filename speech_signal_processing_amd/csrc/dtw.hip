@@ -290,7 +290,7 @@ extern "C" int ssp_dtw_distances(ssp_ctx* ctx, const float* xq, const ssp_segmen
     if (kernel_ms) *kernel_ms = 0.f;
     if (!q_seg || !t_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_dtw_distances: null segments");
     if (dim < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_dtw_distances: dim");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_dtw_distances: where");
+    SSP_TRY(check_where(where, "ssp_dtw_distances"));
     const int64_t n_q = q_seg->n, n_t = t_seg->n, n_pairs = n_q * n_t;
     if (n_pairs == 0) return SSP_OK;
     if (!dist_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_dtw_distances: null output");
@@ -300,14 +300,10 @@ extern "C" int ssp_dtw_distances(ssp_ctx* ctx, const float* xq, const ssp_segmen
     if (max_r > INT32_MAX / 2 || max_c > INT32_MAX / 2 || n_q > INT32_MAX || n_t > INT32_MAX)
         SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dtw_distances: sequence too long");
     hipStream_t s = ctx->stream;
-    Staged sq, st, so;
-    int rc;
-    const float* dq = (const float*)sq.in(ctx, xq, (size_t)rows_q * dim * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dt = (const float*)st.in(ctx, xt, (size_t)rows_t * dim * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dout = (float*)so.out(ctx, dist_out, (size_t)n_pairs * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float *dq = st.in(xq, (size_t)rows_q * dim * sizeof(float)), *dt = st.in(xt, (size_t)rows_t * dim * sizeof(float));
+    float* dout = st.out(dist_out, (size_t)n_pairs * sizeof(float));
+    SSP_TRY(st.status());
     // column block per lane: the smallest of {4, 8, (12,) 16, (20, 24,) 32} that covers the longest template in one super-block, else 32
     const int need = (int)((max_c + 63) / 64);
     int W = need <= 4 ? 4 : need <= 8 ? 8 : need <= 16 ? 16 : 32;
@@ -341,9 +337,7 @@ extern "C" int ssp_dtw_distances(ssp_ctx* ctx, const float* xq, const ssp_segmen
     }
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(so.back(ctx, dist_out, (size_t)n_pairs * sizeof(float), where));
-    SSP_HIP(hipStreamSynchronize(s));  // `bnd` and the staging buffers are freed at return
-    return SSP_OK;
+    return st.finish(true);  // `bnd` and the staging buffers are freed at return
 }
 
 extern "C" int ssp_dtw_path(ssp_ctx* ctx, const float* x, int64_t r, const float* y, int64_t c, int32_t dim, double* dist_out,

@@ -209,12 +209,9 @@ extern "C" int ssp_fastdtw_distances(ssp_ctx* ctx, const float* xq, const ssp_se
     const int64_t max_r = std::max<int64_t>(q_seg->max_len(), 1), max_c = std::max<int64_t>(t_seg->max_len(), 1);
     if (max_r > (1 << 24) || max_c > (1 << 24) || n_t > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_fastdtw_distances: sequence too long");
     hipStream_t s = ctx->stream;
-    Staged sq, st;
-    int rc;
-    const float* dq = (const float*)sq.in(ctx, xq, (size_t)rows_q * sizeof(float), SSP_HOST, &rc);
-    SSP_TRY(rc);
-    const float* dt = (const float*)st.in(ctx, xt, (size_t)rows_t * sizeof(float), SSP_HOST, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, SSP_HOST);  // (host arrays only)
+    const float *dq = st.in(xq, (size_t)rows_q * sizeof(float)), *dt = st.in(xt, (size_t)rows_t * sizeof(float));
+    SSP_TRY(st.status());
     // window cells of a level: every path cell (at most nx + ny of them one level down) becomes <= (2 radius + 1) columns over
     // (2 radius + 1) rows, doubled in both directions; the coarsest level is a full matrix of at most (2 radius + 4)^2 x ... cells
     const int64_t cell_cap = std::max<int64_t>(4 * (2 * radius + 2) * (max_r + max_c) + 64, (int64_t)(2 * radius + 4) * std::max(max_r, max_c) + 64);

@@ -230,23 +230,17 @@ int ssp_enframe(ssp_ctx* ctx, const float* samples, int64_t n, int32_t frame_siz
     if (n_frames == 0) return SSP_OK;
     if (!samples || !frames_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_enframe: null data pointer");
     const size_t out_bytes = (size_t)frame_size * n_frames * sizeof(float);
-    Staged sin, sout, sw;
-    int rc;
-    const float* d_in = (const float*)sin.in(ctx, samples, (size_t)n * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* d_w = (const float*)sw.in(ctx, window, (size_t)frame_size * sizeof(float), SSP_HOST, &rc);
-    SSP_TRY(rc);
-    float* d_out = (float*)sout.out(ctx, frames_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float *d_in = st.in(samples, (size_t)n * sizeof(float)), *d_w = st.in_host(window, (size_t)frame_size * sizeof(float));
+    float* d_out = st.out(frames_out, out_bytes);
+    SSP_TRY(st.status());
     const int grid = (int)std::min<int64_t>(ceil_div<int64_t>((int64_t)frame_size * n_frames, 256), (int64_t)ctx->num_cu * 8);
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     hipLaunchKernelGGL(enframe_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_in, n, frame_size, step, n_frames, d_w, d_out);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(sout.back(ctx, frames_out, out_bytes, where));
-    SSP_HIP(hipStreamSynchronize(ctx->stream));  // the staged window copy dies at return
-    return SSP_OK;
+    return st.finish(true);  // the staged window copy dies at return
 }
 
 int ssp_cepstrum(ssp_ctx* ctx, const float* X, int64_t n_rows, int32_t n_bins, const float* fbank, int32_t n_filt,
@@ -260,25 +254,18 @@ int ssp_cepstrum(ssp_ctx* ctx, const float* X, int64_t n_rows, int32_t n_bins, c
     if (n_rows == 0) return SSP_OK;
     if (!X || !out) SSP_FAIL(SSP_ERR_INVALID, "ssp_cepstrum: null data pointer");
     if (n_rows > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_cepstrum: too many rows");
-    Staged sx, so, sf, sd;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)n_rows * n_bins * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dF = (const float*)sf.in(ctx, fbank, (size_t)n_filt * n_bins * sizeof(float), SSP_HOST, &rc);
-    SSP_TRY(rc);
-    const float* dD = (const float*)sd.in(ctx, dct, (size_t)n_ceps * n_filt * sizeof(float), SSP_HOST, &rc);
-    SSP_TRY(rc);
-    float* dO = (float*)so.out(ctx, out, (size_t)n_rows * n_ceps * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)n_rows * n_bins * sizeof(float));
+    const float *dF = st.in_host(fbank, (size_t)n_filt * n_bins * sizeof(float)), *dD = st.in_host(dct, (size_t)n_ceps * n_filt * sizeof(float));
+    float* dO = st.out(out, (size_t)n_rows * n_ceps * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     hipLaunchKernelGGL(cepstrum_kernel, dim3((unsigned)n_rows), dim3(256), (size_t)n_filt * sizeof(float), ctx->stream, dX, n_bins, dF,
                        n_filt, dD, n_ceps, log_mode, floor_mode, eps, dO);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(so.back(ctx, out, (size_t)n_rows * n_ceps * sizeof(float), where));
-    SSP_HIP(hipStreamSynchronize(ctx->stream));  // staged tables die at return
-    return SSP_OK;
+    return st.finish(true);  // staged tables die at return
 }
 
 int ssp_delta(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, int32_t dim, int32_t N, float* out,
@@ -293,12 +280,10 @@ int ssp_delta(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, i
     if (rows == 0) return SSP_OK;
     if (!feats || !out) SSP_FAIL(SSP_ERR_INVALID, "ssp_delta: null data pointer");
     const size_t bytes = (size_t)frame_seg->host.back() * dim * sizeof(float);
-    Staged sin, sout;
-    int rc;
-    const float* d_in = (const float*)sin.in(ctx, feats, bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_out = (float*)sout.out(ctx, out, bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_in = st.in(feats, bytes);
+    float* d_out = st.out(out, bytes);
+    SSP_TRY(st.status());
     int den = 0;
     for (int i = 1; i <= N; ++i) den += 2 * i * i;
     const int64_t n_blocks = ceil_div<int64_t>(rows, DELTA_RB);
@@ -313,9 +298,7 @@ int ssp_delta(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, i
                            (int)frame_seg->n, dim, N, 1.0f / (float)den, row0, rows);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(sout.back(ctx, out, bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_cmvn(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, int32_t dim, float* out, int where,
@@ -329,19 +312,15 @@ int ssp_cmvn(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, in
     if (!feats || !out) SSP_FAIL(SSP_ERR_INVALID, "ssp_cmvn: null data pointer");
     if (frame_seg->max_len() * dim > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_cmvn: utterance too long");
     const size_t bytes = (size_t)frame_seg->host.back() * dim * sizeof(float);
-    Staged sin, sout;
-    int rc;
-    const float* d_in = (const float*)sin.in(ctx, feats, bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_out = (float*)sout.out(ctx, out, bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_in = st.in(feats, bytes);
+    float* d_out = st.out(out, bytes);
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     SSP_TRY(launch_cmvn(d_in, d_out, frame_seg->dev.as<int64_t>(), frame_seg->n, dim, frame_seg->max_len(), ctx->stream));
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(sout.back(ctx, out, bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"
@@ -365,23 +344,19 @@ extern "C" int ssp_spectrum_abs(ssp_ctx* ctx, const float* reim, int64_t n_rows,
     SSP_TRY(use_ctx(ctx));
     if (kernel_ms) *kernel_ms = 0.f;
     if (n_rows < 0 || n_bins < 1 || (power != 1 && power != 2)) SSP_FAIL(SSP_ERR_INVALID, "ssp_spectrum_abs: bad argument");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_spectrum_abs: where");
+    SSP_TRY(check_where(where, "ssp_spectrum_abs"));
     if (n_rows == 0) return SSP_OK;
     if (!reim || !out) SSP_FAIL(SSP_ERR_INVALID, "ssp_spectrum_abs: null data pointer");
     const int64_t n = n_rows * n_bins;
     if ((n + 255) / 256 > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_spectrum_abs: too many elements");
-    Staged si, so;
-    int rc;
-    const float* dI = (const float*)si.in(ctx, reim, (size_t)n * 2 * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dO = (float*)so.out(ctx, out, (size_t)n * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dI = st.in(reim, (size_t)n * 2 * sizeof(float));
+    float* dO = st.out(out, (size_t)n * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     hipLaunchKernelGGL(spectrum_abs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dI, n, n_bins, scale, power, dO);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(so.back(ctx, out, (size_t)n * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }

@@ -1212,7 +1212,7 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
     if (!gmm || !frame_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_score: null handle");
     ssp_ctx* ctx = gmm->ctx;
     SSP_TRY(use_ctx(ctx));
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_score: where");
+    SSP_TRY(check_where(where, "ssp_gmm_score"));
     if (precision < 0 || precision > 4)
         SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_score: precision must be 0 (fp32 MFMA), 1 (bf16x3 MFMA + fp32 re-scoring inside the proven error bound), "
                                   "2 (bf16x3 MFMA alone), 3 (bf16x3 MFMA + fp32 re-scoring inside the calibrated, heuristic band) or 4 (auto: 1 or 0, "
@@ -1230,8 +1230,7 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
     if (n_utt > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "gmm: too many utterances");
     hipStream_t s = ctx->stream;
     const int M = gmm->n_models;
-    Staged sin, sll, ssc, sam;
-    int rc;
+    StageScope st(ctx, where);
     // Host-fed batches without re-scoring (precision 0 / 2) above two slices of features (GMM_UBM.py:181-197 hands host arrays): the
     // feature rows go through the ctx's ring in runs of whole utterances, copied in ahead of the kernels that score them (feed_rows,
     // staging.hpp) — the 81 ms a configs[2] batch spends on PCIe hide under its 120 ms of scoring.  Same kernels, same piece sums:
@@ -1248,10 +1247,9 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
             fcut.push_back(ho[(size_t)e]);
             u = e;
         }
-        float* d_sc = (float*)ssc.out(ctx, scores_out, (size_t)n_utt * M * sizeof(float), where, &rc);
-        SSP_TRY(rc);
-        int32_t* d_am = (int32_t*)sam.out(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where, &rc);
-        SSP_TRY(rc);
+        float* d_sc = st.out(scores_out, (size_t)n_utt * M * sizeof(float));
+        int32_t* d_am = st.out(argmax_out, (size_t)n_utt * sizeof(int32_t));
+        SSP_TRY(st.status());
         gmm->last_rescored = 0;
         Timer tms;
         SSP_TRY(tms.start(kernel_ms != nullptr, s));
@@ -1265,13 +1263,10 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
                                d_am ? d_am + u0 : nullptr, nullptr, s);
         }));
         SSP_TRY(tms.stop(s, kernel_ms));
-        SSP_TRY(ssc.back(ctx, scores_out, (size_t)n_utt * M * sizeof(float), where));
-        SSP_TRY(sam.back(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where));
-        SSP_HIP(hipStreamSynchronize(s));
-        return SSP_OK;
+        return st.finish();
     }
-    const float* d_feats = (const float*)sin.in(ctx, feats, (size_t)F * gmm->D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    const float* d_feats = st.in(feats, (size_t)F * gmm->D * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     bool timer_on = false;
     if (want_auto && !loglik_out && (scores_out || argmax_out)) {
@@ -1282,14 +1277,12 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
     }
     const bool bf16 = precision != 0;
     const size_t ll_bytes = (size_t)M * (size_t)std::max<int64_t>(F, 1) * sizeof(float);
-    float* d_sc = (float*)ssc.out(ctx, scores_out, (size_t)n_utt * M * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    int32_t* d_am = (int32_t*)sam.out(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
+    float* d_ll = st.out(loglik_out, ll_bytes);
+    float* d_sc = st.out(scores_out, (size_t)n_utt * M * sizeof(float));
+    int32_t* d_am = st.out(argmax_out, (size_t)n_utt * sizeof(int32_t));
+    SSP_TRY(st.status());
     if (loglik_out) {
         // the caller wants score_samples: the whole [M x F] matrix in one pass, per-utterance means from it
-        float* d_ll = (float*)sll.out(ctx, loglik_out, ll_bytes, where, &rc);
-        SSP_TRY(rc);
         SSP_TRY(tm.start(kernel_ms != nullptr, s));
         gmm->last_rescored = 0;  // (one pass at the asked precision, nothing is listed or scored twice: an earlier call's count does not stand)
         GmmArgs a{};
@@ -1443,11 +1436,7 @@ int ssp_gmm_score(ssp_gmm* gmm, const float* feats, const ssp_segments* frame_se
         SSP_TRY(tm.start(kernel_ms != nullptr, s));
     }
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sll.back(ctx, loglik_out, ll_bytes, where));
-    SSP_TRY(ssc.back(ctx, scores_out, (size_t)n_utt * M * sizeof(float), where));
-    SSP_TRY(sam.back(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 /* precision = 4: what the last such call's pilot saw and chose */

@@ -577,7 +577,7 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
         SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: bad shape or null array");
     if (D > 4 * EM_DG) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_gmm_em_stats: D=%d exceeds the supported feature dimension (%d)", D, 4 * EM_DG);
     if (n_frames < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: no frames");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_em_stats: where");
+    SSP_TRY(check_where(where, "ssp_gmm_em_stats"));
     const int W = 2 * D + 1, Kp = (K + EM_KC - 1) / EM_KC * EM_KC;
     std::vector<float> par((size_t)Kp * W, 0.f);
     SSP_TRY(em_pack(K, D, Kp, weights, means, covars, par.data(), -1));
@@ -592,10 +592,9 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     // device scratch lives in the ctx (grow-only): an EM loop calls this once per iteration
     DevBuf &d_par = ctx->scratch[0], &d_lse = ctx->scratch[1], &d_lsep = ctx->scratch[2], &d_part = ctx->scratch[3],
            &d_out = ctx->scratch[4];
-    Staged sx;
-    int rc;
-    const float* d_x = (const float*)sx.in(ctx, feats, (size_t)n_frames * D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(feats, (size_t)n_frames * D * sizeof(float));
+    SSP_TRY(st.status());
     SSP_TRY(d_par.reserve(par.size() * sizeof(float)));
     SSP_TRY(d_lse.reserve((size_t)n_frames * sizeof(float)));
     SSP_TRY(d_lsep.reserve((size_t)std::max<int64_t>(n_tiles, G) * sizeof(float)));
@@ -624,7 +623,7 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     ssp_segments* seg = nullptr;
     if (mfma && !fuse) {
         const int64_t off[2] = {0, n_frames};
-        rc = ssp_gmm_pack(ctx, 1, K, D, weights, means, covars, 0, &scorer);
+        int rc = ssp_gmm_pack(ctx, 1, K, D, weights, means, covars, 0, &scorer);
         if (rc == SSP_OK) rc = segments_make(ctx, off, 1, &seg);
         if (rc != SSP_OK) {
             ssp_gmm_destroy(scorer);
@@ -632,7 +631,7 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
         }
     }
     Timer tm;
-    rc = tm.start(kernel_ms != nullptr, s);
+    int rc = tm.start(kernel_ms != nullptr, s);
     if (rc == SSP_OK && fuse) {
         switch (nct) {
             case 1: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<1, true>), dim3(G, 1), dim3(256), lds3, s, a); break;
@@ -702,7 +701,7 @@ static int em_stats_batch_impl(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, co
     const int W = 2 * D + 1, nct = (W + 31) / 32;
     if (nct > 3) SSP_FAIL(SSP_ERR_UNSUPPORTED, "%s: D=%d exceeds the batched path's feature dimension (47)", fn, D);
     if (n_rows < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "%s: no frames", fn);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", fn);
+    SSP_TRY(check_where(where, fn));
     for (int m = 0; m < M; ++m) {
         if (n_frames[m] < 1) SSP_FAIL(SSP_ERR_INVALID, "%s: model %d has no frames", fn, m);
         if (row_off[m] < 0 || row_off[m] > n_rows - n_frames[m])
@@ -755,10 +754,9 @@ static int em_stats_batch_impl(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, co
     hipStream_t s = ctx->stream;
     DevBuf &d_par = ctx->scratch[0], &d_lse = ctx->scratch[1], &d_lsep = ctx->scratch[2], &d_part = ctx->scratch[3],
            &d_out = ctx->scratch[4], &d_tab = ctx->scratch[5];
-    Staged sx;
-    int rc;
-    const float* d_x = (const float*)sx.in(ctx, feats, (size_t)n_rows * D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(feats, (size_t)n_rows * D * sizeof(float));
+    SSP_TRY(st.status());
     const size_t tab_models = (size_t)M * sizeof(EmModel), tab_work = work.size() * sizeof(int2), tab_tiles = tiles.size() * sizeof(int2);
     SSP_TRY(d_par.reserve(par.size() * sizeof(float)));
     SSP_TRY(d_lse.reserve((size_t)std::max<int64_t>(lse_tot, 1) * sizeof(float)));
@@ -791,7 +789,7 @@ static int em_stats_batch_impl(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, co
     if (!fuse && lds_lse > 64 * 1024)
         SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_em_lse_mfma_seg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lse));
     Timer tm;
-    rc = tm.start(kernel_ms != nullptr, s);
+    int rc = tm.start(kernel_ms != nullptr, s);
     if (rc == SSP_OK) {
         if (!fuse) {
             EmBatchArgs bt = b;

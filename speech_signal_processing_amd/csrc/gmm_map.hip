@@ -525,7 +525,7 @@ int ssp_gmm_map_score(ssp_gmm_map* map, const float* feats, const ssp_segments* 
     SSP_TRY(map_check(map, frame_seg, C, "ssp_gmm_map_score"));
     ssp_ctx* ctx = map->ctx;
     SSP_TRY(use_ctx(ctx));
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_map_score: where");
+    SSP_TRY(check_where(where, "ssp_gmm_map_score"));
     if (kernel_ms) *kernel_ms = 0.f;
     const int64_t f0 = frame_seg->host.front(), F = frame_seg->host.back(), n_utt = frame_seg->n;
     if (n_utt == 0) return SSP_OK;
@@ -535,18 +535,14 @@ int ssp_gmm_map_score(ssp_gmm_map* map, const float* feats, const ssp_segments* 
     hipStream_t s = ctx->stream;
     const int D = map->D, S = map->S;
     const size_t rows = (size_t)std::max<int64_t>(F, 1);
-    Staged sin, sdf, sub, sam, six;
-    int rc;
-    const float* d_x = (const float*)sin.in(ctx, feats, (size_t)F * D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* d_diff = (float*)sdf.out(ctx, diff_out, (size_t)n_utt * S * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* d_ubm = (float*)sub.out(ctx, ubm_out, (size_t)n_utt * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    int32_t* d_am = (int32_t*)sam.out(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    int32_t* d_idx = (int32_t*)six.out(ctx, idx_out, rows * C * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(feats, (size_t)F * D * sizeof(float));
+    float* d_diff = st.out(diff_out, (size_t)n_utt * S * sizeof(float));
+    float* d_ubm = st.out(ubm_out, (size_t)n_utt * sizeof(float));
+    int32_t* d_am = st.out(argmax_out, (size_t)n_utt * sizeof(int32_t));
+    // (a batch without frames has no idx_out entries to give back: `rows` is 1 then, the caller's array empty)
+    int32_t* d_idx = st.out(F > 0 || where == SSP_DEVICE ? idx_out : nullptr, rows * C * sizeof(int32_t));
+    SSP_TRY(st.status());
     if (!d_idx) {
         SSP_TRY(map->idx.reserve(rows * C * sizeof(int32_t)));
         d_idx = map->idx.as<int32_t>();
@@ -597,12 +593,7 @@ int ssp_gmm_map_score(ssp_gmm_map* map, const float* feats, const ssp_segments* 
         SSP_FAIL(SSP_ERR_HIP, "ssp_gmm_map_score: kernel launch failed");
     }
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sdf.back(ctx, diff_out, (size_t)n_utt * S * sizeof(float), where));
-    SSP_TRY(sub.back(ctx, ubm_out, (size_t)n_utt * sizeof(float), where));
-    SSP_TRY(sam.back(ctx, argmax_out, (size_t)n_utt * sizeof(int32_t), where));
-    SSP_TRY(six.back(ctx, idx_out, (size_t)F * C * sizeof(int32_t), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_gmm_map_score_list(ssp_gmm_map* map, const void* const* rows, int row_type, int32_t dim, const ssp_segments* frame_seg, int32_t C,

@@ -356,7 +356,7 @@ int ssp_gru_forward(ssp_gru* gru, const float* X, int64_t N, int32_t T, float* s
     ssp::TraceRange trace_("ssp_gru_forward");
     if (!gru) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_forward: null handle");
     if (kernel_ms) *kernel_ms = 0.f;
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_forward: where");
+    SSP_TRY(check_where(where, "ssp_gru_forward"));
     if (N < 0 || T < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_forward: N >= 0 and T >= 1");
     if (N == 0) return SSP_OK;
     if (!X) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_forward: null input");
@@ -382,12 +382,10 @@ int ssp_gru_forward(ssp_gru* gru, const float* X, int64_t N, int32_t T, float* s
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
     for (int64_t c0 = 0; c0 < N; c0 += slab) {
         const int64_t n = N - c0 < slab ? N - c0 : slab;
-        Staged sx, sm;
-        int rc;
-        const float* dX = (const float*)sx.in(ctx, X + c0 * T * D, (size_t)n * T * D * sizeof(float), where, &rc);
-        SSP_TRY(rc);
-        float* dM = (float*)sm.out(ctx, mean_out ? mean_out + c0 * H : nullptr, (size_t)n * H * sizeof(float), where, &rc);
-        SSP_TRY(rc);
+        StageScope st(ctx, where);  // (of this slab)
+        const float* dX = st.in(X + c0 * T * D, (size_t)n * T * D * sizeof(float));
+        float* dM = st.out(mean_out ? mean_out + c0 * H : nullptr, (size_t)n * H * sizeof(float));
+        SSP_TRY(st.status());
         float* P = ctx->gru_proj.as<float>();
         float* S = in_place ? seq_out + c0 * T * H : gru->seq.as<float>();
         SSP_TRY(ssp_dense_forward(ctx, dX, n * T, D, gru->Wt.as<float>(), gru->bin.as<float>(), (int32_t)H3, 0, P, SSP_DEVICE, nullptr));
@@ -422,12 +420,12 @@ int ssp_gru_forward(ssp_gru* gru, const float* X, int64_t N, int32_t T, float* s
         if (dM) {
             hipLaunchKernelGGL(gru_time_mean_kernel, dim3((unsigned)((n * H + 255) / 256)), dim3(256), 0, s, S, n, T, H, dM);
             SSP_HIP(hipGetLastError());
-            SSP_TRY(sm.back(ctx, mean_out + c0 * H, (size_t)n * H * sizeof(float), where));
+            SSP_TRY(st.copy_back());
         }
         if (seq_out && !in_place)
             SSP_HIP(hipMemcpyAsync(seq_out + c0 * T * H, S, (size_t)n * T * H * sizeof(float),
                                    where == SSP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-        if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));  // (the staging of this slab is given back at the end of the scope)
+        SSP_TRY(st.finish());  // (the slab's wait; its staging is given back at the end of the scope)
     }
     SSP_TRY(tm.stop(s, kernel_ms));
     return SSP_OK;
@@ -438,7 +436,7 @@ int ssp_conv2d_same_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t T, 
     ssp::TraceRange trace_("ssp_conv2d_same_forward");
     if (kernel_ms) *kernel_ms = 0.f;
     if (N < 0 || T < 1 || D < 1 || kh < 1 || kw < 1 || F < 1 || sh < 1 || sw < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_conv2d_same_forward: bad shape");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_conv2d_same_forward: where");
+    SSP_TRY(check_where(where, "ssp_conv2d_same_forward"));
     if (kh > CONV_MAXK || kw > CONV_MAXK || F > CONV_MAXF || sh > 2 || sw > 2)
         SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_conv2d_same_forward: kernels up to %d x %d, up to %d filters, strides 1 or 2", CONV_MAXK, CONV_MAXK, CONV_MAXF);
     if ((int64_t)T * D > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_conv2d_same_forward: T x D above 2^31");
@@ -454,51 +452,41 @@ int ssp_conv2d_same_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t T, 
     a.pl = (pw > 0 ? pw : 0) / 2;
     a.total = N * a.To * a.Do * F;
     hipStream_t s = ctx->stream;
-    Staged sx, sk, sb, sy;
-    int rc;
-    a.X = (const float*)sx.in(ctx, X, (size_t)N * T * D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    a.K = (const float*)sk.in(ctx, K, (size_t)kh * kw * F * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    a.bias = (const float*)sb.in(ctx, bias, (size_t)F * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    a.Y = (float*)sy.out(ctx, Y, (size_t)a.total * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    a.X = st.in(X, (size_t)N * T * D * sizeof(float));
+    a.K = st.in(K, (size_t)kh * kw * F * sizeof(float));
+    a.bias = st.in(bias, (size_t)F * sizeof(float));
+    a.Y = st.out(Y, (size_t)a.total * sizeof(float));
+    SSP_TRY(st.status());
     const int64_t blocks = (a.total + 255) / 256;
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
     hipLaunchKernelGGL(conv2d_same_kernel, dim3((unsigned)(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sy.back(ctx, Y, (size_t)a.total * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_l2_normalize(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, float eps, float* Y, int where, float* kernel_ms) {
     ssp::TraceRange trace_("ssp_l2_normalize");
     if (kernel_ms) *kernel_ms = 0.f;
     if (N < 0 || d < 1 || !(eps >= 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_l2_normalize: bad shape or eps");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_l2_normalize: where");
+    SSP_TRY(check_where(where, "ssp_l2_normalize"));
     if (N > 0 && (!X || !Y)) SSP_FAIL(SSP_ERR_INVALID, "ssp_l2_normalize: null array");
     if ((N + 3) / 4 > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_l2_normalize: too many rows for one launch");
     SSP_TRY(use_ctx(ctx));
     if (N == 0) return SSP_OK;
     hipStream_t s = ctx->stream;
-    Staged sx, sy;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dY = (float*)sy.out(ctx, Y, (size_t)N * d * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)N * d * sizeof(float));
+    float* dY = st.out(Y, (size_t)N * d * sizeof(float));
+    SSP_TRY(st.status());
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
     hipLaunchKernelGGL(l2_normalize_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, dX, N, d, eps, dY);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sy.back(ctx, Y, (size_t)N * d * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

@@ -330,7 +330,7 @@ extern "C" int ssp_kmeanspp_seed(ssp_ctx* ctx, int32_t P, int32_t K, int32_t D, 
         SSP_FAIL(SSP_ERR_INVALID, "ssp_kmeanspp_seed: bad shape or null array");
     if (D > KPP_MAX_D) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_kmeanspp_seed: D=%d exceeds the kernel's feature dimension (%d)", D, KPP_MAX_D);
     if (n_rows < 1 || !feats) SSP_FAIL(SSP_ERR_INVALID, "ssp_kmeanspp_seed: no rows");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_kmeanspp_seed: where");
+    SSP_TRY(check_where(where, "ssp_kmeanspp_seed"));
     const int L = 2 + (int)std::log((double)K);  // candidates per step: 2 + int(ln K), as _kmeanspp and sklearn draw them
     if (L > KPP_MAX_L) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_kmeanspp_seed: K=%d gives more than %d candidates per step", K, KPP_MAX_L);
     int64_t sel_total = 0, work_total = 0;
@@ -361,10 +361,9 @@ extern "C" int ssp_kmeanspp_seed(ssp_ctx* ctx, int32_t P, int32_t K, int32_t D, 
     }
     hipStream_t s = ctx->stream;
     DevBuf &d_work = ctx->scratch[0], &d_tab = ctx->scratch[1], &d_out = ctx->scratch[2];
-    Staged sx;
-    int rc;
-    const float* d_x = (const float*)sx.in(ctx, feats, (size_t)n_rows * D * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(feats, (size_t)n_rows * D * sizeof(float));
+    SSP_TRY(st.status());
     // one table upload: the draws, the lists, the problems (8-byte entries first)
     const size_t n_u = (size_t)P * (K - 1) * L, b_u = n_u * sizeof(double), b_sel = (size_t)sel_total * sizeof(int64_t), b_pr = (size_t)P * sizeof(KppProb);
     std::vector<char> tab(b_u + b_sel + b_pr);
@@ -390,7 +389,7 @@ extern "C" int ssp_kmeanspp_seed(ssp_ctx* ctx, int32_t P, int32_t K, int32_t D, 
     a.D = D;
     a.L = L;
     Timer tm;
-    rc = tm.start(kernel_ms != nullptr, s);
+    int rc = tm.start(kernel_ms != nullptr, s);
     if (rc == SSP_OK) {
         switch (std::min(L, KPP_LT_MAX)) {
             case 2: rc = kpp_launch<2>(a, P, s); break;

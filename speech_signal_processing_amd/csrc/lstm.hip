@@ -310,7 +310,7 @@ int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* fra
     ssp_ctx* ctx = lstm->ctx;
     SSP_TRY(use_ctx(ctx));
     if (kernel_ms) *kernel_ms = 0.f;
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_forward: where");
+    SSP_TRY(check_where(where, "ssp_lstm_forward"));
     if (frame_seg->ctx && frame_seg->ctx->device != ctx->device) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_forward: the segments live on another device");
     const int64_t n_seq = frame_seg->n;
     if (n_seq == 0) return SSP_OK;
@@ -320,12 +320,10 @@ int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* fra
     hipStream_t s = ctx->stream;
     const size_t in_bytes = (size_t)frame_seg->host.back() * lstm->d_in * sizeof(float);
     const size_t out_bytes = (size_t)n_seq * lstm->units * sizeof(float);
-    Staged sx, sy;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, in_bytes ? feats : nullptr, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* dY = (float*)sy.out(ctx, h_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(in_bytes ? feats : nullptr, in_bytes);
+    float* dY = st.out(h_out, out_bytes);
+    SSP_TRY(st.status());
     LstmArgs a{};
     a.feats = dX;
     a.off = frame_seg->dev.as<int64_t>();
@@ -351,9 +349,7 @@ int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* fra
         default: SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_lstm_forward: no kernel instance");
     }
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sy.back(ctx, h_out, out_bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

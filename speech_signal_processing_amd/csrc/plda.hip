@@ -385,17 +385,15 @@ int ssp_plda_stats(ssp_ctx* ctx, const float* X, const int32_t* labels, int64_t 
     SSP_TRY(use_ctx(ctx));
     if (N < 1 || q < 1 || S < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_stats: bad shape (N=%lld, q=%d, S=%d)", (long long)N, q, S);
     if (q > PL_QMAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_plda_stats: q=%d exceeds the supported dimension (%d)", q, PL_QMAX);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_stats: where");
+    SSP_TRY(check_where(where, "ssp_plda_stats"));
     if (!X || !labels || !sum_out || !count_out || !mean_out || !sw_out) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_stats: null pointer");
     if (ceil_div<int64_t>(N, 256) > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_plda_stats: too many rows");
     if (kernel_ms) *kernel_ms = 0.f;
     hipStream_t s = ctx->stream;
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * q * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)N * q * sizeof(float));
+    const int32_t* dL = st.in(labels, (size_t)N * sizeof(int32_t));
+    SSP_TRY(st.status());
     const size_t Sq = (size_t)S * q, qq = (size_t)q * q;
     const int64_t slab = std::min<int64_t>(N, (int64_t)PL_SLAB_CHUNKS * PL_KC);
     const int slab_chunks = (int)ceil_div<int64_t>(slab, PL_KC);
@@ -556,30 +554,22 @@ int ssp_plda_score(ssp_plda* p, const float* T, int64_t N, float* llr_out, int32
     ssp_ctx* ctx = p->ctx;
     SSP_TRY(use_ctx(ctx));
     if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_score: N=%lld", (long long)N);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_score: where");
+    SSP_TRY(check_where(where, "ssp_plda_score"));
     if (N > 0 && !T) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_score: null test vectors");
     if (kernel_ms) *kernel_ms = 0.f;
     if (N == 0) return SSP_OK;
-    Staged st, sl, sa, sm;
-    int rc;
-    const float* dT = (const float*)st.in(ctx, T, (size_t)N * p->q * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dL = (float*)sl.out(ctx, llr_out, (size_t)N * p->S * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    int32_t* dA = (int32_t*)sa.out(ctx, argmax_out, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    float* dM = (float*)sm.out(ctx, max_out, (size_t)N * sizeof(float), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dT = st.in(T, (size_t)N * p->q * sizeof(float));
+    float* dL = st.out(llr_out, (size_t)N * p->S * sizeof(float));
+    int32_t* dA = st.out(argmax_out, (size_t)N * sizeof(int32_t));
+    float* dM = st.out(max_out, (size_t)N * sizeof(float));
+    SSP_TRY(st.status());
     PldaScoreArgs a{dT, p->img.as<float>(), p->c.as<float>(), p->cls.as<int32_t>(), dL, dA, dM, N, p->q, p->S, p->n_tiles};
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     SSP_TRY(p->shared ? launch_plda_score_nq<true>(p->nq, a, ctx->stream) : launch_plda_score_nq<false>(p->nq, a, ctx->stream));
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(sl.back(ctx, llr_out, (size_t)N * p->S * sizeof(float), where));
-    SSP_TRY(sa.back(ctx, argmax_out, (size_t)N * sizeof(int32_t), where));
-    SSP_TRY(sm.back(ctx, max_out, (size_t)N * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

@@ -431,7 +431,7 @@ extern "C" int ssp_plp_features(ssp_ctx* ctx, const float* logspec, const ssp_se
     const int nb = n_bands, P = plp_order - 1, P1 = plp_order;
     SSP_TRY(plp_check_sizes("ssp_plp_features", nb, plp_order));
     if (!(fmax_hz > 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_features: fmax");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_features: where");
+    SSP_TRY(check_where(where, "ssp_plp_features"));
     if (out_type != 0 && out_type != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_features: out_type must be 0 (float32) or 1 (float64)");
     if (delta_order < 0 || delta_order > 2) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_features: delta_order must be 0, 1 or 2");
     if (left_dim < 0 || left_dim > 4096 || left_dim % (1 + delta_order) != 0)
@@ -446,14 +446,11 @@ extern "C" int ssp_plp_features(ssp_ctx* ctx, const float* logspec, const ssp_se
     hipStream_t s = ctx->stream;
     const size_t in_bytes = (size_t)F * nb * sizeof(float), left_bytes = (size_t)F * left_dim * sizeof(float),
                  out_bytes = (size_t)F * D * (out_type == 1 ? sizeof(double) : sizeof(float));
-    Staged sin, sleft, sout;
-    int rc;
-    const float* d_x = (const float*)sin.in(ctx, logspec, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    const float* d_left = left_dim > 0 ? (const float*)sleft.in(ctx, left, left_bytes, where, &rc) : nullptr;
-    SSP_TRY(rc);
-    void* d_out = sout.out(ctx, feats_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(logspec, in_bytes);
+    const float* d_left = st.in(left_dim > 0 ? left : nullptr, left_bytes);
+    void* d_out = st.out(feats_out, out_bytes);
+    SSP_TRY(st.status());
     // one path per call, decided on the longest utterance: the fused kernel for the two fixed sizes when that utterance fits the LDS
     // budget, else the existing kernels chained on the stream
     const bool fixed21 = nb == 21 && P == 12, fixed17 = nb == 17 && P == 12;
@@ -507,9 +504,7 @@ extern "C" int ssp_plp_features(ssp_ctx* ctx, const float* logspec, const ssp_se
         SSP_HIP(hipGetLastError());
     }
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sout.back(ctx, feats_out, out_bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 extern "C" int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segments* frame_seg, int32_t n_bands, float fmax_hz,
@@ -521,7 +516,7 @@ extern "C" int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segmen
     const int nb = n_bands, P = plp_order - 1;  // plp_order counts c0, as sidekit's argument does
     SSP_TRY(plp_check_sizes("ssp_plp_post", nb, plp_order));
     if (!(fmax_hz > 0.f)) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_post: fmax");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_post: where");
+    SSP_TRY(check_where(where, "ssp_plp_post"));
     if (frame_seg->host.front() != 0) SSP_FAIL(SSP_ERR_INVALID, "ssp_plp_post: segments must start at frame 0");
     const int64_t F = frame_seg->total();
     if (F == 0) return SSP_OK;
@@ -533,12 +528,10 @@ extern "C" int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segmen
     SSP_HIP(hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, s));
     SSP_HIP(hipStreamSynchronize(s));  // `tab` (host) dies at return
     const size_t in_bytes = (size_t)F * nb * sizeof(float), out_bytes = (size_t)F * (P + 1) * sizeof(float);
-    Staged sin, sout;
-    int rc;
-    const float* d_x = (const float*)sin.in(ctx, logspec, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_out = (float*)sout.out(ctx, ceps_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* d_x = st.in(logspec, in_bytes);
+    float* d_out = st.out(ceps_out, out_bytes);
+    SSP_TRY(st.status());
     const float* d_in = d_x;
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, s));
@@ -557,7 +550,5 @@ extern "C" int ssp_plp_post(ssp_ctx* ctx, const float* logspec, const ssp_segmen
     else hipLaunchKernelGGL(plp_cep_kernel, dim3(grid), dim3(128), lds, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sout.back(ctx, ceps_out, out_bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }

@@ -267,34 +267,24 @@ int ssp_topn_stats(ssp_ctx* ctx, const float* scores, int64_t rows, int32_t cols
     if (n < 1 || rows < 0 || cols < 1 || ld < cols)
         SSP_FAIL(SSP_ERR_INVALID, "ssp_topn_stats: bad shape (rows=%lld, cols=%d, ld=%lld, n=%d)", (long long)rows, cols, (long long)ld, n);
     if (axis != 0 && axis != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_topn_stats: axis=%d", axis);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_topn_stats: where");
+    SSP_TRY(check_where(where, "ssp_topn_stats"));
     if (rows > 0 && !scores) SSP_FAIL(SSP_ERR_INVALID, "ssp_topn_stats: null scores");
     const int64_t len = axis == 1 ? (int64_t)cols : rows, n_lines = axis == 1 ? rows : (int64_t)cols;
     if (len > SN_LINE_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_topn_stats: lines of %lld entries exceed the supported length (%d)", (long long)len, SN_LINE_MAX);
     SSP_TRY(use_ctx(ctx));
     if (kernel_ms) *kernel_ms = 0.f;
     if (rows == 0) return SSP_OK;
-    Staged sx, sm, ss, sk;
-    int rc;
+    StageScope st(ctx, where);
     const size_t in_bytes = ((size_t)(rows - 1) * (size_t)ld + (size_t)cols) * sizeof(float), out_bytes = (size_t)n_lines * sizeof(float);
-    const float* dX = (const float*)sx.in(ctx, scores, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* dM = (float*)sm.out(ctx, mean_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* dS = (float*)ss.out(ctx, std_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* dK = (float*)sk.out(ctx, kth_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    const float* dX = st.in(scores, in_bytes);
+    float *dM = st.out(mean_out, out_bytes), *dS = st.out(std_out, out_bytes), *dK = st.out(kth_out, out_bytes);
+    SSP_TRY(st.status());
     TopnArgs a{dX, dM, dS, dK, n_lines, ld, (int32_t)len, (int32_t)std::min<int64_t>(n, len)};
     Timer tm;
     SSP_TRY(tm.start(kernel_ms != nullptr, ctx->stream));
     SSP_TRY(axis == 1 ? launch_topn<1>(a, ctx->stream) : launch_topn<0>(a, ctx->stream));
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(sm.back(ctx, mean_out, out_bytes, where));
-    SSP_TRY(ss.back(ctx, std_out, out_bytes, where));
-    SSP_TRY(sk.back(ctx, kth_out, out_bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int64_t ld, const float* row_mean, const float* row_std,
@@ -304,7 +294,7 @@ int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int
     if (!ctx) SSP_FAIL(SSP_ERR_INVALID, "null ssp_ctx");
     if (N < 0 || S < 1 || ld < S) SSP_FAIL(SSP_ERR_INVALID, "ssp_snorm_apply: bad shape (N=%lld, S=%d, ld=%lld)", (long long)N, S, (long long)ld);
     if (out && ld_out < S) SSP_FAIL(SSP_ERR_INVALID, "ssp_snorm_apply: ld_out=%lld < S=%d", (long long)ld_out, S);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_snorm_apply: where");
+    SSP_TRY(check_where(where, "ssp_snorm_apply"));
     if ((row_mean == nullptr) != (row_std == nullptr) || (col_mean == nullptr) != (col_std == nullptr))
         SSP_FAIL(SSP_ERR_INVALID, "ssp_snorm_apply: a mean without its deviation");
     if (!row_mean && !col_mean) SSP_FAIL(SSP_ERR_INVALID, "ssp_snorm_apply: neither row nor column statistics");
@@ -314,28 +304,18 @@ int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int
     if (kernel_ms) *kernel_ms = 0.f;
     if (N == 0) return SSP_OK;
     if (ceil_div<int64_t>(N, 4) > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_snorm_apply: too many rows for one launch");
-    Staged sx, so, srm, srs, scm, scs, sa, smx;
-    int rc;
+    StageScope st(ctx, where);
     const size_t in_bytes = ((size_t)(N - 1) * (size_t)ld + (size_t)S) * sizeof(float);
     const size_t out_bytes = ((size_t)(N - 1) * (size_t)(out ? ld_out : 0) + (size_t)S) * sizeof(float);
-    const float* dX = (const float*)sx.in(ctx, scores, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    const float* dRm = (const float*)srm.in(ctx, row_mean, (size_t)N * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dRs = (const float*)srs.in(ctx, row_std, (size_t)N * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dCm = (const float*)scm.in(ctx, col_mean, (size_t)S * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* dCs = (const float*)scs.in(ctx, col_std, (size_t)S * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    float* dO = (float*)so.out(ctx, out, out_bytes, where, &rc);  // (a staged output never aliases the staged input: the kernel reads, then writes)
-    SSP_TRY(rc);
-    int32_t* dA = (int32_t*)sa.out(ctx, argmax_out, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
-    float* dMx = (float*)smx.out(ctx, max_out, (size_t)N * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    if (where == SSP_HOST && out && ld_out > S)  // the gaps between the rows of a host output keep their bytes
-        SSP_HIP(hipMemcpyAsync(dO, out, out_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const float* dX = st.in(scores, in_bytes);
+    const float *dRm = st.in(row_mean, (size_t)N * sizeof(float)), *dRs = st.in(row_std, (size_t)N * sizeof(float));
+    const float *dCm = st.in(col_mean, (size_t)S * sizeof(float)), *dCs = st.in(col_std, (size_t)S * sizeof(float));
+    // (a staged output never aliases the staged input: the kernel reads, then writes; pre-loaded when the gaps between the rows of a
+    //  host output have to keep their bytes)
+    float* dO = st.out(out, out_bytes, ld_out > S);
+    int32_t* dA = st.out(argmax_out, (size_t)N * sizeof(int32_t));
+    float* dMx = st.out(max_out, (size_t)N * sizeof(float));
+    SSP_TRY(st.status());
     ApplyArgs a{dX, dO, dRm, dRs, dCm, dCs, dA, dMx, N, ld, ld_out, S, std_floor};
     const dim3 g((unsigned)ceil_div<int64_t>(N, 4)), b(256);
     Timer tm;
@@ -348,11 +328,7 @@ int ssp_snorm_apply(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int
         hipLaunchKernelGGL((snorm_apply_kernel<true, false>), g, b, 0, ctx->stream, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(ctx->stream, kernel_ms));
-    SSP_TRY(so.back(ctx, out, out_bytes, where));
-    SSP_TRY(sa.back(ctx, argmax_out, (size_t)N * sizeof(int32_t), where));
-    SSP_TRY(smx.back(ctx, max_out, (size_t)N * sizeof(float), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(ctx->stream));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_det_counts(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int64_t ld, const int32_t* target, const float* thresholds, int32_t M,
@@ -361,7 +337,7 @@ int ssp_det_counts(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int6
     if (!ctx) SSP_FAIL(SSP_ERR_INVALID, "null ssp_ctx");
     if (N < 0 || S < 1 || ld < S) SSP_FAIL(SSP_ERR_INVALID, "ssp_det_counts: bad shape (N=%lld, S=%d, ld=%lld)", (long long)N, S, (long long)ld);
     if (M < 0 || M > SN_DET_MAX_M) SSP_FAIL(SSP_ERR_INVALID, "ssp_det_counts: M=%d outside [0, %d]", M, SN_DET_MAX_M);
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_det_counts: where");
+    SSP_TRY(check_where(where, "ssp_det_counts"));
     if (!tar_hist || !non_hist || !nan_count || !range_out || (M > 0 && !thresholds) || (N > 0 && (!scores || !target)))
         SSP_FAIL(SSP_ERR_INVALID, "ssp_det_counts: null pointer");
     for (int j = 0; j < M; ++j)
@@ -378,12 +354,10 @@ int ssp_det_counts(ssp_ctx* ctx, const float* scores, int64_t N, int32_t S, int6
             SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_det_counts: too many scores per workgroup for 32-bit bins");
         if (ceil_div<int64_t>(N, 256) > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_det_counts: too many rows");
         hipStream_t s = ctx->stream;
-        Staged sx, st;
-        int rc;
-        const float* dX = (const float*)sx.in(ctx, scores, ((size_t)(N - 1) * (size_t)ld + (size_t)S) * sizeof(float), where, &rc);
-        SSP_TRY(rc);
-        const int32_t* dT = (const int32_t*)st.in(ctx, target, (size_t)N * sizeof(int32_t), where, &rc);
-        SSP_TRY(rc);
+        StageScope st(ctx, where);
+        const float* dX = st.in(scores, ((size_t)(N - 1) * (size_t)ld + (size_t)S) * sizeof(float));
+        const int32_t* dT = st.in(target, (size_t)N * sizeof(int32_t));
+        SSP_TRY(st.status());
         DevBuf th, acc;
         SSP_TRY(th.alloc((size_t)std::max(M, 1) * sizeof(float)));
         SSP_TRY(acc.alloc(h.size() * sizeof(unsigned long long)));

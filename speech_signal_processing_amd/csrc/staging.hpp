@@ -1,5 +1,5 @@
 // Host-side staging of SSP_HOST calls (included twice by common.hpp: part 1 before ssp_ctx — the pool it holds —, part 2 behind it — the
-// per-operand helper).  No device code here: the file is deliberately NOT part of bench.py's kernel-source hash.
+// per-call scope and its per-operand primitive).  No device code here: the file is deliberately NOT part of bench.py's kernel-source hash.
 #if SSP_STAGING_PART == 1
 #include <algorithm>
 #include <atomic>
@@ -238,7 +238,88 @@ struct HostPipe {
 #include <cstdlib>
 #include <memory>
 namespace ssp {
-// Staging helper for SSP_HOST calls: device copy of a host input / device scratch for an output.
+// The staged operands of ONE host-or-device call (or of one slab of it).  in / out hand back the pointer the kernels use — the argument
+// itself with SSP_DEVICE or for a null pointer, else a staged device copy — and an output's host pointer and byte count are kept, once,
+// for the copy back.  The first failure sticks: later in / out calls stage nothing and return null, so ONE SSP_TRY(status()) behind the
+// operand block checks them all.  copy_back queues the device-to-host copies in the order of the out calls and does not wait; finish
+// adds the call's one wait on SSP_HOST.  A call that leaves with copies queued and not waited for (an error return) waits in the
+// destructor, before the slots go back: no copy outlives the call on the caller's arrays.  No heap: CAP operands, as the pool has slots.
+// (a template over the operand type, HIP-free like StagePoolT: tests/native/stage_scope.cpp drives it with a malloc-backed stand-in.
+//  Op: in / out / back as Staged below, static int wait(ctx) — sets the error message — and static void wait_quietly(ctx))
+template <class Op, class Ctx>
+struct StageScopeT {
+    static constexpr int CAP = 8;  // ssp_snorm_apply's need, the largest; = StagePoolT::SLOTS
+    StageScopeT(const Ctx* c, int w) : ctx(c), where(w) {}
+    ~StageScopeT() {
+        if (in_flight) Op::wait_quietly(ctx);
+    }
+    int status() const { return rc; }
+    template <class T>
+    const T* in(const T* host, size_t bytes) {
+        return static_cast<const T*>(stage(host, bytes, where, true, false));
+    }
+    template <class T>
+    const T* in_host(const T* host, size_t bytes) {  // a host array in the device form too (tables): such a call ends in finish(true)
+        return static_cast<const T*>(stage(host, bytes, SSP_HOST, true, false));
+    }
+    template <class T>
+    T* out(T* host, size_t bytes, bool preload = false) {  // preload: the staged copy starts out with the caller's bytes
+        return static_cast<T*>(stage(host, bytes, where, preload, true));
+    }
+    int copy_back() {
+        for (int i = 0; i < n && rc == SSP_OK; ++i) {
+            if (!back_to[i]) continue;
+            in_flight = true;
+            rc = op[i].back(ctx, back_to[i], back_bytes[i], SSP_HOST);
+            back_to[i] = nullptr;  // (each output goes back once, whichever exit asks)
+        }
+        return rc;
+    }
+    int finish(bool device_too = false) {
+        if (copy_back() != SSP_OK || (where != SSP_HOST && !device_too)) return rc;
+        in_flight = false;
+        return rc = Op::wait(ctx);
+    }
+    void waited() { in_flight = false; }  // the caller has waited for the stream by means of its own since copy_back
+
+  private:
+    const Ctx* ctx;
+    const int where;
+    Op op[CAP];
+    void* back_to[CAP];  // the host array of a staged output, else null
+    size_t back_bytes[CAP];
+    int n = 0, rc = SSP_OK;
+    bool in_flight = false;  // device-to-host copies queued and not waited for
+    void* stage(const void* host, size_t bytes, int w, bool load, bool is_out) {
+        if (rc != SSP_OK) return nullptr;
+        if (w == SSP_DEVICE || host == nullptr) return const_cast<void*>(host);
+        if (n == CAP) {
+            set_error("staging scope: more than %d staged operands in one call", CAP);
+            rc = SSP_ERR_UNSUPPORTED;
+            return nullptr;
+        }
+        void* d = load ? const_cast<void*>(op[n].in(ctx, host, bytes, w, &rc)) : op[n].out(ctx, const_cast<void*>(host), bytes, w, &rc);
+        back_to[n] = is_out && rc == SSP_OK ? const_cast<void*>(host) : nullptr;
+        back_bytes[n++] = bytes;
+        return rc == SSP_OK ? d : nullptr;
+    }
+};
+
+#ifndef SSP_STAGING_NO_HIP
+static inline int check_where(int where, const char* fn) {
+    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", fn);
+    return SSP_OK;
+}
+// hipStreamSynchronize on a stream its owner has already destroyed (a borrowed stream at process exit) does not return an error on
+// ROCm 7.2 — it throws std::bad_variant_access out of the C API; nothing may escape a destroy function
+static inline bool sync_quietly(hipStream_t s) {
+    try {
+        return hipStreamSynchronize(s) == hipSuccess;
+    } catch (...) {
+        return false;
+    }
+}
+// Staging of one operand of an SSP_HOST call: device copy of a host input / device scratch for an output (StageScope's primitive).
 struct Staged {
     DevBuf own;  // operands too large for the ctx's pool (or when all its slots are taken)
     const ssp_ctx* pool = nullptr;
@@ -287,17 +368,14 @@ struct Staged {
         SSP_HIP(hipMemcpyAsync(host, p, bytes, hipMemcpyDeviceToHost, ctx->stream));
         return SSP_OK;
     }
-};
-
-// hipStreamSynchronize on a stream its owner has already destroyed (a borrowed stream at process exit) does not return an error on
-// ROCm 7.2 — it throws std::bad_variant_access out of the C API; nothing may escape a destroy function
-static inline bool sync_quietly(hipStream_t s) {
-    try {
-        return hipStreamSynchronize(s) == hipSuccess;
-    } catch (...) {
-        return false;
+    static int wait(const ssp_ctx* ctx) {
+        SSP_HIP(hipStreamSynchronize(ctx->stream));
+        return SSP_OK;
     }
-}
+    static void wait_quietly(const ssp_ctx* ctx) { (void)sync_quietly(ctx->stream); }
+};
+using StageScope = StageScopeT<Staged, ssp_ctx>;
+
 // Waits for the ctx stream and the ring's copy streams.  Throws nothing and sets no error message (false = a wait failed).
 static inline bool drain_pipe(const ssp_ctx* ctx) {
     bool ok = sync_quietly(ctx->stream);
@@ -417,5 +495,6 @@ static inline size_t host_slice_bytes() {
     if (const char* e = getenv("SSP_HOST_SLICE_MB")) mb = (size_t)std::max(1, atoi(e));
     return mb << 20;
 }
+#endif  // SSP_STAGING_NO_HIP
 }  // namespace ssp
 #endif

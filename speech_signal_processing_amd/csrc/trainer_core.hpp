@@ -67,7 +67,7 @@ struct TrainerCore {
     }
 
     int check_data(const char* who, const float* X, const int32_t* labels, int64_t N, int where) const {
-        if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "%s: where", who);
+        SSP_TRY(check_where(where, who));
         if (N < 0) SSP_FAIL(SSP_ERR_INVALID, "%s: N < 0", who);
         if (N > 0 && (!X || !labels)) SSP_FAIL(SSP_ERR_INVALID, "%s: null array", who);
         if (where == SSP_HOST)
@@ -146,12 +146,10 @@ int trainer_run(const char* who, TrainerCore* c, const float* X, int64_t row_flo
     hipStream_t s = ctx->stream;
     const int64_t steps = (N + batch_size - 1) / batch_size;
     SSP_TRY(c->slots(steps));
-    Staged sx, sl;
-    int rc;
-    const float* dX = (const float*)sx.in(ctx, X, (size_t)N * row_floats * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const int32_t* dL = (const int32_t*)sl.in(ctx, labels, (size_t)N * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float* dX = st.in(X, (size_t)N * row_floats * sizeof(float));
+    const int32_t* dL = st.in(labels, (size_t)N * sizeof(int32_t));
+    SSP_TRY(st.status());
     const int64_t* dO = nullptr;
     if (order) {
         SSP_TRY(c->order.reserve((size_t)N * sizeof(int64_t)));

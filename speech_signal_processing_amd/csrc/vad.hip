@@ -363,7 +363,7 @@ int ssp_vad_features(ssp_ctx* ctx, const void* samples, int sample_type, const s
     ssp::TraceRange trace_("ssp_vad_features");
     if (!ctx || !sample_seg || !frame_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_features: null ctx or segments");
     if (sample_type != 0 && sample_type != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_features: sample_type must be 0 (float32) or 1 (int16)");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_features: where");
+    SSP_TRY(check_where(where, "ssp_vad_features"));
     SSP_TRY(vad_check_step("ssp_vad_features", frame_size, step));
     if (flags & ~(uint32_t)SSP_VAD_ZCR_UNGATED) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_features: unknown flag bits %#x", (unsigned)flags);
     if (sample_seg->n != frame_seg->n) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_features: sample and frame segments differ in count");
@@ -414,16 +414,10 @@ int ssp_vad_features(ssp_ctx* ctx, const void* samples, int sample_type, const s
     SSP_HIP(hipStreamSynchronize(s));  // `chunks` (host) dies at return
 
     const size_t in_bytes = (size_t)sample_seg->host.back() * es, out_bytes = (size_t)frame_seg->host.back() * sizeof(float);
-    Staged sin, sz, sp, se;
-    int rc;
-    const void* d_in = sin.in(ctx, samples, in_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_z = (float*)sz.out(ctx, zcr_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_p = (float*)sp.out(ctx, power_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
-    float* d_e = (float*)se.out(ctx, entropy_out, out_bytes, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const void* d_in = st.in(samples, in_bytes);
+    float *d_z = st.out(zcr_out, out_bytes), *d_p = st.out(power_out, out_bytes), *d_e = st.out(entropy_out, out_bytes);
+    SSP_TRY(st.status());
 
     VadArgs a;
     a.samples = d_in;
@@ -466,11 +460,7 @@ int ssp_vad_features(ssp_ctx* ctx, const void* samples, int sample_type, const s
     else hipLaunchKernelGGL(vad_feature_kernel<0>, dim3(grid), dim3(64 * VAD_WAVES), lds, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sz.back(ctx, zcr_out, out_bytes, where));
-    SSP_TRY(sp.back(ctx, power_out, out_bytes, where));
-    SSP_TRY(se.back(ctx, entropy_out, out_bytes, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy, const ssp_segments* frame_seg, int32_t mode, float zcr_gate,
@@ -478,7 +468,7 @@ int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy
     ssp::TraceRange trace_("ssp_vad_detect");
     if (!ctx || !frame_seg) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_detect: null ctx or segments");
     if (mode != 0 && mode != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_detect: mode must be 0 (VAD_detection) or 1 (VAD_frequency)");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_detect: where");
+    SSP_TRY(check_where(where, "ssp_vad_detect"));
     if (mode == 0 && min_len < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_detect: min_len must be >= 1");
     if (kernel_ms) *kernel_ms = 0.f;
     const int64_t n_utt = frame_seg->n;
@@ -488,16 +478,11 @@ int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy
     SSP_TRY(use_ctx(ctx));
     hipStream_t s = ctx->stream;
     const size_t n_all = (size_t)frame_seg->host.back();
-    Staged sz, sp, sm, sn;
-    int rc;
-    const float* d_z = (const float*)sz.in(ctx, mode == 0 ? zcr : nullptr, n_all * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* d_p = (const float*)sp.in(ctx, power_or_entropy, n_all * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    uint8_t* d_m = (uint8_t*)sm.out(ctx, mask_out, n_all, where, &rc);
-    SSP_TRY(rc);
-    int32_t* d_n = (int32_t*)sn.out(ctx, n_speech_out, (size_t)n_utt * sizeof(int32_t), where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float *d_z = st.in(mode == 0 ? zcr : nullptr, n_all * sizeof(float)), *d_p = st.in(power_or_entropy, n_all * sizeof(float));
+    uint8_t* d_m = st.out(mask_out, n_all);
+    int32_t* d_n = st.out(n_speech_out, (size_t)n_utt * sizeof(int32_t));
+    SSP_TRY(st.status());
     uint64_t* gw = nullptr;
     int64_t plane = 0;
     if (mode == 0 && frame_seg->max_len() > (int64_t)64 * VAD_LDS_WORDS) {
@@ -512,10 +497,7 @@ int ssp_vad_detect(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy
                        zcr_gate, ampl, amph, (int)min_len, d_m, d_n, gw, plane);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sm.back(ctx, mask_out, n_all, where));
-    SSP_TRY(sn.back(ctx, n_speech_out, (size_t)n_utt * sizeof(int32_t), where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

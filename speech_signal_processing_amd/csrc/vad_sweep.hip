@@ -140,7 +140,7 @@ int ssp_vad_sweep(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy,
                   int32_t* counts_out, int where, float* kernel_ms) {
     ssp::TraceRange trace_("ssp_vad_sweep");
     if (mode != 0 && mode != 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_sweep: mode must be 0 (VAD_detection) or 1 (VAD_frequency)");
-    if (where != SSP_HOST && where != SSP_DEVICE) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_sweep: where");
+    SSP_TRY(check_where(where, "ssp_vad_sweep"));
     if (n_par < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_sweep: n_par must be >= 1");
     if (min_len < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_sweep: min_len must be >= 1");
     if (!ampl || (mode == 0 && (!zcr_gate || !amph))) SSP_FAIL(SSP_ERR_INVALID, "ssp_vad_sweep: null threshold array");
@@ -184,16 +184,11 @@ int ssp_vad_sweep(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy,
     SSP_HIP(hipStreamSynchronize(s));
 
     const size_t n_all = (size_t)frame_seg->host.back(), n_out = (size_t)n_par * (size_t)n_utt * 3 * sizeof(int32_t);
-    Staged sz, sp, sl, sc;
-    int rc;
-    const float* d_z = (const float*)sz.in(ctx, mode == 0 ? zcr : nullptr, n_all * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const float* d_p = (const float*)sp.in(ctx, power_or_entropy, n_all * sizeof(float), where, &rc);
-    SSP_TRY(rc);
-    const uint8_t* d_l = (const uint8_t*)sl.in(ctx, labels, n_all, where, &rc);
-    SSP_TRY(rc);
-    int32_t* d_c = (int32_t*)sc.out(ctx, counts_out, n_out, where, &rc);
-    SSP_TRY(rc);
+    StageScope st(ctx, where);
+    const float *d_z = st.in(mode == 0 ? zcr : nullptr, n_all * sizeof(float)), *d_p = st.in(power_or_entropy, n_all * sizeof(float));
+    const uint8_t* d_l = st.in(labels, n_all);
+    int32_t* d_c = st.out(counts_out, n_out);
+    SSP_TRY(st.status());
 
     SweepArgs a;
     a.zcr = d_z;
@@ -214,9 +209,7 @@ int ssp_vad_sweep(ssp_ctx* ctx, const float* zcr, const float* power_or_entropy,
     hipLaunchKernelGGL(vad_sweep_kernel, dim3(grid), dim3(64 * W), lds, s, a);
     SSP_HIP(hipGetLastError());
     SSP_TRY(tm.stop(s, kernel_ms));
-    SSP_TRY(sc.back(ctx, counts_out, n_out, where));
-    if (where == SSP_HOST) SSP_HIP(hipStreamSynchronize(s));
-    return SSP_OK;
+    return st.finish();
 }
 
 }  // extern "C"

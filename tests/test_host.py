@@ -375,6 +375,25 @@ def test_staging_pool_under_thread_sanitizer(tmp_path):
     assert "ownership errors 0" in r.stdout
 
 
+def test_stage_scope_under_address_sanitizer(tmp_path):
+    """the staging scope every host-or-device entry point stages its operands through (csrc/staging.hpp, StageScopeT), driven without a
+    HIP runtime by tests/native/stage_scope.cpp (a malloc-backed operand stand-in that logs its copies and waits, on the real slot pool),
+    compiled with -fsanitize=address,undefined and run as a process of its own: inputs go in with their bytes; each output comes back
+    once, in the order of the out calls, with the bytes given to out; null and device operands are neither staged nor copied; a failure
+    sticks (nothing staged or copied after it); an unfinished host scope waits before it releases; every slot is free afterwards; a
+    ninth operand is an error code; copy_back does not wait, finish waits once on host and never on device."""
+    import subprocess
+    exe = str(tmp_path / "stage_scope_asan")
+    src = os.path.join(ROOT, "tests", "native", "stage_scope.cpp")
+    b = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread", src, "-o", exe],
+                       capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    assert "stage_scope: 0 failed checks" in r.stdout
+
+
 def test_flatten_signals_keeps_int16_pcm():
     """api.flatten_signals (what every reference-shaped extractor feeds the device from): a list whose utterances are ALL int16 PCM stays
     int16 (ssp_mfcc_run_i16 widens on the device: half the PCIe bytes, no host pass); anything else becomes float32 as before."""
