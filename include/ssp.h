@@ -219,6 +219,43 @@ int ssp_delta(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, i
 int ssp_cmvn(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, int32_t dim,
              float* out, int where, float* kernel_ms);
 
+/* ---- sliding-window normalisation, feature warping and speech-frame selection (featnorm.hip).  An extension: the reference scales once
+ * per utterance (ssp_cmvn), which suits its 3 s clips; long recordings and sessions whose channel drifts are normalised over a window of
+ * about 3 s, and the non-speech frames are dropped before any statistics are taken.  The counterparts — Kaldi's apply-cmvn-sliding
+ * (center=true), sidekit's cep_sliding_norm and stg, the feature warping of Pelecanos and Sridharan — are recalled, parity unpinned:
+ * none of them is at hand and the reference has no such step.  The float64 restatement in tests/featnorm_oracle.py is the yardstick.
+ *
+ * The window of frame t of an utterance of T frames is centred and slid back inside the utterance: lo = t - window / 2 (integer
+ * division), hi = lo + window; if lo < 0: hi -= lo, lo = 0; if hi > T: lo -= hi - T, hi = T, lo = max(lo, 0).  Every window holds
+ * min(window, T) frames and contains t.  Columns are independent.  NaN entries (the silent frames of a dialect without a log floor) are
+ * left out of the window's statistics and ranks and come out as NaN; n below is the number of non-NaN entries of the column in the window.
+ *   mode 0: y = x - mean over the n entries;  mode 1: y = (x - mean) / deviation about that mean (ddof 0; a deviation below
+ *   10 * 2^-23 becomes 1, ssp_cmvn's rule).  A +-inf inside a window gives the non-finite result float64 arithmetic gives on that
+ *   window alone, and never reaches a frame whose window does not hold it.  The error does not grow with T.
+ *   mode 2 (feature warping): k = 2 #{x_s < x_t} + #{x_s == x_t} over the n entries (the frame itself included, so 1 <= k <= 2n - 1),
+ *   y = phi^-1(k / 2n): (rank - 1/2) / n without ties, the mid-rank with ties; +-inf rank like any value.  The count is exact and
+ *   phi^-1 comes from the table of ssp_featnorm_table: the device adds no error of its own.
+ * feats, out: float[frames x dim] laid out by frame_seg, which need not start at row 0 (rows in front of it are neither read nor
+ * written); 1 <= window <= 1024, 1 <= dim <= 4096, utterances of any length, empty ones anywhere.  out == feats is SSP_ERR_INVALID
+ * and arrays that overlap in any other way are not supported: tiles read their neighbours' rows.  Device pointers at any 4-byte
+ * alignment; the device path returns without a host wait (the first mode-2 call of a ctx with a new window builds and uploads that
+ * window's table; a ctx keeps six).  No atomics: the same bits every call. */
+#define SSP_FEATNORM_TILE 256 /* frames of one utterance a workgroup takes: lengths around its multiples are the kernel's edge cases */
+int ssp_featnorm_sliding(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, int32_t dim, int32_t window, int32_t mode,
+                         float* out, int where, float* kernel_ms);
+/* The rows of feats whose mask byte is non-zero, in order, packed from row 0 of out: utterance u's kept rows follow utterance u - 1's,
+ * rows are copied bit for bit (NaN payloads included), rows of out past the total kept are not written.  mask: uint8[frames], indexed
+ * like the rows of feats, on the side `where` names (any alignment); out: float[(frames of frame_seg) x dim], room for every row; counts_out:
+ * HOST int64[n utterances], the kept rows of each, from which the caller builds the new segment table.  One host wait, for the
+ * counts.  out == feats is SSP_ERR_INVALID, overlapping arrays are not supported.  What Kaldi's select-voiced-frames and sidekit's
+ * label selection do (recalled, parity unpinned). */
+int ssp_select_frames(ssp_ctx* ctx, const float* feats, const ssp_segments* frame_seg, int32_t dim, const uint8_t* mask, float* out,
+                      int64_t* counts_out, int where, float* kernel_ms);
+/* The warping table of a window, built on the host in double (no GPU, no ctx): row n (1 <= n <= window) holds
+ * float(phi^-1(k / 2n)), k = 1 .. 2n - 1, at offset (n - 1)^2; the entry at k = n is exactly 0 and entry k is exactly the negative of
+ * entry 2n - k.  table_out: HOST float[window * window]. */
+int ssp_featnorm_table(int32_t window, float* table_out);
+
 /* ---- PLP back end: replaces sidekit.frontend.features.plp after its power spectrum -> Bark bands -> ln stage (call sites
  * GMM_UBM.py:95, d_vector.py:93, UI/GMM_UBM_GUI.py:93, UI/tmp.py:315-318; that front stage is ssp_mfcc_run with a Bark table and
  * an identity DCT).  logspec: float[F x n_bands] ln critical-band energies laid out by frame_seg (which must start at frame 0);

@@ -41,10 +41,48 @@ def _feature_plan(feature_type, fs, delta_order):
     return api.MfccPlan(api.default_context(), frontend.preset_sidekit(fs=fs, delta_order=delta_order, cmvn=1))
 
 
-def extract_feature(x, y, is_train=False, feature_type='MFCC', fs=16000, delta_order=1):
+_SLIDING_MODES = {'sliding': 1, 'warp': 2}
+
+
+@functools.lru_cache(maxsize=8)
+def _feature_plan_raw(fs, delta_order):
+    return api.MfccPlan(api.default_context(), frontend.preset_sidekit(fs=fs, delta_order=delta_order, cmvn=0))
+
+
+def _extract_sliding(x, fs, delta_order, mode, window):
+    """[c, delta c (, delta delta c)] without the per-utterance scale, normalised over a sliding window on the device: one upload, the
+    MFCC plan and api.featnorm_sliding there, one download."""
+    import torch
+    plan = _feature_plan_raw(fs, delta_order)
+    flat, lens = api.flatten_signals(x)
+    seg = api.Segments.from_lengths(plan.ctx, lens)
+    fseg = plan.frame_segments(seg)
+    if fseg.total == 0:
+        return [np.zeros((0, plan.d_out), dtype=np.float64) for _ in lens]
+    dev = torch.from_numpy(np.ascontiguousarray(flat)).to("cuda:%d" % plan.ctx.device)
+    feats = api.featnorm_sliding(plan.ctx, plan.run(dev, seg, fseg), fseg, window=window, mode=mode)
+    feats = feats.cpu().numpy().astype(np.float64)
+    return [feats[fseg.offsets[i]:fseg.offsets[i + 1]] for i in range(fseg.n)]
+
+
+def extract_feature(x, y, is_train=False, feature_type='MFCC', fs=16000, delta_order=1, norm='utterance', window=300):
     """GMM_UBM.py:72-118.  x: list of 1-D audio arrays, y: list of labels.
     Returns (feature, y) or (train_data, feature, y); every feature is (T_i, 26) float64 = scale([c, delta c]).
-    ``delta_order=2`` appends delta-delta (39-d) — an extension used by the benchmark configs."""
+    ``delta_order=2`` appends delta-delta (39-d) — an extension used by the benchmark configs.
+    ``norm`` (an extension; 'utterance': the reference's per-utterance scale, unchanged): 'sliding' normalises mean and variance over
+    the ``window`` frames around each frame instead, 'warp' warps the features over them (featnorm.cmvn_sliding / feature_warp; MFCC only)."""
+    if norm not in ('utterance', 'sliding', 'warp'):
+        raise ValueError("norm must be 'utterance', 'sliding' or 'warp'")
+    if norm != 'utterance':
+        if feature_type != 'MFCC':
+            raise NotImplementedError("norm=%r is provided for feature_type='MFCC'" % norm)
+        feature = _extract_sliding(x, int(fs), int(delta_order), _SLIDING_MODES[norm], int(window))
+        if not is_train:
+            return feature, y
+        train_data = {}
+        for f, lab in zip(feature, y):
+            train_data[lab] = np.vstack((train_data[lab], f)) if lab in train_data else f
+        return train_data, feature, y
     if feature_type in ('PLP', 'MFCC_PLP'):  # GMM_UBM.py:94-99: plp -> hstack(c, delta c) -> scale; UI/tmp.py:319-324: hstack(mfcc, plp)
         feature = _extract_plp(x, int(fs), int(delta_order), with_mfcc=feature_type == 'MFCC_PLP')
         if not is_train:

@@ -13,6 +13,8 @@ ABI_VERSION = 4
 COMM_ID_BYTES = 128
 VAD_ZCR_UNGATED = 1
 PLDA_NO_CLASS_PATH = 1
+FEATNORM_TILE = 256          # SSP_FEATNORM_TILE: frames of one utterance a workgroup of the sliding-normalisation kernel takes
+FEATNORM_MAX_WINDOW = 1024
 
 
 class SspError(RuntimeError):
@@ -77,6 +79,9 @@ SIGNATURES = {
     "ssp_spectrum_abs": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_float, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_delta": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_cmvn": (C.c_int, [_P, _F32P, _P, C.c_int32, _F32P, C.c_int, _MSP]),
+    "ssp_featnorm_sliding": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
+    "ssp_select_frames": (C.c_int, [_P, _F32P, _P, C.c_int32, _P, _F32P, _I64P, C.c_int, _MSP]),
+    "ssp_featnorm_table": (C.c_int, [C.c_int32, _F32P]),
     "ssp_plp_post": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, _F32P, C.c_int, _MSP]),
     "ssp_plp_features": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_float, _F32P, C.c_int32, C.c_int32, C.c_int32,
                                    _F32P, C.c_int, C.c_int, _MSP]),

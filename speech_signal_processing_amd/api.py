@@ -452,6 +452,59 @@ def cmvn_features(ctx: Context, feats, frame_seg: Segments, timing: bool = False
     return (out, ms.value) if timing else out
 
 
+def featnorm_sliding(ctx: Context, feats, frame_seg: Segments, window: int = 300, mode: int = 1, timing: bool = False):
+    """Sliding-window normalisation of a ragged batch of feature rows (ssp_featnorm_sliding): per column, over the ``window`` frames
+    centred on each frame and slid back inside its utterance, mode 0 subtracts the mean, mode 1 also divides by the deviation, mode 2
+    warps to a standard normal by rank (feature warping).  feats (frames, dim): numpy -> host path, torch cuda -> device path (no host
+    wait).  Returns an array like feats [and kernel milliseconds when timing=True]."""
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2:
+        raise ValueError("feats must be (frames, dim)")
+    if int(keep.shape[0]) < frame_seg.total:
+        raise ValueError("feats has fewer rows than the segment table")
+    out = ctx._empty(tuple(keep.shape), where)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_featnorm_sliding(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), int(window), int(mode), _raw_ptr(out, where),
+                                                 where, C.byref(ms) if timing else None))
+    return (out, ms.value) if timing else out
+
+
+def featnorm_table(window: int) -> np.ndarray:
+    """The warping table of a window (ssp_featnorm_table; host only): float32[window * window], row n at offset (n - 1)^2 holds
+    phi^-1(k / 2n) for k = 1 .. 2n - 1."""
+    if not 1 <= int(window) <= _lib.FEATNORM_MAX_WINDOW:
+        raise ValueError("window must lie in [1, %d]" % _lib.FEATNORM_MAX_WINDOW)
+    out = np.empty(int(window) * int(window), dtype=np.float32)
+    _lib.check(_lib.load().ssp_featnorm_table(int(window), out.ctypes.data))
+    return out
+
+
+def select_frames(ctx: Context, feats, frame_seg: Segments, mask, timing: bool = False):
+    """The rows of feats whose mask entry is non-zero, packed in order (ssp_select_frames): feats (frames, dim) and mask (frames,) are
+    arrays of the same kind (numpy, or torch cuda: the rows stay on the device; one host wait for the counts).  Returns (kept rows,
+    the Segments of the kept rows, kept rows per utterance int64[n]) [and kernel milliseconds when timing=True]."""
+    keep, ptr, where = _as_f32(feats, "feats")
+    mk, mptr, mwhere = _as_u8(mask, "mask")
+    if keep.ndim != 2:
+        raise ValueError("feats must be (frames, dim)")
+    if mwhere != where:
+        raise ValueError("feats and mask must be arrays of the same kind")
+    if int(keep.shape[0]) < frame_seg.total or int(np.prod(mk.shape)) < frame_seg.total:
+        raise ValueError("feats or mask has fewer rows than the segment table")
+    rows = int(frame_seg.offsets[-1] - frame_seg.offsets[0])
+    out = ctx._empty((rows, int(keep.shape[1])), where)
+    counts = np.zeros(frame_seg.n, dtype=np.int64)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_select_frames(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), mptr, _raw_ptr(out, where),
+                                              counts.ctypes.data_as(C.POINTER(C.c_int64)), where, C.byref(ms) if timing else None))
+    del mk
+    kept = out[:int(counts.sum())]
+    seg = Segments.from_lengths(ctx, counts)
+    return (kept, seg, counts, ms.value) if timing else (kept, seg, counts)
+
+
 def plp_post(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_order: int = 13, rasta: bool = True, lift: float = 0.6,
              timing: bool = False):
     """Back end of sidekit's plp on the GPU (ssp_plp_post): (frames, bands) ln critical-band energies -> (frames, plp_order)

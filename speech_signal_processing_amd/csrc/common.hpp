@@ -149,6 +149,8 @@ struct ssp_ctx {
     // the recordings ssp_ahc_cluster cannot keep in LDS; grow-only
     ssp::DevBuf diar_tab, diar_r, diar_ws;
     std::vector<char> diar_host;
+    // sliding normalisation and frame selection (featnorm.hip): warping tables by window and the work buffers, made on first use
+    void* featnorm = nullptr;
     mutable ssp::StagePool stage;  // staging buffers of SSP_HOST calls
     int32_t* pinned_words = nullptr;  // 64 bytes of pinned host memory for small read-backs (precision-auto pilots)
     ssp::HostPipe* pipe = nullptr;  // slots / streams of the sliced host-fed MFCC path (staging.hpp; made on first use)
@@ -181,6 +183,7 @@ int segments_make(ssp_ctx* ctx, const int64_t* offsets, int64_t n, ssp_segments*
 // touching the ctx: it waits for the ctx's stream when the ctx is still alive and does nothing when it is gone (ssp_ctx_destroy
 // has already drained the stream); device buffers are then freed without reference to the ctx.
 void quiesce_ctx(const ssp_ctx* ctx);
+void featnorm_release(ssp_ctx* ctx);  // frees ctx->featnorm (featnorm.hip; ssp_ctx_destroy calls it once the stream has drained)
 
 }  // namespace ssp
 #define SSP_STAGING_PART 2

@@ -185,6 +185,7 @@ int ssp_ctx_destroy(ssp_ctx* ctx) {
     (void)ssp::drain_pipe(ctx);
     (void)ssp_comm_destroy(ctx);
     delete ctx->pipe;
+    ssp::featnorm_release(ctx);
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     for (hipEvent_t& ev : ctx->order_ev)
         if (ev) (void)hipEventDestroy(ev);

@@ -88,6 +88,22 @@ def plp_features_batch(signals, fs=16000, nwin=0.025, shift=0.01, plp_order=13, 
     return feats.cpu().numpy(), fseg
 
 
+def cep_sliding_norm(features, win=301, center=True, reduce=False):
+    """sidekit's cep_sliding_norm by name: mean (``reduce``: and variance) normalisation of a (T, D) array over a window of ``win``
+    frames centred on each frame — featnorm.cmvn_sliding (recalled, parity unpinned).  The causal form (center=False) is not provided."""
+    if not center:
+        raise NotImplementedError("cep_sliding_norm: center=False (the causal window) is not provided")
+    from . import featnorm
+    return featnorm.cmvn_sliding(features, window=int(win), norm_vars=bool(reduce))
+
+
+def stg(features, win=301):
+    """sidekit's stg (short-term gaussianisation) by name: feature warping of a (T, D) array over a window of ``win`` frames —
+    featnorm.feature_warp (recalled, parity unpinned)."""
+    from . import featnorm
+    return featnorm.feature_warp(features, window=int(win))
+
+
 def plp(input_sig, nwin=0.025, fs=16000, plp_order=13, shift=0.01, get_spec=False, get_mspec=False, prefac=0.97, rasta=True):
     """sidekit plp (call sites GMM_UBM.py:95, d_vector.py:93, UI/GMM_UBM_GUI.py:93): [cepstra (T, plp_order), None, None, None].
     (log-energy / spectra, items 1-3 of sidekit's list, are not used by the reference and not computed.)"""
