@@ -419,7 +419,17 @@ int ssp_gmm_last_auto(const ssp_gmm* gmm, int32_t* precision_used, int32_t* pilo
  * Non-finite rows.  When any of the n_frames rows holds a NaN or +-inf entry (a BAD frame, as for ssp_gmm_score), EVERY entry of nk_out,
  * sx_out and sxx_out and loglik_sum_out are NaN, on each kernel family (D <= 47 with K <= 64 or K > 64, D > 47); the call reports no
  * error, and nothing of it stays behind in the ctx's scratch: the next call on clean rows gives the bits it gave before.  A caller that
- * iterates (gmm_train.GaussianMixture.fit) must look before it loops: |NaN - previous bound| < tol never holds. */
+ * iterates (gmm_train.GaussianMixture.fit) must look before it loops: |NaN - previous bound| < tol never holds.
+ * Accuracy (this call, ssp_gmm_em_stats_batch and ssp_gmm_em_stats_shared alike).  The kernels evaluate the EXPANDED quadratic
+ * lp = c + sum_d x_d (mu_d P_d - x_d P_d / 2) in float32 and resp = exp(lp - lse) from it; the sums over the frames are float32 per
+ * workgroup and float64 across them.  The error of a statistic is proportional to the SUM OF THE MAGNITUDES of the terms, not to their
+ * sum: a few float32 roundings of sum_d (|x mu P| + x^2 P / 2) + |c| nats on every exponent, and that many parts of every
+ * responsibility.  On centred features (|mu| / sigma of order 1) that is 1e-6 .. 1e-5 of a mixture's mass.  A common offset of r sigma
+ * in every column makes the terms r^2 larger than their sum: measured 2e-4 relative on nk / sx / sxx at r = 10, 3e-3 at r = 30 and
+ * 2e-2 at r = 100, with 0.07 nat per frame on loglik_sum there (D = 13 .. 39, overlapping mixtures, mixtures holding at least one
+ * frame; profiles/em_accuracy.md).  Centre the features (subtract a global mean) before training on raw cepstra; the library does
+ * not do it for the caller.  tests/em_cases.py holds every kernel to 8 x the error of a plain float32 restatement of this formula, on
+ * and off centre. */
 int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, const double* means, const double* covars,
                      const float* feats, int64_t n_frames, double* nk_out, double* sx_out, double* sxx_out,
                      double* loglik_sum_out, int where, float* kernel_ms);
@@ -432,7 +442,8 @@ int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, 
  * (the messages name the model).  SSP_ERR_UNSUPPORTED: D > 47.
  * Contract.  K <= 64: each model's outputs are BIT-IDENTICAL to ssp_gmm_em_stats on that model's rows (same kernel body, same partition
  * of its frames, same float64 reduction order).  K > 64: fp32 MFMA log-sum-exp per frame and fp32 partial sums reduced in float64, within
- * fp32 rounding of ssp_gmm_em_stats (whose log-sum-exp comes from the scoring kernel) but not bit for bit.
+ * fp32 rounding of ssp_gmm_em_stats (whose per-frame log-sum-exp is the same kernel body's; only the partition of the frames among the
+ * persistent workgroups differs) but not bit for bit.
  * Non-finite rows.  A model whose row range holds a bad frame gets NaN in all of its nk_out, sx_out, sxx_out and loglik_sum_out, as
  * ssp_gmm_em_stats gives.  A model whose range holds none is BIT-IDENTICAL to the same call without the bad entries — whichever other
  * models of the launch are poisoned, overlapping ranges included — and a bad frame in a gap between the ranges, or in the rows of a

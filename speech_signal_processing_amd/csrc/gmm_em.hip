@@ -17,7 +17,8 @@
 // on the device): lp = c + sum_d x_d (A_d + x_d B_d).
 // Batched form (ssp_gmm_em_stats_batch, D <= 47): M models over row ranges of one feature buffer, one launch group per scratch budget:
 //   gmm_em_acc_mfma_seg_kernel  the body of gmm_em_acc_mfma_kernel over a work table of (model, walker) — K <= 64 bit-identical per model
-//   gmm_em_lse_mfma_seg_kernel  K > 64: per-frame log-sum-exp over every 64-mixture chunk of a model (MFMA, online max / sum)
+//   gmm_em_lse_mfma_seg_kernel  K > 64: per-frame log-sum-exp over every 64-mixture chunk of a model (MFMA, online max / sum); the single
+//                               call's unfused path runs the same body as gmm_em_lse_mfma_kernel
 //   gmm_em_reduce_seg_kernel    the body of gmm_em_reduce_kernel per model
 #include <cmath>
 
@@ -28,6 +29,7 @@ namespace ssp {
 constexpr int EM_TF = 64;   // frames per tile
 constexpr int EM_KC = 64;   // mixtures per chunk
 constexpr int EM_DG = 16;   // max dims per accumulation group (4 groups: D <= 64)
+constexpr int EM_WS = 65;   // LDS row stride of the lse kernels' k-major parameter chunk (em_lse_mfma_body)
 
 struct EmArgs {
     const float* x;       // [n x D]
@@ -145,14 +147,6 @@ __global__ __launch_bounds__(256) void gmm_em_acc_kernel(EmArgs a) {
 }
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// sum of lse over 64-frame tiles (one partial per tile, like gmm_em_lse_kernel writes)
-__global__ __launch_bounds__(64) void gmm_em_lsesum_kernel(const float* __restrict__ lse, int64_t n, float* __restrict__ part) {
-    const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    float v = i < n ? lse[i] : 0.f;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
 
 // MFMA form of gmm_em_acc_kernel (D <= 47: at most 3 column tiles of [x, x^2, 1]).  Grid (G, K/64), 4 waves; per 64-frame tile
 //   GEMM1  lp[64 mix x 64 frames] = W[64 x (2D+1)] . aug^T        wave (r, c) owns one 32 x 32 tile; mixtures = MFMA rows, frames =
@@ -435,19 +429,21 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_seg_kernel(EmBatchArgs b)
     em_mfma_body<NCT, FUSE, true>(em_seg_args(b, m), (unsigned)g);
 }
 
-// per-frame log-sum-exp for K > 64 (several 64-mixture chunks): workgroup = one 64-frame tile of one model (work[x] = (model, tile)).
-// Per chunk: GEMM1 as in em_mfma_body (wave (r1, c1): mixtures 32 r1.., frames 32 c1..), then an online (max, sum) per frame over the
-// chunks; the two mixture halves meet in LDS.  Writes lse[t] of the tile's frames and one lse partial per tile.
-__global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b) {
+// per-frame log-sum-exp of the unfused MFMA path (several 64-mixture chunks, or SSP_EM_NO_FUSE): workgroup = one 64-frame tile of one
+// model.  Per chunk: GEMM1 as in em_mfma_body (wave (r1, c1): mixtures 32 r1.., frames 32 c1..) over the SAME parameter image and in the
+// same k order, so that lp - lse in the accumulation kernel is the difference of two evaluations of one formula; then an online
+// (max, sum) per frame over the chunks; the two mixture halves meet in LDS.  Writes lse[t] of the tile's frames and one lse partial per
+// tile.  The body is shared by the single-model kernel (tile = blockIdx.x) and the batched one (work[x] = (model, tile)).
+__device__ __forceinline__ void em_lse_mfma_body(const EmArgs& a, int tile) {
     extern __shared__ float sm[];
-    const int2 w = b.work[blockIdx.x];
-    const int mi = em_uniform(w.x), tile = em_uniform(w.y);
-    const EmArgs a = em_seg_args(b, mi);
     const int D = a.D, W = 2 * D + 1, KS = (W + 1) / 2;
     const int XS = (2 * KS) | 1;
     float* xs = sm;                    // [64 frames][XS]  aug = [x, x^2, 1, 0]
-    float* wsT = xs + EM_TF * XS;      // [2 KS][64 mix]   parameter chunk, k-major
-    float* ex = wsT + 2 * KS * EM_KC;  // [2 mixture halves][64 frames][2]  (max, sum) exchange, then 4 wave sums
+    float* wsT = xs + EM_TF * XS;      // [2 KS][EM_WS]    parameter chunk, k-major, row stride 65: the chunk is read from global memory as
+                                       // it lies (mixture-major, consecutive lanes consecutive addresses) and transposed on the way in
+                                       // — lane to lane the LDS address moves by 65 floats (or by 1), never onto the same bank.  Read
+                                       // k-major from global memory, every lane touched a cache line of its own: 64 lines per load.
+    float* ex = wsT + 2 * KS * EM_WS;  // [2 mixture halves][64 frames][2]  (max, sum) exchange, then 4 wave sums
     const int tid = threadIdx.x, lane = tid & 63, wave = em_uniform(tid >> 6);
     const int fl = lane & 31, h = lane >> 5, r1 = wave >> 1, c1 = wave & 1;
     const int64_t base = (int64_t)tile * EM_TF;
@@ -466,17 +462,38 @@ __global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b)
         }
     }
     const float* xrow = xs + (32 * c1 + fl) * XS;
-    const float* wcol = wsT + h * EM_KC + 32 * r1 + fl;
+    const float* wcol = wsT + h * EM_WS + 32 * r1 + fl;
+    if (tid < EM_KC) wsT[W * EM_WS + tid] = 0.f;  // the zero pad row k = 2 D + 1 of the last k-step: written once, no chunk touches it
+    // element i = tid + 256 j of a chunk [64 mix][W] is (mixture i / W, column i % W): stepped, not divided
+    const int i_q = 256 / W, i_r = 256 - i_q * W, m_first = tid / W, k_first = tid - m_first * W;
+    // the parameter chunk of the NEXT iteration is fetched into registers while this one's MFMAs run, as em_mfma_body fetches its frame
+    // tiles: EM_WP floats per thread cover 64 x (2 D + 1) <= 64 x 95
+    constexpr int EM_WP = 24;
+    float wpre[EM_WP];
+    auto fetchw = [&](int kc) {
+        const float* pc = a.par + (size_t)kc * W;
+#pragma unroll
+        for (int u = 0; u < EM_WP; ++u) {
+            const int i = tid + u * 256;
+            wpre[u] = (kc < a.Kp && i < EM_KC * W) ? pc[i] : 0.f;
+        }
+    };
+    fetchw(0);
     float m = -INFINITY, s = 0.f;  // this lane's frame over the mixtures of half r1 seen so far
     for (int kc = 0; kc < a.Kp; kc += EM_KC) {
         __syncthreads();  // the previous chunk's GEMM1 is done with wsT
-        for (int i0 = 0; i0 < 2 * KS * EM_KC; i0 += 256) {
-            const int i = i0 + tid;
-            if (i < 2 * KS * EM_KC) {
-                const int k = i / EM_KC, mm = i - k * EM_KC;
-                wsT[i] = k < W ? a.par[(size_t)(kc + mm) * W + k] : 0.f;
+        int pm = m_first, pk = k_first;
+#pragma unroll
+        for (int u = 0; u < EM_WP; ++u) {
+            if (tid + u * 256 < EM_KC * W) wsT[pk * EM_WS + pm] = wpre[u];
+            pm += i_q;
+            pk += i_r;
+            if (pk >= W) {
+                pk -= W;
+                ++pm;
             }
         }
+        fetchw(kc + EM_KC);  // the next chunk travels while this one's MFMAs run
         __syncthreads();
         f32x16 acc1;
 #pragma unroll
@@ -486,14 +503,14 @@ __global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b)
             float av[4], bv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                av[u] = wcol[(2 * (s2 + u)) * EM_KC];
+                av[u] = wcol[(2 * (s2 + u)) * EM_WS];
                 bv[u] = xrow[2 * (s2 + u) + h];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc1, 0, 0, 0);
         }
         for (; s2 < KS; ++s2)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * EM_KC], xrow[2 * s2 + h], acc1, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * EM_WS], xrow[2 * s2 + h], acc1, 0, 0, 0);
         float cm = acc1[0];
 #pragma unroll
         for (int i = 1; i < 16; ++i) cm = fmaxf(cm, acc1[i]);
@@ -520,6 +537,14 @@ __global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b)
     if (lane == 0) ex[wave] = v;
     __syncthreads();
     if (tid == 0) a.lse_part[tile] = ex[0] + ex[1];
+}
+
+__global__ __launch_bounds__(256) void gmm_em_lse_mfma_kernel(EmArgs a) { em_lse_mfma_body(a, (int)blockIdx.x); }
+
+__global__ __launch_bounds__(256) void gmm_em_lse_mfma_seg_kernel(EmBatchArgs b) {
+    const int2 w = b.work[blockIdx.x];
+    const int mi = em_uniform(w.x), tile = em_uniform(w.y);
+    em_lse_mfma_body(em_seg_args(b, mi), tile);
 }
 
 // gmm_em_reduce_kernel per model: grid (column blocks, models of the launch group from m0); out[m][cols + 1]
@@ -607,6 +632,7 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     const size_t lds1 = ((size_t)EM_TF * XS + (size_t)EM_KC * W + 512) * sizeof(float);
     const size_t lds2 = ((size_t)EM_TF * XS + (size_t)EM_KC * W + (size_t)EM_TF * 65) * sizeof(float);
     const size_t lds3 = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + (size_t)EM_TF * 65 + 256) * sizeof(float);
+    const size_t lds4 = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_WS + 256) * sizeof(float);
     const bool fuse = mfma && Kp == EM_KC && !getenv("SSP_EM_NO_FUSE");  // K <= 64: log-sum-exp inside the accumulation kernel
     if (lds1 > 64 * 1024)
         SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_em_lse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
@@ -618,18 +644,11 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
                              reinterpret_cast<const void*>(gmm_em_acc_mfma_kernel<2, false>), reinterpret_cast<const void*>(gmm_em_acc_mfma_kernel<3, false>)};
         for (const void* k : ks) SSP_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
     }
-    // the per-frame log-sum-exp of the MFMA path comes from the scoring kernel (csrc/gmm.hip: fp32 MFMA, score_samples of ONE model)
-    ssp_gmm* scorer = nullptr;
-    ssp_segments* seg = nullptr;
-    if (mfma && !fuse) {
-        const int64_t off[2] = {0, n_frames};
-        int rc = ssp_gmm_pack(ctx, 1, K, D, weights, means, covars, 0, &scorer);
-        if (rc == SSP_OK) rc = segments_make(ctx, off, 1, &seg);
-        if (rc != SSP_OK) {
-            ssp_gmm_destroy(scorer);
-            return rc;
-        }
-    }
+    // the per-frame log-sum-exp of the unfused MFMA path comes from gmm_em_lse_mfma_kernel: the image, formula and k order of the
+    // accumulation kernel's own GEMM1 (it once came from the scorer of csrc/gmm.hip, whose log2 image rounds differently: resp =
+    // exp(lp - lse) then carried the DIFFERENCE of two roundings of an exponent of size |lp| — 1 % of a frame's mass at |lp| = 5e4)
+    if (mfma && !fuse && lds4 > 64 * 1024)
+        SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_em_lse_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4));
     Timer tm;
     int rc = tm.start(kernel_ms != nullptr, s);
     if (rc == SSP_OK && fuse) {
@@ -639,14 +658,11 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
             default: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<3, true>), dim3(G, 1), dim3(256), lds3, s, a); break;
         }
     } else if (rc == SSP_OK && mfma) {
-        rc = ssp_gmm_score(scorer, d_x, seg, d_lse.as<float>(), nullptr, nullptr, SSP_DEVICE, 0, nullptr);
-        if (rc == SSP_OK) {
-            hipLaunchKernelGGL(gmm_em_lsesum_kernel, dim3((unsigned)n_tiles), dim3(64), 0, s, d_lse.as<float>(), n_frames, d_lsep.as<float>());
-            switch (nct) {
-                case 1: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<1, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
-                case 2: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<2, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
-                default: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<3, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
-            }
+        hipLaunchKernelGGL(gmm_em_lse_mfma_kernel, dim3((unsigned)n_tiles), dim3(256), lds4, s, a);
+        switch (nct) {
+            case 1: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<1, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
+            case 2: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<2, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
+            default: hipLaunchKernelGGL((gmm_em_acc_mfma_kernel<3, false>), dim3(G, Kp / EM_KC), dim3(256), lds3, s, a); break;
         }
     } else if (rc == SSP_OK) {
         hipLaunchKernelGGL(gmm_em_lse_kernel, dim3((unsigned)n_tiles), dim3(256), lds1, s, a);
@@ -663,15 +679,11 @@ extern "C" int ssp_gmm_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double
     if (rc == SSP_OK) rc = tm.stop(s, kernel_ms);
     if (rc != SSP_OK) {
         (void)hipStreamSynchronize(s);
-        ssp_gmm_destroy(scorer);
-        ssp_segments_destroy(seg);
         return rc;
     }
     std::vector<double> host((size_t)cols + 1);
     hipError_t he = hipMemcpyAsync(host.data(), d_out.p, host.size() * sizeof(double), hipMemcpyDeviceToHost, s);
     if (he == hipSuccess) he = hipStreamSynchronize(s);
-    ssp_gmm_destroy(scorer);
-    ssp_segments_destroy(seg);
     if (he != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "ssp_gmm_em_stats: result copy failed: %s", hipGetErrorString(he));
     for (int k = 0; k < K; ++k) {
         const double* r = host.data() + (size_t)k * W;
@@ -775,7 +787,7 @@ static int em_stats_batch_impl(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, co
     const int2* d_tiles = (const int2*)((char*)d_tab.p + tab_models + tab_work);
     EmBatchArgs b{d_x, d_par.as<float>(), d_lse.as<float>(), d_lsep.as<float>(), d_part.as<float>(), d_models, d_work, D, K, Kp, shared ? (int64_t)0 : (int64_t)Kp * W};
     const size_t lds_acc = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + (size_t)EM_TF * 65 + 256) * sizeof(float);
-    const size_t lds_lse = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_KC + 256) * sizeof(float);
+    const size_t lds_lse = ((size_t)EM_TF * ((W + 1) | 1) + (size_t)(W + 1) * EM_WS + 256) * sizeof(float);
     const void* acc_k = nullptr;
     switch (nct * 2 + (fuse ? 1 : 0)) {
         case 2: acc_k = reinterpret_cast<const void*>(gmm_em_acc_mfma_seg_kernel<1, false>); break;

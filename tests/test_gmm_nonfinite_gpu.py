@@ -344,7 +344,7 @@ def _bits_equal(a, b):
 
 @pytest.mark.parametrize("K,D", [(3, 1), (64, 39), (70, 47), (5, 60)], ids=["K3_D1", "K64_D39", "K70_D47", "K5_D60_valu"])
 def test_em_stats_with_a_bad_frame_are_all_nan_and_leave_nothing_behind(api, K, D):
-    """both MFMA families (fused log-sum-exp for K <= 64, the scoring kernel's for K > 64) and the VALU path (D > 47)"""
+    """both MFMA families (fused log-sum-exp for K <= 64, gmm_em_lse_mfma_kernel's for K > 64) and the VALU path (D > 47)"""
     rng = np.random.default_rng(40 + K)
     n = 64 * 5 + 37
     w, mu, cov = rng.dirichlet(5 * np.ones(K)), rng.standard_normal((K, D)), rng.uniform(0.5, 2.0, (K, D))

@@ -3,12 +3,60 @@ import sys, time, numpy as np
 sys.path.insert(0, '.')
 from speech_signal_processing_amd import api
 from oracle import ref_cpu as O
-# the derived bound of a float32 DTW against float64 (tests/dtw_cases.py band(), restated: this tool imports nothing from tests/;
-# tests/test_dtw_instances_host.py holds the two to each other)
+# the derived bound of a float32 DTW against float64 (tests/dtw_cases.py band(), restated; tests/test_dtw_instances_host.py holds the two
+# to each other)
 dtw_band = lambda r, c, dim, ref: 1.01 * (r + c + (1 if dim == 1 else dim + 3)) * 2.0 ** -24 * abs(ref)
 # the derived bound of one float32 dense layer against float64, per output element (tests/dense_cases.py band_of(), restated for one
 # layer; tests/test_dense_instances_host.py holds that one): d_in accumulations and the bias add, 2^-23 each, on sum |x| |w| + |b|
 dense_band = lambda X, W, b: 1.01 * (W.shape[0] + 1) * 2.0 ** -23 * (np.abs(X.astype(np.float64)) @ np.abs(W.astype(np.float64)) + np.abs(b.astype(np.float64)))
+
+# the one rule of the EM instance suite (tests/em_cases.py compare(), restated: this tool imports nothing from tests/;
+# tests/test_em_instances_host.py holds the two to each other).  Float64 oracle; yardstick: a float32 restatement of the kernels' formula
+# (em_pack's image, one product at a time, float32 log-sum-exp); errors normalised by the sum of the magnitudes a statistic is made of.
+# Returns the largest of the four ratios error / limit: above 1 is a failure.
+# ---- em_rule begin
+def em_rule(w, mu, cov, X, nk, sx, sxx, ll, n_tiles_cap):
+    w, mu, cov = (np.asarray(a, dtype=np.float64) for a in (w, mu, cov))
+    X = np.asarray(X, dtype=np.float32)
+    (K, D), n = mu.shape, len(X)
+    X64 = X.astype(np.float64)
+    lp = O.gmm_log_prob(w, mu, cov, X64)
+    mx = lp.max(axis=1, keepdims=True)
+    lse = (mx + np.log(np.exp(lp - mx).sum(axis=1, keepdims=True)))[:, 0]
+    resp = np.exp(lp - lse[:, None])
+    aug = np.concatenate([X64, X64 * X64, np.ones((n, 1))], axis=1)
+    ref, den = resp.T @ aug, resp.T @ np.abs(aug) + 2.0 ** -100 * np.abs(aug).sum(axis=0)[None, :]
+    P = 1.0 / cov
+    c = np.log(w) - 0.5 * D * np.log(2.0 * np.pi)
+    for d in range(D):
+        c = c + (0.5 * np.log(P[:, d]) - 0.5 * mu[:, d] * mu[:, d] * P[:, d])
+    W = np.zeros(((K + 63) // 64 * 64, 2 * D + 1))   # with the padded mixtures of the image: constant -1e30
+    W[:, 2 * D] = -1.0e30
+    W[:K] = np.concatenate([mu * P, -0.5 * P, c[:, None]], axis=1)
+    W = W.astype(np.float32)
+    a32 = np.concatenate([X, X * X, np.ones((n, 1), np.float32)], axis=1)
+    acc = np.zeros((n, len(W)), dtype=np.float32)
+    for j in range(2 * D + 1):
+        acc = acc + a32[:, j:j + 1] * W[None, :, j]
+    m32 = acc.max(axis=1, keepdims=True)
+    l32 = m32[:, 0] + np.log(np.exp(acc - m32).sum(axis=1, dtype=np.float32))
+    emu = np.exp(acc - l32[:, None]).astype(np.float64)[:, :K].T @ a32.astype(np.float64)
+    rms = lambda v: float(np.sqrt(np.mean(np.square(v)))) if np.size(v) else 0.0
+    e = lambda v: np.abs(v - ref) / den
+    n_tiles = (n + 63) // 64
+    G = min(n_tiles, n_tiles_cap)
+    L = 64 * ((n_tiles + G - 1) // G)
+    got = np.concatenate([sx, sxx, np.asarray(nk)[:, None]], axis=1).astype(np.float64)
+    lim_max = 8.0 * float(e(emu).max()) + 2.0 ** -20 + L * 2.0 ** -24
+    ratios = [float(e(got).max()) / lim_max, abs(float(got[:, -1].sum()) - n) / (n * lim_max)]
+    rows = ref[:, -1] >= 8.0
+    if int(rows.sum()) >= 4:
+        ratios.append(rms(e(got)[rows]) / (3.0 * rms(e(emu)[rows]) + 2.0 ** -22))
+    dl = l32.astype(np.float64) - lse
+    ratios.append(abs(float(ll) - float(lse.sum())) / (8.0 * max(abs(float(dl.sum())), np.sqrt(n) * rms(dl)) + 2.0 ** -22 * float((np.abs(lse) + 1).sum())))
+    return max(ratios)
+# ---- em_rule end
+em_chunks = lambda K: (K + 63) // 64   # the walker cap as csrc/gmm_em.hip takes it: 2 CUs' worth, shared among the chunks when batched
 
 ctx = api.default_context()
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
@@ -18,6 +66,8 @@ n_cases = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 rng_bad = np.random.default_rng([0x6ad, int(sys.argv[1]) if len(sys.argv) > 1 else 0])
 BAD_VALUES = (np.nan, np.inf, -np.inf)
 verbose = '-v' in sys.argv
+import torch
+ctx_num_cu = torch.cuda.get_device_properties(0).multi_processor_count   # the walker cap of the EM kernels
 t_start = time.time()
 for case in range(n_cases):
     # ---- GMM scoring
@@ -132,6 +182,21 @@ for case in range(n_cases):
     assert np.allclose(st["nk"], nk, rtol=2e-4, atol=2e-4 * max(1.0, nk.max())), (case, "em nk")
     assert np.allclose(st["sx"], sx, rtol=2e-4, atol=2e-4 * max(1.0, np.abs(sx).max())), (case, "em sx")
     assert np.allclose(st["sxx"], sxx, rtol=2e-4, atol=2e-4 * max(1.0, np.abs(sxx).max())), (case, "em sxx")
+    # ---- EM statistics under the instance suite's rule: own shapes, every model its own draw, the single call and (D <= 47) the batched one
+    Kr, Dr, nr = int(rng.choice([1, 5, 33, 64, 65, 129, 300])), int(rng.choice([1, 3, 13, 16, 31, 39, 47, 48, 64])), int(rng.choice([1, 64, 65, 209, 1000, 40000]))
+    if verbose:
+        print(case, "em rule", Kr, Dr, nr, flush=True)
+    wr = rng.dirichlet(5 * np.ones(Kr)); cvr = rng.uniform(0.5, 2.0, (Kr, Dr)); mur = rng.standard_normal((Kr, Dr))
+    Xr = (mur[rng.choice(Kr, nr, p=wr)] + rng.standard_normal((nr, Dr))).astype(np.float32)
+    st = api.gmm_em_stats(ctx, wr, mur, cvr, Xr)
+    ratio = em_rule(wr, mur, cvr, Xr, st["nk"], st["sx"], st["sxx"], st["loglik_sum"], 2 * ctx_num_cu)
+    assert ratio <= 1.0, (case, "em rule single", Kr, Dr, nr, ratio)
+    if Dr <= 47:
+        Xp = np.concatenate([np.full((5, Dr), 50.0, np.float32), Xr])
+        sb = api.gmm_em_stats_batch(ctx, wr[None], mur[None], cvr[None], Xp, [5], [nr])
+        cap = 2 * ctx_num_cu if em_chunks(Kr) == 1 else max(1, 2 * ctx_num_cu // em_chunks(Kr))
+        ratio = em_rule(wr, mur, cvr, Xr, sb["nk"][0], sb["sx"][0], sb["sxx"][0], sb["loglik_sum"][0], cap)
+        assert ratio <= 1.0, (case, "em rule batch", Kr, Dr, nr, ratio)
     # ---- DTW
     dim = int(rng.choice([1, 1, 2, 13]))
     ql = [int(x) for x in rng.choice([1, 2, 63, 64, 65, 200, 700], int(rng.integers(1, 4)))]
