@@ -712,6 +712,63 @@ int ssp_ahc_cluster(ssp_ctx* ctx, const float* scores, const ssp_segments* seg, 
                     const int32_t* n_speakers, int32_t* labels_out, int32_t* n_clusters_out, int32_t* merge_pair_out,
                     float* merge_score_out, int where, float* kernel_ms);
 
+/* ---- VB-HMM resegmentation of diarization labels (VBx, Landini et al. 2022: "Bayesian HMM clustering of x-vector sequences"), for a batch
+ *      of recordings: the second pass behind AHC.  It re-assigns windows that greedy merging misplaced, smooths the label sequence in time
+ *      and lets superfluous clusters die out.  An EXTENSION and UNPINNED: the yardstick is a float64 restatement (tests/vbhmm_oracle.py),
+ *      corroborated by brute-force enumeration and the dense linear-Gaussian formulas.  Added to ABI 4 without a version step. ----
+ * Model, per recording.  X (T x q): the projected vectors of the recording's windows in time order (plda.Plda.project: within-speaker
+ *   covariance I, between-speaker covariance diag(phi)); phi HOST float[q], >= 0; rho = X sqrt(phi).  S HMM states, 1 <= S <= 64;
+ *   recording r uses S_r = clamp(n_init[r], 1, S) live states (S_r = S if n_init is NULL); states >= S_r are inert: pi = gamma = 0
+ *   throughout, they add 0 to every sum.
+ *   Start: pi_s = 1 / S_r; row t of gamma is the softmax over the live states of init_smoothing * onehot(init_labels[t]); a label
+ *   outside [0, S_r) gives the uniform row.
+ *   Iteration i = 0, 1, ...:
+ *     1. N_s = sum_t gamma_ts                               2. invL_sd = 1 / (1 + (Fa/Fb) N_s phi_d)
+ *     3. alpha_sd = (Fa/Fb) invL_sd sum_t gamma_ts rho_td   4. G_t = -1/2 (sum_d x_td^2 + q ln 2 pi)
+ *     5. ll_ts = Fa (sum_d rho_td alpha_sd - 1/2 sum_d (invL_sd + alpha_sd^2) phi_d + G_t)
+ *     6. forward-backward with initial probabilities pi and transitions tr[i][j] = P delta_ij + (1 - P) pi_j (P = loop_prob): the new
+ *        gamma (every row sums to 1) and ln p(X)
+ *     7. ELBO_i = ln p(X) + 1/2 Fb sum_{s,d} (ln invL_sd - invL_sd - alpha_sd^2 + 1)
+ *     8. pi_s proportional to gamma_0s + sum_{t>=1} xi_t(any -> s by the non-loop branch)
+ *          = gamma_0s + (1 - P) pi_s sum_{t>=1} exp(lse_i lfw[t-1][i] + ll_ts + lbw[t][s] - ln p(X)), normalised to sum 1
+ *     9. stop after this iteration if i > 0 and ELBO_i - ELBO_{i-1} < epsilon, or if i = max_iters - 1.
+ *   The gamma and pi of the last iteration run are the result.
+ * Outputs, per recording.  states_out int32[offsets[R]] (nullable): arg max_s gamma_ts, ties to the lowest s.  labels_out
+ *   int32[offsets[R]]: the rank of that state among the states that win at least one row, ordered by the smallest row they win (AHC's
+ *   label convention).  n_speakers_out int32[R]: the number of such states.  n_iters_out int32[R]: iterations run.  elbo_out
+ *   double[R x max_iters] (nullable): NaN beyond n_iters.  gamma_out float[offsets[R] x S], pi_out float[R x S], loglik_out
+ *   float[offsets[R] x S]: ll of the last iteration (each nullable).  Inert columns of gamma and pi are 0; inert columns of loglik are
+ *   UNSPECIFIED.  A recording without rows writes nothing.  init_labels int32[offsets[R]] and n_init int32[R] sit on the side `where`
+ *   names and are read on the device only: ssp_ahc_cluster's labels_out and n_clusters_out feed the call with no read-back.
+ *   A recording with a non-finite entry in X gets labels and states -1, n_speakers -1, n_iters 0 and NaN in gamma, pi, loglik and elbo;
+ *   every other recording keeps the bits it has without that recording.  R == 0 or T == 0 is a no-op.  No float atomics: same call, same
+ *   bits; a recording alone gives the bits it has in a batch (they depend on its T, q, S and numbers only).
+ * Kernel.  A row pre-pass (one wave per row) gives G_t, float64 inside, NaN for a row with a non-finite entry.  Then one 256-thread
+ *   workgroup per recording, longest first, runs the whole iteration loop: one launch per residency form and call, no host round trip
+ *   per iteration, no communication between workgroups, no spin or claim loops; every loop has a trip count known on entry.  S is padded
+ *   to SP = 16, 32 or 64 columns (template instances).  The two products of an iteration run on v_mfma_f32_16x16x4_f32 with ONE ascending
+ *   k-ordered chain per output: gamma^T rho with a wave per 64 columns of q (k = t), rho alpha^T with a wave per 16 rows (k = d); rho is
+ *   formed from X as it is loaded and never stored.  Forward-backward is the O(T S) structured recursion in the per-step-normalised
+ *   linear domain, states on the lanes of one wave: forward a_t = b_t o (P a-hat_{t-1} + (1 - P) pi) with b_ts = exp(ll_ts - max ll_t.),
+ *   backward beta_t = P y + (1 - P) sum_j pi_j y_j with y = b_{t+1} o beta-hat_{t+1}, gamma_t proportional to a-hat_t o beta-hat_t, the
+ *   pi update from the same scaled quantities; ln p(X) = sum_t (ln c_t + max ll_t.), the ELBO and the stop decision are float64.  The
+ *   backward pass runs BEHIND the forward pass on the same wave, not beside it: that takes two T x SP buffers, not three.
+ *   Residency.  alpha (SP x (q | 1) floats) sits in LDS when it takes at most SSP_VBHMM_ALPHA_LDS_BYTES, else in the ctx's grow-only
+ *   workspace; the two T x SP float buffers (ll; a-hat, then gamma) sit in LDS when alpha's LDS share plus 8 T SP bytes is at most
+ *   SSP_VBHMM_LDS_BYTES, else in the workspace.
+ *   SSP_ERR_INVALID before any GPU work: q < 1, S < 1, max_iters < 1; loop_prob outside [0, 1); Fa or Fb not finite and > 0;
+ *   init_smoothing not finite and >= 0; epsilon NaN (+-inf are allowed: -inf never stops early); phi non-finite or negative.
+ *   SSP_ERR_UNSUPPORTED: S > 64, q > 1024, max_iters > 100, a recording with more than 4096 rows.
+ *   Contracts as ssp_ahc_cluster: device pointers at any 4-byte alignment; with SSP_DEVICE the call is stream-ordered on the ctx's stream
+ *   and never waits on the host (once the ctx's tables and workspace have grown to the batch); SSP_HOST goes through the staging scope and
+ *   waits for the results.  An error leaves the ctx usable.  kernel_ms: device time of the kernels (asking for it waits). */
+#define SSP_VBHMM_LDS_BYTES 155648
+#define SSP_VBHMM_ALPHA_LDS_BYTES 65536
+int ssp_vbhmm_resegment(ssp_ctx* ctx, const float* X, const ssp_segments* seg, int32_t q, const float* phi, const int32_t* init_labels,
+                        const int32_t* n_init, int32_t S, float loop_prob, float Fa, float Fb, float init_smoothing, int32_t max_iters,
+                        double epsilon, int32_t* labels_out, int32_t* states_out, int32_t* n_speakers_out, int32_t* n_iters_out,
+                        double* elbo_out, float* gamma_out, float* pi_out, float* loglik_out, int where, float* kernel_ms);
+
 /* k-means++ seeding for the k-means start of the same fits (GMM_UBM.py:158-170: GaussianMixture(init_params='kmeans'), sklearn's default;
  * sklearn cluster/_kmeans.py:kmeans_plusplus), for P seeding PROBLEMS (one per model and start) in ONE launch, one workgroup each, with
  * the random numbers handed in.  feats: float[n_rows x D] on the side `where` names (any 4-byte alignment).  Problem p has n_sel[p] rows:

@@ -15,6 +15,8 @@ VAD_ZCR_UNGATED = 1
 PLDA_NO_CLASS_PATH = 1
 FEATNORM_TILE = 256          # SSP_FEATNORM_TILE: frames of one utterance a workgroup of the sliding-normalisation kernel takes
 FEATNORM_MAX_WINDOW = 1024
+VBHMM_LDS_BYTES = 155648         # SSP_VBHMM_LDS_BYTES: LDS a workgroup of the VB-HMM kernel has for alpha and its two T x SP buffers
+VBHMM_ALPHA_LDS_BYTES = 65536    # SSP_VBHMM_ALPHA_LDS_BYTES: alpha sits in LDS up to this many bytes
 
 
 class SspError(RuntimeError):
@@ -119,6 +121,8 @@ SIGNATURES = {
     "ssp_pairwise_size": (C.c_int, [_P, _I64P]),
     "ssp_pairwise_scores": (C.c_int, [_P, _F32P, _P, C.c_int32, _P, _P, C.c_float, _F32P, C.c_int, _MSP]),
     "ssp_ahc_cluster": (C.c_int, [_P, _F32P, _P, C.c_int32, C.c_float, C.c_int32, _P, _P, _P, _P, _F32P, C.c_int, _MSP]),
+    "ssp_vbhmm_resegment": (C.c_int, [_P, _F32P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
+                                      C.c_double, _P, _P, _P, _P, _P, _F32P, _F32P, _F32P, C.c_int, _MSP]),
     "ssp_kmeanspp_seed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F32P, C.c_int64, C.c_int, _P, _P, _P, _P, _P, _P, _P, _MSP]),
     "ssp_dense_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_dnn_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(_P)]),

@@ -1511,6 +1511,102 @@ def ahc_cluster(ctx: Context, scores, seg_or_counts, linkage: str = "average", t
     return res
 
 
+VBHMM_MAX_STATES = 64     # most HMM states of ssp_vbhmm_resegment (include/ssp.h); its q, rows and iterations: 1024, 4096, 100
+VBHMM_MAX_ITERS = 100
+VBHMM_LDS_BYTES = _lib.VBHMM_LDS_BYTES              # LDS a workgroup has for alpha and its two T x SP buffers
+VBHMM_ALPHA_LDS_BYTES = _lib.VBHMM_ALPHA_LDS_BYTES  # alpha (SP x (q | 1) floats) sits in LDS up to this many bytes, else in the workspace
+VBHMM_WANT = ("gamma", "pi", "elbo", "loglik")
+
+
+def vbhmm_padded_states(n_states: int) -> int:
+    """SP: the columns the kernel pads n_states to (its three template instances)"""
+    return 16 if n_states <= 16 else (32 if n_states <= 32 else 64)
+
+
+def vbhmm_alpha_in_lds(n_states: int, q: int) -> bool:
+    return vbhmm_padded_states(n_states) * (int(q) | 1) * 4 <= VBHMM_ALPHA_LDS_BYTES
+
+
+def vbhmm_n_lds(n_states: int, q: int) -> int:
+    """the residency border of ssp_vbhmm_resegment: recordings of up to this many rows keep their two T x SP buffers in LDS (beside
+    alpha, where that sits in LDS), longer ones in the context's workspace"""
+    a = vbhmm_padded_states(n_states) * (int(q) | 1) * 4
+    return (VBHMM_LDS_BYTES - (a if a <= VBHMM_ALPHA_LDS_BYTES else 0)) // (8 * vbhmm_padded_states(n_states))
+
+
+def vb_resegment(ctx: Context, X, seg_or_counts, phi, init_labels, n_init=None, n_states=None, loop_prob: float = 0.99, Fa: float = 0.3,
+                 Fb: float = 17.0, init_smoothing: float = 5.0, max_iters: int = 10, epsilon: float = 1e-4, want=("gamma", "pi", "elbo"),
+                 out=None, timing: bool = False) -> dict:
+    """VB-HMM resegmentation of every recording of a batch, one workgroup per recording (ssp_vbhmm_resegment; include/ssp.h has the
+    model).  X (total, q) numpy or torch CUDA tensor: the PROJECTED vectors (plda.Plda.project) in time order; phi: host vector of q
+    entries (plda.Plda.psi_); init_labels (total,) and n_init (R,) or None, int32 of X's kind: what ahc_cluster returns as "labels" and
+    "n_clusters" feeds it on the device with no read-back.  n_states: HMM states, default 64 for device inputs (no read-back) and
+    max(init_labels) + 1 clamped to [1, 64] for host inputs.  Returns "labels", "states" (total,) int32, "n_speakers", "n_iters" (R,)
+    int32 — -1 / -1 / -1 / 0 for a recording with a non-finite entry — and what ``want`` names of "gamma" (total, S) float32, "pi"
+    (R, S) float32, "elbo" (R, max_iters) float64 (NaN beyond n_iters) and "loglik" (total, S) float32 (inert columns unspecified).
+    out: a dict of arrays of X's kind to write into, by those names.  A device call given a Segments object returns without a host wait."""
+    keep, ptr, where = _as_f32(X, "X")
+    if keep.ndim != 2:
+        raise ValueError("X must be (total, q)")
+    seg = _as_recordings(ctx, seg_or_counts)
+    q, total = int(keep.shape[1]), seg.total
+    if int(keep.shape[0]) != total:
+        raise ValueError("X has %d rows, the recordings %d" % (int(keep.shape[0]), total))
+    for w in want:
+        if w not in VBHMM_WANT:
+            raise ValueError("want: %r is not one of %s" % (w, VBHMM_WANT))
+    ph = np.ascontiguousarray(phi.cpu().numpy() if _is_torch(phi) else phi, dtype=np.float32).reshape(-1)
+    if ph.shape[0] != q:
+        raise ValueError("phi must have %d entries" % q)
+
+    def ints(x, name, n):
+        if where == _lib.DEVICE:
+            import torch
+            if not (_is_torch(x) and x.is_cuda):
+                raise ValueError("%s must be a torch CUDA tensor, as X is" % name)
+            x = x.to(torch.int32).contiguous().reshape(-1)
+        else:
+            x = np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x, dtype=np.int32).reshape(-1)
+        if int(x.shape[0]) != n:
+            raise ValueError("%s must have %d entries" % (name, n))
+        return x
+    lab0 = ints(init_labels, "init_labels", total)
+    ni = None if n_init is None else ints(n_init, "n_init", seg.n)
+    if n_states is None:
+        n_states = VBHMM_MAX_STATES if where == _lib.DEVICE else int(min(VBHMM_MAX_STATES, max(1, (int(lab0.max()) + 1) if total else 1)))
+    S, mi = int(n_states), int(max_iters)
+    shapes = {"labels": ((total,), "int32"), "states": ((total,), "int32"), "n_speakers": ((seg.n,), "int32"), "n_iters": ((seg.n,), "int32"),
+              "elbo": ((seg.n, mi), "float64"), "gamma": ((total, S), "float32"), "pi": ((seg.n, S), "float32"), "loglik": ((total, S), "float32")}
+    res = {}
+    for name in ("labels", "states", "n_speakers", "n_iters") + tuple(w for w in VBHMM_WANT if w in want):
+        shape, dt = shapes[name]
+        if out is not None and name in out:
+            o = out[name]
+            ok = (_is_torch(o) and where == _lib.DEVICE and o.is_cuda and str(o.dtype) == "torch." + dt and o.is_contiguous()) or (
+                isinstance(o, np.ndarray) and where == _lib.HOST and o.dtype == np.dtype(dt) and o.flags.c_contiguous)
+            if not ok or tuple(int(v) for v in o.shape) != tuple(shape):
+                raise ValueError("out[%r] must be a contiguous %s array of X's kind and shape %s" % (name, dt, tuple(shape)))
+            res[name] = o
+        else:
+            res[name] = ctx._empty(shape, where, dt)
+            if name in ("n_speakers", "n_iters", "pi", "elbo"):
+                res[name][...] = 0   # (a recording without rows is not written)
+    ms = C.c_float(0.0)
+
+    def p(name):
+        return None if name not in res else _raw_ptr(res[name], where)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_vbhmm_resegment(ctx._h, ptr, seg._h, q, ph.ctypes.data, _raw_ptr(lab0, where),
+                                                None if ni is None else _raw_ptr(ni, where), S, float(loop_prob), float(Fa), float(Fb),
+                                                float(init_smoothing), mi, float(epsilon), p("labels"), p("states"), p("n_speakers"),
+                                                p("n_iters"), p("elbo"), p("gamma"), p("pi"), p("loglik"), where,
+                                                C.byref(ms) if timing else None))
+    del keep, lab0, ni
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
 def centroids(ctx: Context, X, labels, num: int):
     """avg[s] = mean(X[labels == s]) (float64 accumulator, row order) — d_vector.py:310-313."""
     keep, ptr, where = _as_f32(X, "X")

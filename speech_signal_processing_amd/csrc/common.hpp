@@ -145,8 +145,8 @@ struct ssp_ctx {
     // input projection of the GRU layer that is running (gru.hip): grow-only, shared by the layers of a network, which run one after
     // the other on the ctx stream
     ssp::DevBuf gru_proj;
-    // diarization (diarize.hip): the per-call tables and their host image, the row terms of ssp_pairwise_scores, and the working copies of
-    // the recordings ssp_ahc_cluster cannot keep in LDS; grow-only
+    // diarization (diarize.hip, vbhmm.hip): the per-call tables and their host image, the row terms of ssp_pairwise_scores / ssp_vbhmm_resegment,
+    // and what ssp_ahc_cluster and ssp_vbhmm_resegment cannot keep in LDS of their recordings; grow-only, one call at a time on the ctx's stream
     ssp::DevBuf diar_tab, diar_r, diar_ws;
     std::vector<char> diar_host;
     // sliding normalisation and frame selection (featnorm.hip): warping tables by window and the work buffers, made on first use

@@ -18,7 +18,7 @@ namespace ssp {
 //  ThreadSanitizer with a malloc-backed buffer, without a HIP runtime)
 template <class Buf>
 struct StagePoolT {
-    static constexpr int SLOTS = 8;
+    static constexpr int SLOTS = 12;
     static constexpr size_t KEEP_MAX = (size_t)64 << 20;
     Buf slot[SLOTS];
     bool busy[SLOTS] = {};
@@ -248,7 +248,7 @@ namespace ssp {
 //  Op: in / out / back as Staged below, static int wait(ctx) — sets the error message — and static void wait_quietly(ctx))
 template <class Op, class Ctx>
 struct StageScopeT {
-    static constexpr int CAP = 8;  // ssp_snorm_apply's need, the largest; = StagePoolT::SLOTS
+    static constexpr int CAP = 12;  // ssp_vbhmm_resegment's need (three inputs, eight outputs), the largest; = StagePoolT::SLOTS
     StageScopeT(const Ctx* c, int w) : ctx(c), where(w) {}
     ~StageScopeT() {
         if (in_flight) Op::wait_quietly(ctx);

@@ -8,6 +8,9 @@ the reference has no diarization; tests/diarize_oracle.py restates the two kerne
     labels, n_clusters = d.cluster(embeddings, counts)                 # embeddings (total, q), counts: windows per recording
     frames = d.run(signals, embed, win=24000, hop=12000)               # per signal: one label per VAD frame, -1 = no speech
 
+    d = diarize.Diarizer(plda_model, threshold=0.0, resegment=True)    # pair scores -> AHC -> VB-HMM resegmentation, all on the device
+
+``VbHmm`` is the resegmentation pass on its own (api.vb_resegment: a Bayesian HMM over the projected vectors, started from the AHC labels).
 ``windows`` and ``frame_labels`` are host helpers; ``metrics.diarization_error`` scores the frame labels against a reference."""
 from __future__ import annotations
 
@@ -60,18 +63,51 @@ def frame_labels(wins, labels, n_frames, frame_hop):
     return out
 
 
+class VbHmm:
+    """VB-HMM resegmentation (VBx) of diarization labels: ``phi_or_plda`` is the between-speaker variance of the projected space — a
+    vector of q entries, or a fitted plda.Plda, whose ``psi_`` it is and whose ``project`` then maps raw embeddings into that space.  The
+    parameters are api.vb_resegment's; n_states None: 64 for device inputs, max(label) + 1 for host inputs."""
+
+    def __init__(self, phi_or_plda, loop_prob=0.99, Fa=0.3, Fb=17.0, init_smoothing=5.0, max_iters=10, epsilon=1e-4, n_states=None,
+                 ctx=None):
+        self.plda = phi_or_plda if hasattr(phi_or_plda, "psi_") else None
+        phi = self.plda.psi_ if self.plda is not None else phi_or_plda
+        self.phi = np.ascontiguousarray(phi.cpu().numpy() if _is_torch(phi) else phi, dtype=np.float32).reshape(-1)
+        if self.phi.size < 1 or not np.isfinite(self.phi).all() or (self.phi < 0).any():
+            raise ValueError("phi must be a vector of finite, non-negative entries")
+        self.params = dict(loop_prob=float(loop_prob), Fa=float(Fa), Fb=float(Fb), init_smoothing=float(init_smoothing),
+                           max_iters=int(max_iters), epsilon=float(epsilon))
+        self.n_states, self.ctx = n_states, ctx
+
+    def resegment(self, projected, counts, labels, n_init=None, want=()):
+        """projected (total, q): the PROJECTED vectors in time order, numpy or torch CUDA tensor; counts: windows per recording (or an
+        api.Segments); labels (total,), n_init (R,) or None: the initial labels and cluster counts, of projected's kind.  -> the dict
+        of api.vb_resegment ("labels", "states", "n_speakers", "n_iters" and what ``want`` names)"""
+        self.ctx = self.ctx or api.default_context()
+        return api.vb_resegment(self.ctx, projected, counts, self.phi, labels, n_init, n_states=self.n_states, want=want, **self.params)
+
+
 class Diarizer:
     """backend: "cosine" (rows are L2-normalised, the score is their cosine) or a fitted plda.Plda (rows are projected, the score is the
     log-likelihood ratio of the pair); linkage "average" / "complete" / "single"; merging stops below ``threshold`` or at
-    ``min_clusters`` clusters."""
+    ``min_clusters`` clusters.  resegment: None, or a VbHmm (True: VbHmm(backend)) that runs on the AHC labels; with it ``cluster``
+    returns the VB-HMM labels and speaker counts.  It needs the projected space of a PLDA back end; with the cosine back end True
+    raises ValueError (there is no phi) and a VbHmm built from an explicit phi takes the rows as they are given."""
 
-    def __init__(self, backend="cosine", linkage="average", threshold=0.0, min_clusters=1, ctx=None):
+    def __init__(self, backend="cosine", linkage="average", threshold=0.0, min_clusters=1, ctx=None, resegment=None):
         if backend != "cosine" and not hasattr(backend, "pairwise_coeffs"):
             raise ValueError('backend must be "cosine" or a fitted plda.Plda')
         if linkage not in api.AHC_LINKAGES:
             raise ValueError("linkage must be one of %s" % sorted(api.AHC_LINKAGES))
         self.backend, self.linkage, self.threshold, self.min_clusters = backend, linkage, float(threshold), int(min_clusters)
         self.ctx = ctx
+        if resegment is True:
+            if backend == "cosine":
+                raise ValueError("resegment=True needs a PLDA back end: the cosine back end has no between-speaker variance (pass a VbHmm built from phi)")
+            resegment = VbHmm(backend)
+        if resegment is not None and resegment is not False and not isinstance(resegment, VbHmm):
+            raise ValueError("resegment must be None, True or a VbHmm")
+        self.resegment = resegment or None
 
     def scores(self, embeddings, counts):
         """-> (packed score blocks, the api.Segments of the recordings)"""
@@ -85,10 +121,26 @@ class Diarizer:
     def cluster(self, embeddings, counts, n_speakers=None):
         """embeddings (total, q) numpy or torch CUDA tensor, counts: windows per recording (or an api.Segments).  -> (labels (total,)
         int32, n_clusters (R,) int32) of embeddings' kind"""
-        s, seg = self.scores(embeddings, counts)
+        if self.resegment is None:
+            s, seg = self.scores(embeddings, counts)
+            r = api.ahc_cluster(self.ctx, s, seg, linkage=self.linkage, threshold=self.threshold, min_clusters=self.min_clusters,
+                                n_speakers=n_speakers)
+            return r["labels"], r["n_clusters"]
+        # pair scores, AHC and the VB-HMM on the same rows: projected once, the AHC outputs stay where they are
+        self.ctx = self.ctx or api.default_context()
+        seg = api._as_recordings(self.ctx, counts)
+        if self.backend == "cosine":
+            rows = embeddings
+            s = api.pairwise_scores(self.ctx, api.l2_normalize(self.ctx, embeddings), seg)
+        else:
+            rows = self.backend.project(embeddings)
+            g, h, c0 = self.backend.pairwise_coeffs()
+            s = api.pairwise_scores(self.ctx, rows, seg, g=g, h=h, c0=c0)
         r = api.ahc_cluster(self.ctx, s, seg, linkage=self.linkage, threshold=self.threshold, min_clusters=self.min_clusters,
                             n_speakers=n_speakers)
-        return r["labels"], r["n_clusters"]
+        self.resegment.ctx = self.resegment.ctx or self.ctx
+        v = self.resegment.resegment(rows, seg, r["labels"], r["n_clusters"])
+        return v["labels"], v["n_speakers"]
 
     def run(self, signals, embed, win, hop, min_len=None, n_speakers=None, **vad):
         """signals: a list of raw signals (int16 PCM or float arrays); embed: a callable that takes the list of window chunks (1-D arrays)
