@@ -64,6 +64,7 @@ typedef struct ssp_plda ssp_plda;         /* enrolled speakers of a diagonalised
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
 typedef struct ssp_lstm ssp_lstm;         /* one LSTM layer packed for the recurrent MFMA forward pass */
 typedef struct ssp_gru ssp_gru;           /* one GRU layer packed for the per-step MFMA forward pass */
+typedef struct ssp_xvector ssp_xvector; /* an x-vector network (frame layers, pooling, segment layers) with its workspace */
 typedef struct ssp_dnn_trainer ssp_dnn_trainer; /* a fully connected network with its gradients and Adam state, for training */
 
 /* MFCC dialect knobs.  Three presets are built by the host side:
@@ -923,6 +924,83 @@ int ssp_conv2d_same_forward(ssp_ctx* ctx, const float* X, int64_t N, int32_t T, 
 /* K.l2_normalize(x, axis=1) (d_vector.py:243-246): Y = X / sqrt(max(sum_k X_k^2, eps)) per row (Keras' eps: 1e-12; an all-zero row stays
  * zero).  X, Y: float[N x d]; Y may be X. */
 int ssp_l2_normalize(ssp_ctx* ctx, const float* X, int64_t N, int32_t d, float eps, float* Y, int where, float* kernel_ms);
+
+/* ---- x-vector extractor forward (since without a version step, like the LSTM and GRU entries): the time-delay network of Snyder et
+ *      al. 2018 ("X-vectors: robust DNN embeddings for speaker recognition") — frame layers, statistics pooling, segment layers — that
+ *      Kaldi's nnet3 recipes, VBx, SpeechBrain and wespeaker put between the features and the back ends above (ssp_plda_*, ssp_snorm_*,
+ *      ssp_pairwise_scores / ssp_ahc_cluster, ssp_vbhmm_resegment).  An EXTENSION and UNPINNED: the reference has no TDNN and none of
+ *      those toolkits or their models is at hand; the forms below are recalled from them, tests/xvector_oracle.py restates them in
+ *      float64 and tests/test_xvector_host.py corroborates the restatement against torch.nn.functional.conv1d in float64.  Inference only.
+ *        Frame layer    T rows of width d_in -> T - (taps - 1) dil rows of width units ("valid": no padding, the sequence shrinks):
+ *                         z[t][u] = b[u] + sum_{j < taps} sum_{c < d_in} x[t + j dil][c] W[u][j][c]
+ *                         y[t][u] = scale[u] act(z[t][u]) + offset[u]      act = max(0, .) if relu else the identity
+ *                       scale / offset are nullable (1 / 0) and applied as ONE fused multiply-add.  Kaldi's affine -> ReLU -> batch-norm
+ *                       (no learnt scale) and SpeechBrain's conv -> ReLU -> BN are this form with the inference-time BN in scale /
+ *                       offset; conv -> BN -> ReLU folds into W and b.  A NaN stays a NaN through the ReLU (ssp_dense_forward's rule).
+ *        Network        n_f frame layers; statistics pooling over the rows of the last one; n_s >= 0 segment layers of the same form
+ *                       with taps = 1 on the pooled vector.  The output is the last segment layer given (for Kaldi's embedding: the
+ *                       layers up to segment6 with relu = 0), the pooled vector itself with n_s = 0.  R = 1 + sum (taps - 1) dil is
+ *                       the receptive field: a sequence of T frames has T - R + 1 pooled rows.  The standard network: (taps, dil) =
+ *                       (5,1), (3,2), (3,3), (1,1), (1,1), widths 512, 512, 512, 512, 1500, pooled width 3000, a 3000 -> 512 segment
+ *                       layer, R = 15.
+ *        Pooling        of rows t in [a, b), n = b - a, of width C gives 2 C values, the means then the deviations:
+ *                         mean_c = sum_t x[t][c] / n;   dev_c = sqrt(max(sum_t (x[t][c] - mean_c)^2 / n, var_floor))
+ *                       — the population variance in the CENTRED form, accumulated in float64 with t ascending (two passes), rounded to
+ *                       float32 once.  A column constant over the window gives exactly sqrt(var_floor).  n = 0 (a sequence or window
+ *                       of fewer than R frames) gives a row of NaN — numpy's mean of nothing — and the call still answers SSP_OK; no
+ *                       other row moves by a bit.
+ *        Pool windows   pool_win: HOST int64[n_win x 3] of (sequence, first, end) in INPUT frame coordinates inside the sequence,
+ *                       sequences non-decreasing, 0 <= first <= end <= T_sequence (else SSP_ERR_INVALID before any GPU work); window w
+ *                       gives output row w.  The embedding of a window is DEFINED as the embedding of frames [first, end) extracted
+ *                       as a sequence of their own — the pooling of the last frame layer's rows [first, end - R + 1) of the sequence
+ *                       — and has the same BITS as that stand-alone extraction: the frame layers run once per sequence, only the
+ *                       pooling and the segment layers run per window.  NULL: one window per sequence, covering all of it.
+ *        Non-finite     the output is non-finite exactly where the float64 evaluation of the same float32 operands is: a NaN in frame
+ *                       t reaches exactly the pooled rows whose receptive field covers t and makes every column NaN in exactly the
+ *                       embeddings that pool such a row; every other sequence's and window's row keeps its bits.
+ *      A sequence's (window's) output bits depend neither on the batch it is in nor on the slab it lands in.
+ *      Limits (SSP_ERR_UNSUPPORTED before any GPU work): d_in and units of a frame layer up to 8192, taps up to 16, (taps - 1) dil up
+ *      to 1024, up to 64 frame and 64 segment layers, pooled width and segment widths up to 2^21. ---- */
+/* ONE frame layer.  X: float[frames x d_in] laid out by frame_seg (what ssp_mfcc_run and ssp_featnorm_sliding write); W:
+ * float[units x taps x d_in]; bias, scale, offset: float[units] (nullable); all on the side `where` names, any 4-byte alignment.
+ * Y: float[frames x units] with the ROW INDEX of X: output t of sequence s stands at row offsets[s] + t, left-aligned in the sequence;
+ * out_len (HOST int64[n_seq], nullable) receives the valid lengths max(0, T_s - (taps - 1) dil).  The last (taps - 1) dil rows of each
+ * sequence in Y are written but UNSPECIFIED (they hold sums that run into the next sequence or past the end, where the input reads as
+ * zero); rows in front of offsets[0] are neither read nor written.  Feeding Y and frame_seg to the next layer is therefore correct as
+ * it stands: a valid row never reads an unspecified one.  One launch of an implicit-im2col GEMM on the exact-fp32 MFMA: one k-ordered
+ * chain per output, taps ascending, channels ascending.
+ * Error against float64, before scale / offset: |z - ref| <= 1.01 (K + 1) 2^-23 (sum |x| |w| + |b|), K = taps d_in; with them multiply
+ * by |scale| and add 2^-23 |y| (tests/test_xvector_gpu.py). */
+int ssp_tdnn_forward(ssp_ctx* ctx, const float* X, const ssp_segments* frame_seg, int32_t d_in, const float* W, const float* bias, int32_t taps,
+                     int32_t dilation, int32_t units, int32_t relu, const float* scale, const float* offset, float* Y, int64_t* out_len, int where,
+                     float* kernel_ms);
+/* The pooling alone.  X: float[frames x dim] laid out by frame_seg; pool_win: HOST int64[n_win x 3] of (sequence, first, end) in X's
+ * frame coordinates inside the sequence — rows [first, end) are pooled as they stand, no receptive field is taken off — or NULL: every
+ * sequence whole (n_win is then ignored).  out: float[n_win or n_seq x 2 dim].  One workgroup per (window, 256 columns). */
+int ssp_stats_pool(ssp_ctx* ctx, const float* X, const ssp_segments* frame_seg, int32_t dim, const int64_t* pool_win, int64_t n_win, double var_floor,
+                   float* out, int where, float* kernel_ms);
+/* The network as one object.  Everything is a HOST array: units, taps, dilation, relu: int32[n_frame_layers]; W[l]:
+ * float[units[l] x taps[l] x d_in_l] (d_in_0 = d_in, d_in_l = units[l - 1]); bias, scale, offset: arrays of pointers to float[units[l]],
+ * each array and each entry nullable.  The segment layers likewise with taps = 1: seg_W[l]: float[seg_units[l] x d_in_l], d_in_0 =
+ * 2 units[n_frame_layers - 1].  n_frame_layers >= 1, n_segment_layers >= 0. */
+int ssp_xvector_create(ssp_ctx* ctx, int32_t d_in, int32_t n_frame_layers, const int32_t* units, const int32_t* taps, const int32_t* dilation,
+                       const float* const* W, const float* const* bias, const int32_t* relu, const float* const* scale, const float* const* offset,
+                       int32_t n_segment_layers, const int32_t* seg_units, const float* const* seg_W, const float* const* seg_bias,
+                       const int32_t* seg_relu, const float* const* seg_scale, const float* const* seg_offset, double var_floor, ssp_xvector** out);
+int ssp_xvector_destroy(ssp_xvector* xv);
+/* the receptive field R, the pooled width and the embedding width (each nullable) */
+int ssp_xvector_info(const ssp_xvector* xv, int32_t* receptive_field, int32_t* pooled_width, int32_t* embed_width);
+/* the workspace cap of one forward call in bytes (default 2 GiB): two ping-pong activation buffers of (slab rows x widest frame layer)
+ * floats, grow-only and kept on the object; a batch above it runs in slabs of WHOLE sequences, one sequence always runs.
+ * ssp_xvector_last_slab: the sequences in the largest slab of the last forward call. */
+int ssp_xvector_set_workspace(ssp_xvector* xv, size_t bytes);
+int ssp_xvector_last_slab(const ssp_xvector* xv, int64_t* sequences_out);
+/* feats: float[total frames x d_in] laid out by frame_seg, which must start at frame 0; pool_win (HOST, nullable) and n_win as above;
+ * emb_out: float[n_win or n_seq x embed width].  Ordered on the context's stream: with device pointers the call returns without a host
+ * wait once its buffers have grown.  Frame layers: one ssp_tdnn_forward launch each per slab; pooling: one launch; segment layers:
+ * ssp_dense_forward, then scale / offset in a launch of their own where given. */
+int ssp_xvector_forward(ssp_xvector* xv, const float* feats, const ssp_segments* frame_seg, const int64_t* pool_win, int64_t n_win, float* emb_out,
+                        int where, float* kernel_ms);
 
 /* ---- d-vector network training (since without a version step, like the LSTM and GRU entries): nn_model.inference, d_vector.py:168-206 —
  *      the Sequential of Dense / ReLU / Dropout layers :171-194, categorical cross-entropy and Adam(lr=1e-4) :198-203, spk.fit(batch_size

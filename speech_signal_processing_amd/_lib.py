@@ -140,6 +140,18 @@ SIGNATURES = {
     "ssp_conv2d_same_forward": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, _F32P, C.c_int, _MSP]),
     "ssp_l2_normalize": (C.c_int, [_P, _F32P, C.c_int64, C.c_int32, C.c_float, _F32P, C.c_int, _MSP]),
+    "ssp_tdnn_forward": (C.c_int, [_P, _F32P, _P, C.c_int32, _F32P, _F32P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F32P, _F32P, _F32P, _I64P,
+                                   C.c_int, _MSP]),
+    "ssp_stats_pool": (C.c_int, [_P, _F32P, _P, C.c_int32, _I64P, C.c_int64, C.c_double, _F32P, C.c_int, _MSP]),
+    "ssp_xvector_create": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                     C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_double, C.POINTER(_P)]),
+    "ssp_xvector_destroy": (C.c_int, [_P]),
+    "ssp_xvector_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ssp_xvector_set_workspace": (C.c_int, [_P, C.c_size_t]),
+    "ssp_xvector_last_slab": (C.c_int, [_P, _I64P]),
+    "ssp_xvector_forward": (C.c_int, [_P, _F32P, _P, _I64P, C.c_int64, _F32P, C.c_int, _MSP]),
     "ssp_dnn_trainer_create": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_void_p), C.c_int32, C.POINTER(_P)]),
     "ssp_dnn_trainer_destroy": (C.c_int, [_P]),

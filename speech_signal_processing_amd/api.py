@@ -2181,6 +2181,175 @@ class GruForward:
             pass
 
 
+def _xv_vec(x, units, what, where=None):
+    """a per-unit vector (bias / scale / offset) or None -> (kept array, address); ``where``: the side it must live on (None: host)"""
+    if x is None:
+        return None, None
+    if where is None:
+        a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+        if a.shape[0] != units:
+            raise ValueError("%s must have %d entries" % (what, units))
+        return a, a.ctypes.data
+    k, p, w = _as_f32(x, what)
+    if w != where or int(np.prod(k.shape)) != units:
+        raise ValueError("%s must have %d entries and live where X lives" % (what, units))
+    return k, p
+
+
+def _xv_windows(windows, seg: Segments):
+    """a window table (n_win, 3) of (sequence, first, end) or None -> (kept int64 array or None, pointer or None, output rows)"""
+    if windows is None:
+        return None, None, seg.n
+    w = np.ascontiguousarray(windows, dtype=np.int64)
+    if w.ndim != 2 or w.shape[1] != 3:
+        raise ValueError("windows must be (n_win, 3): sequence, first frame, end frame")
+    return w, w.ctypes.data_as(C.POINTER(C.c_int64)), int(w.shape[0])
+
+
+def tdnn_forward(ctx: Context, X, seg_or_counts, W, bias=None, dilation: int = 1, relu: bool = False, scale=None, offset=None,
+                 timing: bool = False):
+    """ONE frame layer of an x-vector network (ssp_tdnn_forward; include/ssp.h has the definition): X (frames, d_in) laid out by the
+    segments, W (units, taps, d_in), bias / scale / offset (units,) or None; all numpy or all torch CUDA tensors.  -> (Y (frames, units)
+    of X's kind with the ROW INDEX of X, valid lengths int64 (n_seq,)): the last (taps - 1) dilation rows of each sequence in Y are
+    unspecified [and kernel milliseconds]."""
+    xk, xp, where = _as_f32(X, "X")
+    wk, wp, wwhere = _as_f32(W, "W")
+    if wwhere != where:
+        raise ValueError("X and W must both be numpy arrays or both be torch CUDA tensors")
+    if xk.ndim != 2 or wk.ndim != 3 or int(wk.shape[2]) != int(xk.shape[1]):
+        raise ValueError("X (frames, d_in) and W (units, taps, d_in) must share d_in")
+    seg = _as_recordings(ctx, seg_or_counts)
+    if int(xk.shape[0]) < int(seg.offsets[-1]):
+        raise ValueError("fewer rows than the segments have frames")
+    units, taps, d_in = int(wk.shape[0]), int(wk.shape[1]), int(wk.shape[2])
+    bk, bp = _xv_vec(bias, units, "bias", where)
+    sk, sp = _xv_vec(scale, units, "scale", where)
+    ok, op = _xv_vec(offset, units, "offset", where)
+    Y = ctx._empty((int(xk.shape[0]), units), where)
+    lens = np.zeros(seg.n, dtype=np.int64)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_tdnn_forward(ctx._h, xp, seg._h, d_in, wp, bp, taps, int(dilation), units, 1 if relu else 0, sp, op, _raw_ptr(Y, where),
+                                              lens.ctypes.data_as(C.POINTER(C.c_int64)), where, C.byref(ms) if timing else None))
+    del xk, wk, bk, sk, ok
+    return (Y, lens, ms.value) if timing else (Y, lens)
+
+
+def stats_pool(ctx: Context, X, seg_or_counts, windows=None, var_floor: float = 1e-10, timing: bool = False):
+    """Statistics pooling alone (ssp_stats_pool): X (frames, dim) laid out by the segments, windows None (every sequence whole) or a host
+    table (n_win, 3) of (sequence, first, end) rows.  -> (n_win or n_seq, 2 dim) of X's kind: means, then deviations [and kernel ms]."""
+    xk, xp, where = _as_f32(X, "X")
+    if xk.ndim != 2 or int(xk.shape[1]) < 1:
+        raise ValueError("X must be (frames, dim)")
+    seg = _as_recordings(ctx, seg_or_counts)
+    if int(xk.shape[0]) < int(seg.offsets[-1]):
+        raise ValueError("fewer rows than the segments have frames")
+    wk, wptr, n_out = _xv_windows(windows, seg)
+    dim = int(xk.shape[1])
+    out = ctx._empty((n_out, 2 * dim), where)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_stats_pool(ctx._h, xp, seg._h, dim, wptr, n_out if wk is not None else 0, float(var_floor), _raw_ptr(out, where),
+                                            where, C.byref(ms) if timing else None))
+    del xk, wk
+    return (out, ms.value) if timing else out
+
+
+class XVectorForward:
+    """An x-vector network packed once for the GPU forward pass (ssp_xvector; include/ssp.h has the model).  ``frame_layers``: a list of
+    dicts with W (units, taps, d_in) and optionally b, scale, offset (units,), dilation (1) and relu (False); ``segment_layers``: the same
+    with W (units, d_in) and no dilation.  ``forward`` returns one embedding per sequence, or per window of a host table."""
+
+    def __init__(self, ctx: Context, frame_layers, segment_layers=(), var_floor: float = 1e-10):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        if len(frame_layers) < 1:
+            raise ValueError("at least one frame layer")
+        keep = []
+
+        def pack(layers, ndim, d_in, what):
+            n = len(layers)
+            units, taps, dil, relu, ptr = [], [], [], [], {k: [] for k in ("W", "b", "scale", "offset")}
+            for i, L in enumerate(layers):
+                unknown = set(L) - {"W", "b", "scale", "offset", "dilation", "relu"}
+                if unknown:
+                    raise ValueError("%s layer %d: unknown keys %s" % (what, i, sorted(unknown)))
+                W = np.ascontiguousarray(L["W"], dtype=np.float32)
+                if W.ndim != ndim or int(W.shape[-1]) != d_in:
+                    raise ValueError("%s layer %d: W must be %s with d_in = %d" % (what, i, "(units, taps, d_in)" if ndim == 3 else "(units, d_in)", d_in))
+                u = int(W.shape[0])
+                keep.append(W)
+                ptr["W"].append(W.ctypes.data)
+                for k in ("b", "scale", "offset"):
+                    a, p = _xv_vec(L.get(k), u, "%s layer %d: %s" % (what, i, k))
+                    keep.append(a)
+                    ptr[k].append(p)
+                units.append(u)
+                taps.append(int(W.shape[1]) if ndim == 3 else 1)
+                dil.append(int(L.get("dilation", 1)))
+                relu.append(1 if L.get("relu", False) else 0)
+                d_in = u
+            arr = lambda v: (C.c_int32 * max(n, 1))(*v)           # noqa: E731
+            vp = lambda v: (C.c_void_p * max(n, 1))(*v)           # noqa: E731
+            return n, arr(units), arr(taps), arr(dil), vp(ptr["W"]), vp(ptr["b"]), arr(relu), vp(ptr["scale"]), vp(ptr["offset"]), d_in
+
+        W0 = np.asarray(frame_layers[0]["W"])
+        if W0.ndim != 3:
+            raise ValueError("frame layer 0: W must be (units, taps, d_in)")
+        self.d_in = int(W0.shape[2])
+        nf, fu, ft, fd, fw, fb, fr, fs, fo, last = pack(frame_layers, 3, self.d_in, "frame")
+        ns, su, _, _, sw, sb, sr, ss, so, _ = pack(segment_layers, 2, 2 * last, "segment")
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_xvector_create(ctx._h, self.d_in, nf, fu, ft, fd, fw, fb, fr, fs, fo, ns, su, sw, sb, sr, ss, so, float(var_floor),
+                                                C.byref(h)))
+        self._h = h
+        del keep
+        r, p, e = C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(self._lib.ssp_xvector_info(self._h, C.byref(r), C.byref(p), C.byref(e)))
+        self.receptive_field, self.pooled_width, self.embed_width = r.value, p.value, e.value
+
+    def set_workspace(self, nbytes: int) -> "XVectorForward":
+        """cap of the activation workspace one forward call may hold; larger batches run in slabs of whole sequences (same bits)"""
+        _lib.check(self._lib.ssp_xvector_set_workspace(self._h, C.c_size_t(int(nbytes))))
+        return self
+
+    @property
+    def last_slab(self) -> int:
+        n = C.c_int64(0)
+        _lib.check(self._lib.ssp_xvector_last_slab(self._h, C.byref(n)))
+        return n.value
+
+    def forward(self, feats, seg_or_counts, windows=None, timing: bool = False):
+        """feats (frames, d_in) laid out by the segments (an api.Segments or the frames per sequence), numpy (host) or torch CUDA tensor;
+        windows: None or a host table (n_win, 3) of (sequence, first, end) input frames.  -> (n_seq or n_win, embed width) of feats'
+        kind [and kernel milliseconds]."""
+        keep, ptr, where = _as_f32(feats, "feats")
+        if keep.ndim != 2 or int(keep.shape[1]) != self.d_in:
+            raise ValueError("feats must be (frames, %d)" % self.d_in)
+        seg = _as_recordings(self.ctx, seg_or_counts)
+        if int(keep.shape[0]) < int(seg.offsets[-1]):
+            raise ValueError("fewer rows than the segments have frames")
+        wk, wptr, n_out = _xv_windows(windows, seg)
+        out = self.ctx._empty((n_out, self.embed_width), where)
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_xvector_forward(self._h, ptr, seg._h, wptr, n_out if wk is not None else 0, _raw_ptr(out, where), where,
+                                                     C.byref(ms) if timing else None))
+        del keep, wk
+        return (out, ms.value) if timing else out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_xvector_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def conv2d_same_out_shape(T: int, D: int, strides):
     """(To, Do) of a `same` convolution: ceil(in / stride)"""
     return -(-int(T) // int(strides[0])), -(-int(D) // int(strides[1]))

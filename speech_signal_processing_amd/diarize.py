@@ -144,7 +144,8 @@ class Diarizer:
 
     def run(self, signals, embed, win, hop, min_len=None, n_speakers=None, **vad):
         """signals: a list of raw signals (int16 PCM or float arrays); embed: a callable that takes the list of window chunks (1-D arrays)
-        and returns one embedding row per chunk (numpy or torch CUDA).  VAD.detect_batch (keywords ``vad``) -> VAD.speech_segments ->
+        and returns one embedding row per chunk (numpy or torch CUDA); when it has an ``embed_windows(signals, wins)`` method that is
+        called instead, with the per-signal (n, 2) sample windows.  VAD.detect_batch (keywords ``vad``) -> VAD.speech_segments ->
         windows(win, hop, min_len) -> embed -> cluster -> frame_labels on the VAD's frames.  -> a list of int32 arrays, one label per
         VAD frame of each signal, -1 where there is no speech (or no window)."""
         from . import VAD
@@ -155,7 +156,8 @@ class Diarizer:
         step = VAD.frameSize - VAD.overlap
         if not chunks:
             return [np.full(len(m), -1, dtype=np.int32) for m in masks]
-        emb = embed(chunks)
+        # an embedder that can pool windows of a recording it has run once (xvector.Extractor) is handed the recordings and the windows
+        emb = embed.embed_windows(signals, wins) if hasattr(embed, "embed_windows") else embed(chunks)
         if int(emb.shape[0]) != len(chunks):
             raise ValueError("embed returned %d rows for %d chunks" % (int(emb.shape[0]), len(chunks)))
         labels, _ = self.cluster(emb, counts, n_speakers=n_speakers)
