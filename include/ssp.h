@@ -59,6 +59,7 @@ typedef struct ssp_segments ssp_segments;
 typedef struct ssp_mfcc_plan ssp_mfcc_plan;
 typedef struct ssp_gmm ssp_gmm;
 typedef struct ssp_gmm_map ssp_gmm_map;
+typedef struct ssp_gmm_full ssp_gmm_full; /* full-covariance GMMs packed for the MFMA scorer */
 typedef struct ssp_ivector ssp_ivector;   /* a UBM and a total-variability matrix packed for i-vector extraction and the E-step */
 typedef struct ssp_plda ssp_plda;         /* enrolled speakers of a diagonalised PLDA model packed for the MFMA log-likelihood-ratio sweep */
 typedef struct ssp_dnn ssp_dnn;           /* a fully connected network packed for the MFMA forward pass */
@@ -465,6 +466,52 @@ int ssp_gmm_em_stats_batch(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const 
 int ssp_gmm_em_stats_shared(ssp_ctx* ctx, int32_t M, int32_t K, int32_t D, const double* weights, const double* means,
                             const double* covars, const float* feats, int64_t n_rows, const int64_t* row_off, const int64_t* n_frames,
                             double* nk_out, double* sx_out, double* sxx_out, double* loglik_sum_out, int where, float* kernel_ms);
+
+/* ---- Full-covariance GMMs: sklearn GaussianMixture(covariance_type='full'), sklearn's default.  An EXTENSION: the reference's two call
+ *      sites (GMM_UBM.py:158,169) train 'diag' models; a pickled sklearn model of the default type, and the full-covariance UBMs the
+ *      i-vector / PLDA / diarization chains usually start from, are scored and trained here. ----
+ * Definitions (sklearn mixture/_gaussian_mixture.py).  A model is HOST double weights[K], means[K x D] and prec_chol[K x D x D], row-major:
+ * sklearn's precisions_cholesky_, U_k = solve_triangular(cholesky(Sigma_k, lower=True), I, lower=True).T, UPPER triangular
+ * (_compute_precision_cholesky); only the upper triangle is read.  Per frame x_t (_estimate_log_gaussian_prob, _estimate_log_prob_resp):
+ *   y_tk = (x_t - mu_k) U_k;  lp_tk = log w_k - 1/2 (D log 2 pi + sum_j y_tkj^2) + sum_j log U_kjj;  lse_t = logsumexp_k lp_tk;
+ *   resp_tk = exp(lp_tk - lse_t).
+ * ssp_gmm_full_em_stats: the sums of one EM iteration (_estimate_gaussian_parameters, _estimate_gaussian_covariances_full in raw-moment
+ * form) about a caller-given shift c (HOST double[D]; null = 0), x' = x - c:
+ *   nk_out[K] = sum_t resp_tk;  sx_out[K x D] = sum_t resp_tk x'_t;  sxx_out[K x D x D] = sum_t resp_tk x'_t x'_t^T (exactly symmetric,
+ *   both triangles written);  loglik_sum_out = sum_t lse_t.
+ * The model is translation invariant: the shift only moves where float32 rounding happens (mu - c is formed in float64 on the host, the
+ * kernels subtract c from every x as they load it).  A caller that passes the global mean (gmm_train does) has no need to centre its
+ * features first.  The M step stays with the caller in float64: nk += 10 eps, m' = sx / nk, means = m' + c,
+ * Sigma = sxx / nk - m' m'^T + reg_covar I, U by _compute_precision_cholesky.
+ * feats float[n_frames x D] on the side `where` names (any 4-byte alignment); parameters and outputs are HOST arrays.
+ * Limits: 1 <= D <= 64, K >= 1; outside that SSP_ERR_UNSUPPORTED (D) or SSP_ERR_INVALID before any launch.  SSP_ERR_INVALID before any
+ * upload, the message naming model and mixture: a negative or non-finite weight, an all-zero weight vector, a diagonal entry of U that
+ * is not finite and > 0, a non-finite entry in the upper triangle or the means.  A mixture of weight 0 does not exist (as in
+ * ssp_gmm_pack): its responsibility is 0 and the other mixtures' results are the bits of the model without it.
+ * Kernels: exact fp32 MFMA (v_mfma_f32_32x32x2_f32) in two passes, frames in slabs whose lp[K][slab] workspace respects
+ * SSP_GMM_FULL_SCRATCH_MB (default 256).  Summation: one float32 accumulator adds at most 8192 frames (128 tiles of 64 per walker of the
+ * moment pass; 256 per workgroup sum of lse); everything above that is added in float64 in a fixed order.  Deterministic: no
+ * floating-point atomics, two calls on the same input give the same bits.
+ * Non-finite rows, ssp_gmm_em_stats' rule: a BAD frame (a NaN or +-inf entry) makes EVERY entry of nk_out, sx_out, sxx_out and
+ * loglik_sum_out NaN; no error is reported and nothing stays behind in the ctx's scratch: the next clean call gives the bits it gave
+ * before.
+ * ssp_gmm_full_pack / ssp_gmm_full_score: n_models models of K mixtures (weights[n_models x K], means[.. x D], prec_chol[.. x D x D]);
+ * has_ubm: model 0 is the UBM.  Outputs as ssp_gmm_score's, each nullable, on the side `where` names: loglik_out float[n_models x F]
+ * model-major (= score_samples), scores_out float[n_utt x n_models] per-utterance means (= score), argmax_out int32[n_utt] the arg-max
+ * of score - UBM score over the speaker models (first index on ties).  One precision: exact fp32 MFMA.  Without loglik_out the means are
+ * formed on the device from runs of whole utterances whose [n_models x frames] block fits SSP_GMM_FULL_SCRATCH_MB: the whole matrix
+ * need not exist; scores_out is bit for bit the same with and without loglik_out.  Non-finite rows, ssp_gmm_score's rule: a bad frame is
+ * NaN under every model (never -inf), its utterance's scores_out row is NaN and its argmax_out 0, and so are an empty utterance's; every
+ * other frame and utterance is BIT-IDENTICAL to the same call with the bad entries replaced by finite ones.  Device-pointer calls queue
+ * their kernels on the ctx stream and return without a host wait. */
+int ssp_gmm_full_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const double* weights, const double* means, const double* prec_chol,
+                          const double* shift, const float* feats, int64_t n_frames, double* nk_out, double* sx_out, double* sxx_out,
+                          double* loglik_sum_out, int where, float* kernel_ms);
+int ssp_gmm_full_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const double* weights, const double* means,
+                      const double* prec_chol, int32_t has_ubm, ssp_gmm_full** out);
+int ssp_gmm_full_destroy(ssp_gmm_full* gmm);
+int ssp_gmm_full_score(ssp_gmm_full* gmm, const float* feats, const ssp_segments* frame_seg, float* loglik_out, float* scores_out,
+                       int32_t* argmax_out, int where, float* kernel_ms);
 
 /* ---- Top-C fast scoring of mean-adapted GMM-UBM speaker models (GMM_UBM.py:158-170,181-197 are what it stands beside).  An EXTENSION
  *      the reference does not have: its models are trained independently and its scoring loops evaluate every mixture of every one.

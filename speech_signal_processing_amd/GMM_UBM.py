@@ -149,6 +149,14 @@ def identify_language(models, ubm, features, names=('Chinese', 'English', 'Japan
     return out, prob, pred
 
 
+def _cov_kind(g):
+    """'full' for a model whose precisions_cholesky_ is (K, D, D) (sklearn's default covariance_type), else what it says ('diag')"""
+    kind = getattr(g, "covariance_type", None)
+    if kind is None:
+        kind = "full" if np.ndim(getattr(g, "precisions_cholesky_", 0)) == 3 else "diag"
+    return kind
+
+
 def score_matrix(models, ubm, feats, top_c=None):
     """GMM_UBM.py:181-187 as a function: pred[j, i] = models[i].score(feats[j]) - ubm.score(feats[j]).
     ``top_c`` (an extension; None: the dense path below, unchanged): an int evaluates the same difference over the UBM's best top_c
@@ -156,11 +164,29 @@ def score_matrix(models, ubm, feats, top_c=None):
     same ValueError; with top_c = n_components it is the dense difference.
 
     models / ubm: fitted sklearn GaussianMixture(covariance_type='diag') objects (or anything with weights_,
-    means_, covariances_).  feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64).
+    means_, covariances_).  When every model and the UBM are covariance_type='full' (weights_, means_, precisions_cholesky_) they are scored
+    through api.GmmFullScorer, same shapes and errors; a mixed set, or top_c with full models, raises ValueError.
+    feats: list of (T_j, D) arrays.  Returns (pred (U, S) float64, argmax (U,) int64).
     ValueError when an utterance with frames holds a NaN or infinite entry, as sklearn's score raises (the scorer answers such an
     utterance with a NaN row — include/ssp.h, ssp_gmm_score — so this is read off the scores: no pass over the host arrays).  An empty
     utterance keeps its NaN row."""
+    kinds = {_cov_kind(g) for g in list(models) + [ubm]}  # (looked at before a context is made: the refusals need no device)
+    if len(kinds) > 1:
+        raise ValueError("score_matrix: the models and the UBM mix covariance types %s; score 'diag' and 'full' sets apart" % sorted(kinds))
+    if kinds == {"full"} and top_c is not None:
+        raise ValueError("score_matrix: top_c scoring needs mean-adapted 'diag' models; full-covariance models are scored densely")
     ctx = api.default_context()
+    if kinds == {"full"}:
+        scorer = api.GmmFullScorer.from_sklearn(ctx, models, ubm)
+        r = scorer.score_list(feats)
+        scorer.close()
+        sc = np.asarray(r["scores"], dtype=np.float64)
+        lens = np.array([np.shape(f)[0] for f in feats], dtype=np.int64)
+        bad = np.flatnonzero(~np.isfinite(sc).all(axis=1) & (lens > 0))
+        if bad.size:
+            raise ValueError("Input contains NaN, infinity or a value too large for float32: utterance %d%s"
+                             % (int(bad[0]), "" if bad.size == 1 else " (and %d more)" % (bad.size - 1)))
+        return sc[:, 1:] - sc[:, :1], np.asarray(r["argmax"]).astype(np.int64)
     if top_c is not None:
         scorer = api.MapScorer.from_sklearn(ctx, models, ubm)
         r = scorer.score_list(feats, top_c=int(top_c))
@@ -215,7 +241,7 @@ def load_models(model_dir="Model"):
 
 
 def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, random_state=None, model_dir=None, seeding='host',
-        adapt=None, relevance_factor=16.0, top_c=None):
+        adapt=None, relevance_factor=16.0, top_c=None, covariance_type='diag'):
     """GMM_UBM.py:134-199.  ``model`` falsy (the reference's default): one ``GaussianMixture(n_components, 'diag')`` per
     speaker is fitted on ``train[speaker]`` (speakers in ascending label order, like label_encoder.values()) and the UBM
     on the stacked training data (GMM_UBM.py:154-170), EM on the GPU (the speaker models together through gmm_train.fit_many for
@@ -226,7 +252,8 @@ def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, ra
     ``adapt`` (an extension; None: the reference's independent fits, unchanged): 'map' trains the UBM on the pooled data exactly as
     above and derives every speaker model from it by MAP adaptation of the means (gmm_train.map_adapt, ``relevance_factor``) instead of
     the per-speaker fits.  ``top_c`` (None: dense scoring, unchanged): an int scores through the top-C scorer (score_matrix; needs
-    mean-adapted models).
+    mean-adapted models).  ``covariance_type``: 'diag' (the reference's) or 'full' — passed to every fit; 'full' speaker models are
+    fitted one after the other and cannot be combined with adapt='map' or top_c.
     Prints and returns the train/test accuracies the reference prints; the models are left in ``GMM.last_model``."""
     if model is True:
         model = load_models(model_dir or "Model")
@@ -235,15 +262,20 @@ def GMM(train, x_train, y_train, x_test, y_test, n_components=16, model=None, ra
         D = np.asarray(train[speakers[0]]).shape[1] if speakers else 0
         if adapt not in (None, 'map'):
             raise ValueError("adapt must be None or 'map'")
+        if covariance_type != 'diag' and (adapt is not None or top_c is not None):
+            raise ValueError("adapt and top_c need covariance_type='diag'")
         if adapt == 'map':
             gmms = None  # (from the UBM, below)
+        elif covariance_type != 'diag':
+            gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type=covariance_type, random_state=random_state,
+                            seeding=seeding)
         elif n_components <= 64 and D <= 47:  # one EM launch per iteration for all speakers; the same bits as the loop below
             gmms = fit_many([train[s] for s in speakers], n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding)
         else:
             gmms = [GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(train[s])
                     for s in speakers]
         ubm_train = np.vstack([train[s] for s in speakers])
-        ubm = GaussianMixture(n_components=n_components, covariance_type='diag', random_state=random_state, seeding=seeding).fit(ubm_train)
+        ubm = GaussianMixture(n_components=n_components, covariance_type=covariance_type, random_state=random_state, seeding=seeding).fit(ubm_train)
         if adapt == 'map':
             gmms = map_adapt(ubm, [train[s] for s in speakers], relevance_factor=relevance_factor, adapt='m')
         model = (gmms, ubm)

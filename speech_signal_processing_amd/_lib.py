@@ -97,6 +97,10 @@ SIGNATURES = {
                                          C.c_int, _MSP]),
     "ssp_gmm_em_stats_shared": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, _P, _P,
                                           C.c_int, _MSP]),
+    "ssp_gmm_full_em_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _F32P, C.c_int64, _P, _P, _P, _P, C.c_int, _MSP]),
+    "ssp_gmm_full_pack": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.POINTER(_P)]),
+    "ssp_gmm_full_destroy": (C.c_int, [_P]),
+    "ssp_gmm_full_score": (C.c_int, [_P, _F32P, _P, _F32P, _F32P, _P, C.c_int, _MSP]),
     "ssp_gmm_map_pack": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.POINTER(_P)]),
     "ssp_gmm_map_destroy": (C.c_int, [_P]),
     "ssp_gmm_map_score": (C.c_int, [_P, _F32P, _P, C.c_int32, _F32P, _F32P, _P, _P, C.c_int, _MSP]),

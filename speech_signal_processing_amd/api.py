@@ -777,6 +777,126 @@ def gmm_em_stats_shared(ctx: "Context", weights, means, covars, feats, row_off, 
     return res
 
 
+GMM_FULL_MAX_D = 64  # ssp_gmm_full_em_stats / ssp_gmm_full_pack's feature dimension (include/ssp.h)
+
+
+def gmm_full_em_stats(ctx: "Context", weights, means, prec_chol, feats, shift=None, timing: bool = False) -> dict:
+    """E step + M-step sums of ONE EM iteration of a full-covariance GMM on the GPU (ssp_gmm_full_em_stats).
+    weights (K,), means (K,D), prec_chol (K,D,D) float64 — sklearn's precisions_cholesky_, upper triangular; feats (n, D) float32 (numpy
+    or device tensor); shift (D,) or None: the statistics are taken about it, x' = x - shift.
+    Returns nk (K,), sx (K,D), sxx (K,D,D), loglik_sum (float) as float64."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    mu = np.ascontiguousarray(means, dtype=np.float64)
+    pc = np.ascontiguousarray(prec_chol, dtype=np.float64)
+    if w.ndim != 1 or mu.ndim != 2 or mu.shape[0] != w.shape[0] or pc.shape != mu.shape + mu.shape[1:]:
+        raise ValueError("expected weights (K,), means (K,D), prec_chol (K,D,D)")
+    K, D = mu.shape
+    sh = None
+    if shift is not None:
+        sh = np.ascontiguousarray(shift, dtype=np.float64)
+        if sh.shape != (D,):
+            raise ValueError("shift must be (%d,)" % D)
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2 or keep.shape[1] != D:
+        raise ValueError("feats must be (frames, %d)" % D)
+    nk = np.empty(K, dtype=np.float64)
+    sx = np.empty((K, D), dtype=np.float64)
+    sxx = np.empty((K, D, D), dtype=np.float64)
+    ll = C.c_double(0.0)
+    ms = C.c_float(0.0)
+    with ctx._ordered(where):
+        _lib.check(ctx._lib.ssp_gmm_full_em_stats(ctx._h, K, D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
+                                                   sh.ctypes.data if sh is not None else None, ptr, int(keep.shape[0]), nk.ctypes.data,
+                                                   sx.ctypes.data, sxx.ctypes.data, C.byref(ll), where, C.byref(ms) if timing else None))
+    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll.value}
+    if timing:
+        res["kernel_ms"] = ms.value
+    return res
+
+
+class GmmFullScorer:
+    """Packed full-covariance GMMs (ssp_gmm_full).  weights (M,K), means (M,K,D), prec_chol (M,K,D,D) float64 — sklearn's
+    precisions_cholesky_ of covariance_type='full', upper triangular.  has_ubm: model 0 is the UBM; scores / argmax as GmmScorer's."""
+
+    def __init__(self, ctx: Context, weights, means, prec_chol, has_ubm: bool = True):
+        self.ctx = ctx
+        self._lib = ctx._lib
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        mu = np.ascontiguousarray(means, dtype=np.float64)
+        pc = np.ascontiguousarray(prec_chol, dtype=np.float64)
+        if w.ndim != 2 or mu.ndim != 3 or mu.shape[:2] != w.shape or pc.shape != mu.shape + mu.shape[2:]:
+            raise ValueError("expected weights (M,K), means (M,K,D), prec_chol (M,K,D,D)")
+        self.n_models, self.K, self.D = mu.shape
+        self.has_ubm = bool(has_ubm)
+        h = C.c_void_p()
+        _lib.check(self._lib.ssp_gmm_full_pack(ctx._h, self.n_models, self.K, self.D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
+                                                1 if has_ubm else 0, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_sklearn(cls, ctx: Context, models: Sequence, ubm=None) -> "GmmFullScorer":
+        """models / ubm: fitted sklearn or gmm_train GaussianMixture(covariance_type='full') objects (duck-typed: weights_, means_,
+        precisions_cholesky_), all with the same K and D."""
+        allm = ([ubm] if ubm is not None else []) + list(models)
+        for g in allm:
+            if getattr(g, "covariance_type", "full") != "full" or np.ndim(g.precisions_cholesky_) != 3:
+                raise ValueError("only covariance_type='full' models are supported here (GmmScorer takes 'diag' models)")
+        return cls(ctx, np.stack([g.weights_ for g in allm]), np.stack([g.means_ for g in allm]),
+                   np.stack([g.precisions_cholesky_ for g in allm]), has_ubm=ubm is not None)
+
+    def score(self, feats, frame_seg: Segments, loglik: bool = False, scores: bool = True, argmax: bool = True, timing: bool = False) -> dict:
+        """Returns a dict with the requested arrays: loglik (M, F) per-frame log-likelihood per model (= score_samples), scores (U, M)
+        mean log-likelihood (= GaussianMixture.score), argmax (U,) int32 over speaker models of score - score_ubm."""
+        keep, ptr, where = _as_f32(feats, "feats")
+        if keep.ndim != 2 or keep.shape[1] != self.D:
+            raise ValueError("feats must be (frames, %d)" % self.D)
+        if keep.shape[0] < frame_seg.total:
+            raise ValueError("feats has fewer rows than the frame segments cover")
+        F, U = frame_seg.total, frame_seg.n
+        ll = self.ctx._empty((self.n_models, F), where) if loglik else None
+        sc = self.ctx._empty((U, self.n_models), where) if scores else None
+        am = self.ctx._empty((U,), where, "int32") if argmax else None
+
+        def p(x):
+            if x is None:
+                return None
+            return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
+        ms = C.c_float(0.0)
+        with self.ctx._ordered(where):
+            _lib.check(self._lib.ssp_gmm_full_score(self._h, ptr, frame_seg._h, p(ll), p(sc), p(am), where, C.byref(ms) if timing else None))
+        res = {}
+        if loglik:
+            res["loglik"] = ll
+        if scores:
+            res["scores"] = sc
+        if argmax:
+            res["argmax"] = am
+        if timing:
+            res["kernel_ms"] = ms.value
+        return res
+
+    def score_list(self, feats_list, timing: bool = False) -> dict:
+        """score() on a list of (T_j, D) feature matrices, stacked on the host (not the hot path): scores (U, M) and argmax (U,)."""
+        mats = [np.asarray(a, dtype=np.float32) for a in feats_list]
+        for a in mats:
+            if a.ndim != 2 or a.shape[1] != self.D:
+                raise ValueError("every feature matrix must be (frames, %d)" % self.D)
+        fseg = Segments.from_lengths(self.ctx, [a.shape[0] for a in mats])
+        X = np.ascontiguousarray(np.concatenate(mats)) if mats else np.zeros((0, self.D), np.float32)
+        return self.score(X, fseg, loglik=False, scores=True, argmax=True, timing=timing)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.ssp_gmm_full_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 KMEANSPP_MAX_D = 64  # ssp_kmeanspp_seed's feature dimension (include/ssp.h)
 
 
@@ -862,7 +982,7 @@ class GmmScorer:
         allm = ([ubm] if ubm is not None else []) + list(models)
         for g in allm:
             if getattr(g, "covariance_type", "diag") != "diag":
-                raise ValueError("only covariance_type='diag' models are supported")
+                raise ValueError("only covariance_type='diag' models are supported here (GmmFullScorer takes 'full' models)")
         return cls(ctx, np.stack([g.weights_ for g in allm]), np.stack([g.means_ for g in allm]),
                    np.stack([g.covariances_ for g in allm]), has_ubm=ubm is not None)
 
@@ -988,7 +1108,7 @@ class MapScorer:
         uw, ucv = np.asarray(ubm.weights_), np.asarray(ubm.covariances_)
         for i, g in enumerate(models):
             if getattr(g, "covariance_type", "diag") != "diag":
-                raise ValueError("only covariance_type='diag' models are supported")
+                raise ValueError("only covariance_type='diag' models are supported (top-C scoring of 'full' models is not built)")
             for name, ref in (("weights_", uw), ("covariances_", ucv)):
                 v = np.asarray(getattr(g, name))
                 if v.shape != ref.shape or not np.array_equal(v, ref):

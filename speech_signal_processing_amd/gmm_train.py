@@ -15,6 +15,13 @@ kernels at a small shared spherical variance are the hard-assignment limit of th
 means and variances of the resulting clusters as the start, like sklearn's ``_initialize_parameters``.  The random streams
 differ from sklearn's, so trained models agree in quality, not bit for bit.  ``init_params='random_from_data'``: K distinct
 frames as means, the global variance as every covariance, uniform weights.
+
+``covariance_type='full'`` (sklearn's default) has the same surface: the O(frames x K x D^2) statistics come from
+``ssp_gmm_full_em_stats`` about the global mean (no need to centre the features first), the M step is sklearn's
+``_estimate_gaussian_covariances_full`` from those raw moments and ``_compute_precision_cholesky`` in float64 (``_m_step_full``), the
+start is sklearn's ``_initialize`` for given ``*_init`` and otherwise the stage above with the clusters' full covariances; fitted
+``covariances_`` / ``precisions_cholesky_`` / ``precisions_`` are (K, D, D), and scoring goes through ``api.GmmFullScorer``.
+``'tied'`` and ``'spherical'`` are refused.
 """
 from __future__ import annotations
 
@@ -52,12 +59,50 @@ def _kmeanspp_draws(rng, n, K):
     return idx, first, u
 
 
+_ILL_DEFINED = ("Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance caused by "
+                "singleton or collapsed samples). Try to decrease the number of components, increase reg_covar, or scale the input data.")
+
+
+def _lower_inverse_t(L):
+    """solve_triangular(L, I, lower=True).T by forward substitution, float64"""
+    D = L.shape[0]
+    inv = np.zeros((D, D))
+    for i in range(D):
+        row = -L[i, :i] @ inv[:i]
+        row[i] += 1.0
+        inv[i] = row / L[i, i]
+    return inv.T
+
+
+def precision_cholesky_full(covariances):
+    """sklearn's _compute_precision_cholesky for covariance_type='full': U_k = solve_triangular(cholesky(Sigma_k, lower=True), I,
+    lower=True).T, upper triangular, (K, D, D) float64; its ValueError when a covariance has no Cholesky factor."""
+    covariances = np.asarray(covariances, dtype=np.float64)
+    out = np.empty_like(covariances)
+    for k, cov in enumerate(covariances):
+        try:
+            if not np.isfinite(cov).all():
+                raise np.linalg.LinAlgError
+            L = np.linalg.cholesky(cov)
+        except np.linalg.LinAlgError:
+            raise ValueError(_ILL_DEFINED) from None
+        out[k] = _lower_inverse_t(L)
+    return out
+
+
+def precision_cholesky_from_precisions_full(precisions):
+    """sklearn's _compute_precision_cholesky_from_precisions for 'full': the upper-triangular U with U U^T = precision, J L J of the
+    Cholesky factor L of the row- and column-reversed matrix"""
+    precisions = np.asarray(precisions, dtype=np.float64)
+    return np.stack([np.linalg.cholesky(p[::-1, ::-1])[::-1, ::-1] for p in precisions])
+
+
 class GaussianMixture:
     def __init__(self, n_components=1, covariance_type='diag', tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1,
                  weights_init=None, means_init=None, precisions_init=None, random_state=None, init_params='kmeans', ctx=None,
                  seeding='host'):
-        if covariance_type != 'diag':
-            raise ValueError("only covariance_type='diag' is supported (what GMM_UBM.py:158,169 uses)")
+        if covariance_type not in ('diag', 'full'):
+            raise ValueError("only covariance_type='diag' (what GMM_UBM.py:158,169 uses) and 'full' (sklearn's default) are supported")
         if n_components < 1 or max_iter < 1 or n_init < 1 or tol < 0 or reg_covar < 0:
             raise ValueError("invalid GaussianMixture parameter")
         self.n_components = int(n_components)
@@ -200,6 +245,85 @@ class GaussianMixture:
             weights = np.full(K, 1.0 / K)
         return weights, means, covars
 
+    # ---- covariance_type='full': sklearn's M step from the raw moments about a shift (include/ssp.h, ssp_gmm_full_em_stats), float64
+    def _m_step_full(self, st, n, shift=None):
+        """(weights, means, covariances (K,D,D), precisions_cholesky) from nk, sx, sxx taken about ``shift``: algebraically
+        _estimate_gaussian_parameters / _estimate_gaussian_covariances_full, then _compute_precision_cholesky (its ValueError too)"""
+        nk = st["nk"] + 10 * np.finfo(np.float64).eps
+        m = st["sx"] / nk[:, None]
+        covs = st["sxx"] / nk[:, None, None] - m[:, :, None] * m[:, None, :]
+        D = m.shape[1]
+        covs[:, np.arange(D), np.arange(D)] += self.reg_covar
+        weights = nk / n
+        means = m if shift is None else m + np.asarray(shift, dtype=np.float64)[None]
+        return weights / weights.sum(), means, covs, precision_cholesky_full(covs)
+
+    def _full_start(self, ctx, X, n, D, rng, shift):
+        """the initial (weights, means, precisions_cholesky) of one 'full' start: the *_init arrays as sklearn's _initialize takes them, else
+        the k-means++ / Lloyd stage of the 'diag' path with the clusters' full covariances from ONE ssp_gmm_full_em_stats call at the final
+        centres (a small shared spherical variance: the hard-assignment limit); a cluster of fewer than D + 1 frames takes the global
+        covariance.  'random_from_data': K frames as means, the global covariance, uniform weights."""
+        K = self.n_components
+        eye = np.eye(D)
+        weights = means = U = None
+        if self.weights_init is not None:
+            weights = np.array(self.weights_init, dtype=np.float64).reshape(K)
+        if self.means_init is not None:
+            means = np.array(self.means_init, dtype=np.float64).reshape(K, D)
+        if self.precisions_init is not None:
+            U = precision_cholesky_from_precisions_full(np.array(self.precisions_init, dtype=np.float64).reshape(K, D, D))
+        if weights is not None and means is not None and U is not None:
+            return weights, means, U
+        g = api.gmm_full_em_stats(ctx, np.ones(1), shift[None], eye[None], X, shift=shift)
+        gm = g["sx"][0] / n
+        gcov = g["sxx"][0] / n - np.outer(gm, gm) + self.reg_covar * eye
+        gvar = np.maximum(np.diag(gcov), self.reg_covar)
+        st = None
+        if self.init_params == 'kmeans' and K > 1 and (means is None or U is None or weights is None):
+            _, centres = self._kmeans(ctx, X, n, D, rng, gvar)
+            tau = max(1e-2 * float(gvar.mean()), 1e-12)
+            st = api.gmm_full_em_stats(ctx, np.full(K, 1.0 / K), centres, np.tile(eye / np.sqrt(tau), (K, 1, 1)), X, shift=shift)
+            if means is None:
+                means = centres
+        if means is None:
+            means = (gm + shift)[None] if K == 1 else self._rows(X, np.sort(rng.choice(n, size=K, replace=False)))
+        if U is None:
+            covs = np.tile(gcov, (K, 1, 1))
+            if st is not None:
+                nk = st["nk"] + 10 * np.finfo(np.float64).eps
+                m = st["sx"] / nk[:, None]
+                own = st["sxx"] / nk[:, None, None] - m[:, :, None] * m[:, None, :] + self.reg_covar * eye[None]
+                covs = np.where((st["nk"] >= D + 1)[:, None, None], own, covs)
+            try:
+                U = precision_cholesky_full(covs)
+            except ValueError:  # (a cluster whose frames span no D dimensions: the global covariance, as for a small one)
+                U = precision_cholesky_full(np.tile(gcov, (K, 1, 1)))
+        if weights is None:
+            weights = np.maximum(st["nk"], 1.0) / np.maximum(st["nk"], 1.0).sum() if st is not None else np.full(K, 1.0 / K)
+        return weights, means, U
+
+    def _fit_full(self, ctx, X, n, D, rng):
+        import torch
+        shift = (X.sum(dim=0, dtype=torch.float64) / n).cpu().numpy()  # the global mean: where the statistics' float32 rounding happens
+        best = None
+        for _ in range(self.n_init):
+            weights, means, U = self._full_start(ctx, X, n, D, rng, shift)
+            covars = None
+            lower, converged, n_iter = -np.inf, False, 0
+            for n_iter in range(1, self.max_iter + 1):
+                prev = lower
+                st = api.gmm_full_em_stats(ctx, weights, means, U, X, shift=shift)
+                weights, means, covars, U = self._m_step_full(st, n, shift)
+                lower = st["loglik_sum"] / n
+                if abs(lower - prev) < self.tol:
+                    converged = True
+                    break
+            if best is None or lower > best[0]:
+                best = (lower, weights, means, covars, n_iter, converged, U)
+        self.lower_bound_, self.weights_, self.means_, self.covariances_, self.n_iter_, self.converged_, self.precisions_cholesky_ = best
+        self.precisions_ = np.einsum('kij,klj->kil', self.precisions_cholesky_, self.precisions_cholesky_)
+        return self
+
     def fit(self, X, y=None):
         """EM until |delta lower bound| < tol or max_iter (sk:mixture/_base.py fit_predict), best of n_init starts."""
         ctx = self._ctx or api.default_context()
@@ -221,6 +345,10 @@ class GaussianMixture:
         if bad is not None:
             raise ValueError(_nonfinite_message("", bad))
         rng = np.random.RandomState(self.random_state) if not isinstance(self.random_state, np.random.RandomState) else self.random_state
+        if self.covariance_type == 'full':
+            if D > api.GMM_FULL_MAX_D:
+                raise NotImplementedError("covariance_type='full' covers at most %d features" % api.GMM_FULL_MAX_D)
+            return self._fit_full(ctx, X, n, D, rng)
         best = None
         for _ in range(self.n_init):
             weights, means, covars = self._initial(ctx, X, n, D, rng)
@@ -243,6 +371,8 @@ class GaussianMixture:
     # ---- scoring through the MFMA scorer (api.GmmScorer), same numbers as sklearn's methods
     def _scorer(self):
         ctx = self._ctx or api.default_context()
+        if self.covariance_type == 'full':
+            return api.GmmFullScorer(ctx, self.weights_[None], self.means_[None], self.precisions_cholesky_[None], has_ubm=False), ctx
         return api.GmmScorer(ctx, self.weights_[None], self.means_[None], self.covariances_[None], has_ubm=False), ctx
 
     # (sklearn raises ValueError on a NaN / infinite entry; the scorer answers one with NaN at that frame and in the utterance's score
@@ -288,6 +418,11 @@ def _per_model(v, M, base_ndim):
     return [v] * M
 
 
+def _fits_one_by_one(gms):
+    """the models of a fit_many call are covariance_type='full': fitted one after the other (no batched full-covariance kernel)"""
+    return gms[0].covariance_type == 'full'
+
+
 def _host_f32(X):
     if api._is_torch(X):
         X = X.detach().cpu().numpy()
@@ -316,7 +451,8 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
     if M == 0:
         return []
     inits = {name: _per_model(kwargs.pop(name, None), M, nd)
-             for name, nd in (("weights_init", 1), ("means_init", 2), ("precisions_init", 2))}
+             for name, nd in (("weights_init", 1), ("means_init", 2),
+                              ("precisions_init", 3 if kwargs.get("covariance_type", "diag") == "full" else 2))}
     gms = [GaussianMixture(n_components=n_components, weights_init=inits["weights_init"][m], means_init=inits["means_init"][m],
                            precisions_init=inits["precisions_init"][m], **kwargs) for m in range(M)]
     hosts = [_host_f32(X) for X in Xs]
@@ -327,7 +463,7 @@ def fit_many(Xs, n_components=1, profile=None, **kwargs):
             raise ValueError("every X must have the same number of features")
         if X.shape[0] < K:
             raise ValueError("Expected n_samples >= n_components but got n_components = %d, n_samples = %d" % (K, X.shape[0]))
-    if 2 * D + 1 > 96:  # no batched kernel (ssp_gmm_em_stats_batch: D <= 47)
+    if 2 * D + 1 > 96 or _fits_one_by_one(gms):  # no batched kernel (ssp_gmm_em_stats_batch: D <= 47, 'diag' only)
         out = []
         for m, (gm, X) in enumerate(zip(gms, hosts)):
             try:
@@ -486,7 +622,8 @@ def _diag_ubm_arrays(ubm):
     mu = np.asarray(ubm.means_, dtype=np.float64)
     cv = np.asarray(ubm.covariances_, dtype=np.float64)
     if mu.ndim != 2 or cv.shape != mu.shape or w.shape != mu.shape[:1]:
-        raise ValueError("only covariance_type='diag' UBMs are supported")
+        raise ValueError("only covariance_type='diag' UBMs are supported (MAP adaptation and the Baum-Welch statistics of a "
+                         "covariance_type='full' UBM are not built: fit and score full models through gmm_train / GMM_UBM.score_matrix)")
     return w, mu, cv
 
 
