@@ -70,15 +70,14 @@ struct GemmArgs {
 
 template <int MODE>
 __global__ __launch_bounds__(256) void dt_gemm_kernel(GemmArgs a) {
-    __shared__ __attribute__((aligned(16))) float red[4][256];  // (each wave stores its tile 16 bytes per lane)
+    __shared__ __attribute__((aligned(16))) float red[4][256];  // the waves' partial tiles (splitk_sum), then mode 2's db sums
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, kq = lane >> 4;
     const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
     const int M = a.M, N = a.N, K = a.K;
-    const int kchunk = (((K + 3) / 4 + 15) / 16) * 16;  // the fixed partition of K over the four waves
-    const int kbeg = wave * kchunk;
-    const int kend = kbeg + kchunk < K ? kbeg + kchunk : K;
+    const SplitK ks = splitk_range(K, wave);  // the fixed partition of K over the four waves (nn_device.hpp)
+    const int kend = ks.kend;
     const bool m_ok = m0 + i < M, n_ok = n0 + i < N;
     const float* arow = a.A;  // modes 0, 1: this lane's row of A
     if (MODE != 2 && m_ok) arow = a.A + (a.idx ? a.idx[m0 + i] : (int64_t)(m0 + i)) * a.lda;
@@ -122,30 +121,9 @@ __global__ __launch_bounds__(256) void dt_gemm_kernel(GemmArgs a) {
                 if (k + r < kend) bv[r] = a.B[(int64_t)(k + r) * N + n0 + i];
         }
     };
-    // two register sets: the loads of the blocks at kb + 32 and kb + 48 are issued before the MFMAs of the blocks at kb and kb + 16,
-    // so two blocks' round trips to L2 are in flight under the products (k still accumulates in ascending order: the same bits)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    float a0[4], b0[4], a1[4], b1[4];
-    load(kbeg, a0, b0);
-    load(kbeg + 16, a1, b1);
-    for (int kb = kbeg; kb < kend; kb += 32) {
-        float a2[4], b2[4], a3[4], b3[4];
-        load(kb + 32, a2, b2);
-        load(kb + 48, a3, b3);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[r], b0[r], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[r], b1[r], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a0[r] = a2[r], b0[r] = b2[r], a1[r] = a3[r], b1[r] = b3[r];
-    }
-    // lane (kq, i) register r = element (4 kq + r, i) of this wave's partial tile
-    *reinterpret_cast<f32x4*>(&red[wave][lane * 4]) = acc;
-    __syncthreads();
-    const int row = tid >> 4, col = tid & 15;
-    const int e = ((row >> 2) * 16 + col) * 4 + (row & 3);
-    float v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-    const int m = m0 + row, n = n0 + col;
+    const SplitKElem el = splitk_sum(red, splitk_walk(ks, load), tid, wave);
+    const int row = el.row, m = m0 + row, n = n0 + el.col;
+    float v = el.v;
     if (m < M && n < N) {
         if (MODE == 0) {
             if (a.bias) v += a.bias[n];

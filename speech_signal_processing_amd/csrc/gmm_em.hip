@@ -23,6 +23,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "gmm_lp_tile.hpp"
 
 namespace ssp {
 
@@ -146,7 +147,6 @@ __global__ __launch_bounds__(256) void gmm_em_acc_kernel(EmArgs a) {
     if (kg == 0) out[2 * D] = an;
 }
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // MFMA form of gmm_em_acc_kernel (D <= 47: at most 3 column tiles of [x, x^2, 1]).  Grid (G, K/64), 4 waves; per 64-frame tile
 //   GEMM1  lp[64 mix x 64 frames] = W[64 x (2D+1)] . aug^T        wave (r, c) owns one 32 x 32 tile; mixtures = MFMA rows, frames =
@@ -244,25 +244,8 @@ __device__ __forceinline__ void em_mfma_body(const EmArgs& a, unsigned wg) {
         fetch(tile + a.G);
         __syncthreads();
         // ---- GEMM1: A[row = mix 32 r1 + fl][k = 2 s + h], B[k = 2 s + h][col = frame 32 c1 + fl] = aug[frame][k]
-        f32x16 acc1;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc1[i] = 0.f;
-        const float* xrow = xs + (32 * c1 + fl) * XS;
-        const float* wcol = wsT + h * EM_KC + 32 * r1 + fl;
-        int s2 = 0;
-        for (; s2 + 3 < KS; s2 += 4) {  // four k-steps' operands in flight
-            float av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                av[u] = wcol[(2 * (s2 + u)) * EM_KC];
-                bv[u] = xrow[2 * (s2 + u) + h];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc1, 0, 0, 0);
-        }
-        for (; s2 < KS; ++s2)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * EM_KC], xrow[2 * s2 + h], acc1, 0, 0, 0);
-        // ---- responsibilities of this lane's frame; accumulator i = mixture 32 r1 + (i & 3) + 8 (i >> 2) + 4 h
+        const f32x16 acc1 = em_lp_tile<EM_KC>(xs + (32 * c1 + fl) * XS, wsT + h * EM_KC + 32 * r1 + fl, KS, h);
+        // ---- responsibilities of this lane's frame; accumulator i = mixture 32 r1 + em_lp_mix(i, h)
         const int fr = 32 * c1 + fl;
         if (FUSE) {
             float m = acc1[0];
@@ -285,10 +268,10 @@ __device__ __forceinline__ void em_mfma_body(const EmArgs& a, unsigned wg) {
             const float scale = valid ? __expf(m - mm) / tot : 0.f;
             if (valid && r1 == 0 && h == 0) lsum += mm + __logf(tot);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) rs[fr * 65 + 32 * r1 + (i & 3) + 8 * (i >> 2) + 4 * h] = e[i] * scale;
+            for (int i = 0; i < 16; ++i) rs[fr * 65 + 32 * r1 + em_lp_mix(i, h)] = e[i] * scale;
         } else {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) rs[fr * 65 + 32 * r1 + (i & 3) + 8 * (i >> 2) + 4 * h] = __expf(acc1[i] - l);
+            for (int i = 0; i < 16; ++i) rs[fr * 65 + 32 * r1 + em_lp_mix(i, h)] = __expf(acc1[i] - l);
         }
         __syncthreads();
         // ---- GEMM2 over this wave's 16 frames: A[row = mix 32 r + fl][k = frame], B[k = frame][col = 32 c + fl] = aug[frame][col]
@@ -393,13 +376,6 @@ struct EmBatchArgs {
     int64_t par_stride;     // floats between two models' parameter blocks: Kp (2D+1), or 0 when every model reads the same block
 };
 
-__device__ __forceinline__ int em_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t em_uniform64(int64_t v) {
-    const uint64_t u = (uint64_t)v;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 // model m of a batched call as the EmArgs of a single-model call; every value wave-uniform (read through readfirstlane: a persistent
 // walk whose bounds the compiler cannot prove uniform may be rebuilt as a loop over lane masks — tests/test_isa_guards.py)
 __device__ __forceinline__ EmArgs em_seg_args(const EmBatchArgs& b, int m) {
@@ -430,8 +406,8 @@ __global__ __launch_bounds__(256) void gmm_em_acc_mfma_seg_kernel(EmBatchArgs b)
 }
 
 // per-frame log-sum-exp of the unfused MFMA path (several 64-mixture chunks, or SSP_EM_NO_FUSE): workgroup = one 64-frame tile of one
-// model.  Per chunk: GEMM1 as in em_mfma_body (wave (r1, c1): mixtures 32 r1.., frames 32 c1..) over the SAME parameter image and in the
-// same k order, so that lp - lse in the accumulation kernel is the difference of two evaluations of one formula; then an online
+// model.  Per chunk: em_mfma_body's GEMM1 (wave (r1, c1): mixtures 32 r1.., frames 32 c1..), the same em_lp_tile (gmm_lp_tile.hpp) over
+// the same parameter values, so that lp - lse in the accumulation kernel is the difference of two evaluations of one formula; then an online
 // (max, sum) per frame over the chunks; the two mixture halves meet in LDS.  Writes lse[t] of the tile's frames and one lse partial per
 // tile.  The body is shared by the single-model kernel (tile = blockIdx.x) and the batched one (work[x] = (model, tile)).
 __device__ __forceinline__ void em_lse_mfma_body(const EmArgs& a, int tile) {
@@ -448,19 +424,7 @@ __device__ __forceinline__ void em_lse_mfma_body(const EmArgs& a, int tile) {
     const int fl = lane & 31, h = lane >> 5, r1 = wave >> 1, c1 = wave & 1;
     const int64_t base = (int64_t)tile * EM_TF;
     const int nt = (int)min<int64_t>(EM_TF, a.n - base);
-    for (int i0 = 0; i0 < EM_TF * 2 * KS; i0 += 256) {
-        const int i = i0 + tid;
-        if (i < EM_TF * 2 * KS) {
-            const int r = i / (2 * KS), c = i - r * (2 * KS);
-            float v = c == 2 * D ? 1.f : 0.f;
-            if (c < 2 * D) {
-                const int cd = c < D ? c : c - D;
-                const float xv = r < nt ? a.x[(base + r) * D + cd] : 0.f;
-                v = c < D ? xv : xv * xv;
-            }
-            xs[r * XS + c] = v;
-        }
-    }
+    em_stage_aug(xs, a.x, base, nt, D, KS, XS);
     const float* xrow = xs + (32 * c1 + fl) * XS;
     const float* wcol = wsT + h * EM_WS + 32 * r1 + fl;
     if (tid < EM_KC) wsT[W * EM_WS + tid] = 0.f;  // the zero pad row k = 2 D + 1 of the last k-step: written once, no chunk touches it
@@ -495,22 +459,7 @@ __device__ __forceinline__ void em_lse_mfma_body(const EmArgs& a, int tile) {
         }
         fetchw(kc + EM_KC);  // the next chunk travels while this one's MFMAs run
         __syncthreads();
-        f32x16 acc1;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc1[i] = 0.f;
-        int s2 = 0;
-        for (; s2 + 3 < KS; s2 += 4) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                av[u] = wcol[(2 * (s2 + u)) * EM_WS];
-                bv[u] = xrow[2 * (s2 + u) + h];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc1, 0, 0, 0);
-        }
-        for (; s2 < KS; ++s2)
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * EM_WS], xrow[2 * s2 + h], acc1, 0, 0, 0);
+        const f32x16 acc1 = em_lp_tile<EM_WS>(xrow, wcol, KS, h);
         float cm = acc1[0];
 #pragma unroll
         for (int i = 1; i < 16; ++i) cm = fmaxf(cm, acc1[i]);

@@ -4,8 +4,8 @@
 // every frame (include/ssp.h has the definition):
 //   L_s(x) - L_ubm(x) = log sum_{k in T(x)} post_k(x) exp(delta_{s,k}(x)),   post_k = exp(lp_k - L_ubm),   delta_{s,k} = x . a_{s,k} - b_{s,k}
 // Kernels per call:
-//   gmm_map_select_kernel  workgroup = 64 frames: the UBM's lp tiles per 64-mixture chunk on v_mfma_f32_32x32x2_f32 exactly as
-//                          gmm_em_lse_mfma_seg_kernel forms them; every lane keeps a sorted top-8 (value, index) of the 16 mixtures per chunk
+//   gmm_map_select_kernel  workgroup = 64 frames: the UBM's lp tiles per 64-mixture chunk on v_mfma_f32_32x32x2_f32, the tile function the
+//                          EM kernels call (gmm_lp_tile.hpp: em_stage_aug, em_lp_tile); every lane keeps a sorted top-8 (value, index) of the 16 mixtures per chunk
 //                          it sees of ITS frame; the four lists of a frame (two mixture halves x two lane halves) meet in LDS and one thread
 //                          per frame merges them -> idx[frame][C] in rank order, q[frame][C] = lp - L_ubm (log posterior within T), L_ubm
 //   gmm_map_score_kernel   workgroup = one utterance x 256 speakers, one wave per 64 of them (lane = speaker: a table row [k][d][speakers] is
@@ -19,11 +19,12 @@
 //   gmm_map_reduce_kernel  per utterance: mean of L_ubm (float64, fixed tree) and the first-index arg-max of the diff row
 // A frame's folding order is ascending mixture index whatever else sits in its block, blocks never mix utterances, and no
 // floating-point atomic exists here: same bits every call, and an utterance's results do not depend on its neighbours.
-// Every loop bound and table index that is uniform per wave is read through readfirstlane (map_uniform), as em_uniform in gmm_em.hip.
+// Every loop bound and table index that is uniform per wave is read through readfirstlane (em_uniform, gmm_lp_tile.hpp).
 #include <chrono>
 #include <cmath>
 
 #include "common.hpp"
+#include "gmm_lp_tile.hpp"
 
 namespace ssp {
 
@@ -32,15 +33,6 @@ constexpr int MAP_KC = 64;    // mixtures per chunk
 constexpr int MAP_CMAX = 8;   // largest C
 constexpr int MAP_SL = 64;    // speakers per wave
 constexpr int MAP_WV = 4;     // waves (speaker tiles) per scoring workgroup
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ int map_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t map_uniform64(int64_t v) {
-    const uint64_t u = (uint64_t)v;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(u >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // (value, index) a ranks before b: larger value, of equal values the lower index
 __device__ __forceinline__ bool map_before(float va, int ia, float vb, int ib) { return va > vb || (va == vb && ia < ib); }
@@ -63,23 +55,11 @@ __global__ __launch_bounds__(256) void gmm_map_select_kernel(MapSelArgs a) {
     float* wsT = xs + MAP_TF * XS;       // [2 KS][64 mix]   parameter chunk, k-major
     float* lv = wsT + 2 * KS * MAP_KC;   // [64 frames][4 lists][8] values
     int* li = reinterpret_cast<int*>(lv + MAP_TF * 4 * MAP_CMAX);  // ... and indices
-    const int tid = threadIdx.x, lane = tid & 63, wave = map_uniform(tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wave = em_uniform(tid >> 6);
     const int fl = lane & 31, h = lane >> 5, r1 = wave >> 1, c1 = wave & 1;
     const int64_t base = a.f0 + (int64_t)blockIdx.x * MAP_TF;
     const int nt = (int)min<int64_t>(MAP_TF, a.f1 - base);
-    for (int i0 = 0; i0 < MAP_TF * 2 * KS; i0 += 256) {
-        const int i = i0 + tid;
-        if (i < MAP_TF * 2 * KS) {
-            const int r = i / (2 * KS), c = i - r * (2 * KS);
-            float v = c == 2 * D ? 1.f : 0.f;
-            if (c < 2 * D) {
-                const int cd = c < D ? c : c - D;
-                const float xv = r < nt ? a.x[(base + r) * D + cd] : 0.f;
-                v = c < D ? xv : xv * xv;
-            }
-            xs[r * XS + c] = v;
-        }
-    }
+    em_stage_aug(xs, a.x, base, nt, D, KS, XS);
     const float* xrow = xs + (32 * c1 + fl) * XS;
     const float* wcol = wsT + h * MAP_KC + 32 * r1 + fl;
     float tv[MAP_CMAX];
@@ -99,26 +79,12 @@ __global__ __launch_bounds__(256) void gmm_map_select_kernel(MapSelArgs a) {
             }
         }
         __syncthreads();
-        f32x16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        int s2 = 0;
-        for (; s2 + 3 < KS; s2 += 4) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                av[u] = wcol[(2 * (s2 + u)) * MAP_KC];
-                bv[u] = xrow[2 * (s2 + u) + h];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u], acc, 0, 0, 0);
-        }
-        for (; s2 < KS; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wcol[(2 * s2) * MAP_KC], xrow[2 * s2 + h], acc, 0, 0, 0);
-        // accumulator i = mixture kc + 32 r1 + (i & 3) + 8 (i >> 2) + 4 h of this lane's frame: ascending in i
+        const f32x16 acc = em_lp_tile<MAP_KC>(xrow, wcol, KS, h);
+        // accumulator i = mixture kc + 32 r1 + em_lp_mix(i, h) of this lane's frame: ascending in i
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const float v = acc[i];
-            const int k = kc + 32 * r1 + (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int k = kc + 32 * r1 + em_lp_mix(i, h);
             if (map_before(v, k, tv[MAP_CMAX - 1], ti[MAP_CMAX - 1])) {  // (a NaN never enters: its frame is answered as bad below)
                 tv[MAP_CMAX - 1] = v;
                 ti[MAP_CMAX - 1] = k;
@@ -217,18 +183,18 @@ __global__ __launch_bounds__(256) void gmm_map_score_kernel(MapScoreArgs a) {
     int* badf = ent + MAP_TF * MAP_CMAX;              // [64]
     int* ntot = badf + MAP_TF;                        // [1] pairs of the block (+ 3 pad)
     int* cnt = ntot + 4;                              // [K]  histogram -> bucket starts -> bucket ends
-    const int tid = threadIdx.x, lane = tid & 63, wave = map_uniform(tid >> 6);
-    const int u = blockIdx.x, s0 = map_uniform((blockIdx.y * MAP_WV + wave) * MAP_SL);
+    const int tid = threadIdx.x, lane = tid & 63, wave = em_uniform(tid >> 6);
+    const int u = blockIdx.x, s0 = em_uniform((blockIdx.y * MAP_WV + wave) * MAP_SL);
     const bool live = s0 < a.Sp;                      // (a wave past the last speaker tile stages and sorts with the others, then idles)
     float* st_m = st + wave * 2 * MAP_TF * MAP_SL;
     float* st_s = st_m + MAP_TF * MAP_SL;
-    const int64_t f0 = map_uniform64(a.off[u]), f1 = map_uniform64(a.off[u + 1]);
+    const int64_t f0 = em_uniform64(a.off[u]), f1 = em_uniform64(a.off[u + 1]);
     const float* tcol = a.tab + (live ? s0 : 0) + lane;
     const size_t kstride = (size_t)(DP + 1) * a.Sp;
     const int per = (K + 63) / 64;  // histogram bins per lane in the scan
     double acc = 0.0;
     for (int64_t fb = f0; fb < f1; fb += MAP_TF) {
-        const int nf = map_uniform((int)min<int64_t>(MAP_TF, f1 - fb));
+        const int nf = em_uniform((int)min<int64_t>(MAP_TF, f1 - fb));
         __syncthreads();  // the previous block is done with everything below
         for (int i0 = 0; i0 < nf * DP; i0 += 256) {
             const int i = i0 + tid;
@@ -245,7 +211,7 @@ __global__ __launch_bounds__(256) void gmm_map_score_kernel(MapScoreArgs a) {
             if (k0 + tid < K) cnt[k0 + tid] = 0;
         if (tid < nf) badf[tid] = a.idx[(fb + tid) * C] < 0 ? 1 : 0;
         __syncthreads();
-        const int np = map_uniform(nf * C);
+        const int np = em_uniform(nf * C);
         for (int p0 = 0; p0 < np; p0 += 256) {
             const int p = p0 + tid;
             if (p < np) {
@@ -289,20 +255,20 @@ __global__ __launch_bounds__(256) void gmm_map_score_kernel(MapScoreArgs a) {
             }
         }
         __syncthreads();  // cnt[k] is now the END of bucket k
-        const int n = live ? map_uniform(ntot[0]) : 0;
+        const int n = live ? em_uniform(ntot[0]) : 0;
         // the table columns of the next TWO distinct mixtures fly while a bucket is walked: a wave keeps 2 (DP + 1) x 256 bytes in flight
         float n1[DP + 1], n2[DP + 1];
 #pragma unroll
         for (int d = 0; d <= DP; ++d) n1[d] = n2[d] = 0.f;
         int e1 = 0, e2 = n;  // bucket starts of the mixtures in n1 (the one to walk next) and n2
         if (n > 0) {
-            const int k1 = map_uniform(ent[0]) >> 6;
+            const int k1 = em_uniform(ent[0]) >> 6;
             const float* t = tcol + (size_t)k1 * kstride;
 #pragma unroll
             for (int d = 0; d <= DP; ++d) n1[d] = t[(size_t)d * a.Sp];
-            e2 = map_uniform(cnt[k1]);
+            e2 = em_uniform(cnt[k1]);
             if (e2 < n) {
-                const float* t2 = tcol + (size_t)(map_uniform(ent[e2]) >> 6) * kstride;
+                const float* t2 = tcol + (size_t)(em_uniform(ent[e2]) >> 6) * kstride;
 #pragma unroll
                 for (int d = 0; d <= DP; ++d) n2[d] = t2[(size_t)d * a.Sp];
             }
@@ -317,15 +283,15 @@ __global__ __launch_bounds__(256) void gmm_map_score_kernel(MapScoreArgs a) {
             const int b0 = e1, b1 = e2;  // this bucket
             e1 = e2;
             if (e2 < n) {
-                e2 = map_uniform(cnt[map_uniform(ent[e2]) >> 6]);
+                e2 = em_uniform(cnt[em_uniform(ent[e2]) >> 6]);
                 if (e2 < n) {
-                    const float* t2 = tcol + (size_t)(map_uniform(ent[e2]) >> 6) * kstride;
+                    const float* t2 = tcol + (size_t)(em_uniform(ent[e2]) >> 6) * kstride;
 #pragma unroll
                     for (int d = 0; d <= DP; ++d) n2[d] = t2[(size_t)d * a.Sp];
                 }
             }
             for (int i = b0; i < b1; ++i) {
-                const int r = map_uniform(ent[i]) & 63;
+                const int r = em_uniform(ent[i]) & 63;
                 const float* xr = xs + r * DP;
                 float dl[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved chains (fixed shape): a single one waits on itself
 #pragma unroll

@@ -23,7 +23,7 @@
 //     from the master layout, 64 contiguous bytes per row and k group.  No second image
 //   * the other gradients once per layer and step as GEMMs over the stash: dW = x^T dA with db (mode 2, K = To Bn), dx = dA W^T (mode 1);
 //     dU_zr = h_{t-1}^T [da_z | da_r] and dU_h = (r . h_{t-1})^T da_h write column blocks of the (H, 3H) gradient from column blocks of
-//     dA: gt_gemm_tn_kernel, mode 2's body with row strides for B and C (the same fixed quarters of K over four waves, added in wave order)
+//     dA: gt_gemm_tn_kernel, mode 2's loader with row strides for B and C on the same split-K tile (nn_device.hpp)
 //   * conv backward (dK, db only): the To Bn Do output positions are cut into 64 fixed chunks, one wave per (tap, chunk, 64 filters), the
 //     chunks added in order by a second launch, which also adds the regulariser's 2 lambda K
 #include <cmath>
@@ -244,8 +244,8 @@ __global__ __launch_bounds__(256) void gt_pack_kernel(const float* __restrict__ 
     img[e] = U[(int64_t)(16 * g + 4 * (lane >> 4) + r) * 3 * H + q * H + 16 * j + (lane & 15)];
 }
 
-// C[M x N] (row stride ldc) = A^T B, A [K x M] (row stride lda), B [K x N] (row stride ldb): dnn_train.hip's mode 2 with strides — a
-// 16 x 16 tile per workgroup, K in fixed quarters (rounded up to 16) over four waves, the four partial tiles added in wave order
+// C[M x N] (row stride ldc) = A^T B, A [K x M] (row stride lda), B [K x N] (row stride ldb): dnn_train.hip's mode 2 with strides — the
+// split-K tile of nn_device.hpp (splitk_range, splitk_walk, splitk_sum) behind a strided loader
 struct GtGemmArgs {
     const float *A, *B;
     float* C;
@@ -260,9 +260,8 @@ __global__ __launch_bounds__(256) void gt_gemm_tn_kernel(GtGemmArgs a) {
     const int i = lane & 15, kq = lane >> 4;
     const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
     const int M = a.M, N = a.N, K = a.K;
-    const int kchunk = (((K + 3) / 4 + 15) / 16) * 16;
-    const int kbeg = wave * kchunk;
-    const int kend = kbeg + kchunk < K ? kbeg + kchunk : K;
+    const SplitK ks = splitk_range(K, wave);
+    const int kend = ks.kend;
     const bool m_ok = m0 + i < M, n_ok = n0 + i < N;
     auto load = [&](int kb, float (&av)[4], float (&bv)[4]) {
         const int k = kb + 4 * kq;
@@ -272,27 +271,8 @@ __global__ __launch_bounds__(256) void gt_gemm_tn_kernel(GtGemmArgs a) {
             bv[r] = (n_ok && k + r < kend) ? a.B[(int64_t)(k + r) * a.ldb + n0 + i] : 0.f;
         }
     };
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    float a0[4], b0[4], a1[4], b1[4];
-    load(kbeg, a0, b0);
-    load(kbeg + 16, a1, b1);
-    for (int kb = kbeg; kb < kend; kb += 32) {
-        float a2[4], b2[4], a3[4], b3[4];
-        load(kb + 32, a2, b2);
-        load(kb + 48, a3, b3);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[r], b0[r], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[r], b1[r], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) a0[r] = a2[r], b0[r] = b2[r], a1[r] = a3[r], b1[r] = b3[r];
-    }
-    *reinterpret_cast<f32x4*>(&red[wave][lane * 4]) = acc;
-    __syncthreads();
-    const int row = tid >> 4, col = tid & 15;
-    const int e = ((row >> 2) * 16 + col) * 4 + (row & 3);
-    const float v = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-    if (m0 + row < M && n0 + col < N) a.C[(int64_t)(m0 + row) * a.ldc + n0 + col] = v;
+    const SplitKElem el = splitk_sum(red, splitk_walk(ks, load), tid, wave);
+    if (m0 + el.row < M && n0 + el.col < N) a.C[(int64_t)(m0 + el.row) * a.ldc + n0 + el.col] = el.v;
 }
 
 // Conv2D, one input channel, channels last, TensorFlow's `same` (gru.hip's conv2d_same_kernel) on the rows of this batch, gathered through

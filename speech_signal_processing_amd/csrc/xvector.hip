@@ -2,8 +2,8 @@
 // written out in include/ssp.h ("x-vector extractor").  An EXTENSION and UNPINNED: the reference has no TDNN; tests/xvector_oracle.py is
 // the float64 restatement.
 //
-// * tdnn_kernel     a frame layer as an implicit-im2col GEMM on v_mfma_f32_32x32x2_f32, staged as dense_kernel (dense.hip) stages its
-//                   operands: the k index runs over (tap, channel), tap j of output row r reads input row r + j dil through the
+// * tdnn_kernel     a frame layer as an implicit-im2col GEMM on v_mfma_f32_32x32x2_f32, the staged block of gemm128.hpp that dense_kernel
+//                   (dense.hip) runs too: the k index runs over (tap, channel), tap j of output row r reads input row r + j dil through the
 //                   buffer resource, nothing unfolded is ever written.  The output keeps the ROW INDEX of its input (left-aligned in
 //                   every sequence), so the kernel has no per-sequence logic: the last (taps - 1) dil rows of a sequence are junk that
 //                   no valid row of a later layer reads and no window pools.  ONE k-ordered chain per output (taps ascending, channels
@@ -15,16 +15,13 @@
 #include <cstdlib>
 
 #include "common.hpp"
-#include "nn_device.hpp"
+#include "gemm128.hpp"
 
 namespace ssp {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int TBM = 128;  // units per block step
-constexpr int TBN = 128;  // rows per workgroup
-constexpr int TBK = 32;   // k-chunk (inside one tap)
-constexpr int TPL = 128 * 4 + 4;  // floats per (q, h) plane of an operand image (dense.hip: the pad spreads the planes over the banks)
+constexpr int TBM = G128_BM;  // units per block step
+constexpr int TBN = G128_BN;  // rows per workgroup
+constexpr int TBK = G128_BK;  // k-chunk (inside one tap)
 
 constexpr int TDNN_MAX_DIM = 8192;   // d_in and units
 constexpr int TDNN_MAX_TAPS = 16;
@@ -41,15 +38,6 @@ struct TdnnArgs {
     int32_t d_in, units, taps, dil, relu;
 };
 
-// rows [row0, row0 + n_rows) of a row-major matrix of d floats a row, clipped to the matrix: what lies outside reads as zero
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tdnn_rsrc(const float* A, int64_t row0, int64_t total_rows, int64_t n_rows, int d) {
-    int64_t rows = total_rows - row0 < n_rows ? total_rows - row0 : n_rows;
-    const uint64_t addr = reinterpret_cast<uint64_t>(A + row0 * d);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr), hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-    const int bytes = __builtin_amdgcn_readfirstlane((int)(rows > 0 ? rows * d * 4 : 0));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
-}
-
 // where the two operand streams stand in the (tap, chunk) walk; every step is known on entry: taps x n_kc of them, then zeros
 struct TdnnStep {
     int j, kc;
@@ -60,143 +48,42 @@ struct TdnnStep {
     }
 };
 
-// a [128 x TBK] slab, columns [k0, k0 + 32) of one tap: row r of the slab is `stride` floats after row r - 1 and the tap's first column
-// is `base` floats into row 0.  Columns at and past d (the next tap's, or the next row's) are cleared in registers; a slab that is
-// not `live` (past the last tap) is all zeros
-__device__ __forceinline__ void tdnn_load(__amdgpu_buffer_rsrc_t rs, int stride, int base, int d, int k0, bool live, int tid, float4 (&v)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + i * 256;
-        const int r = idx >> 3, c4 = idx & 7;
-        const int k = k0 + c4 * 4;
-        const f32x4 t = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (live && k < d) ? (r * stride + base + k) * 4 : 0x7ffffff0, 0, 0));
-        v[i].x = t.x;
-        v[i].y = k + 1 < d ? t.y : 0.f;
-        v[i].z = k + 2 < d ? t.z : 0.f;
-        v[i].w = k + 3 < d ? t.w : 0.f;
-    }
-}
-
-__device__ __forceinline__ void tdnn_store(float* __restrict__ img, int tid, const float4 (&v)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = tid + i * 256;
-        const int r = idx >> 3, c4 = idx & 7;
-        const int q = c4 >> 1, e0 = (c4 & 1) * 2;
-        *reinterpret_cast<float2*>(img + (size_t)(q * 2 + 0) * TPL + r * 4 + e0) = make_float2(v[i].x, v[i].z);
-        *reinterpret_cast<float2*>(img + (size_t)(q * 2 + 1) * TPL + r * 4 + e0) = make_float2(v[i].y, v[i].w);
-    }
-}
-
+// gemm128.hpp's block with the k index running over (tap, channel): slab (j, kc) of the weights is columns [32 kc, 32 kc + 32) of tap j
+// of a row of taps x d_in floats, that of the rows the same columns of input row r + j dil (d_in floats on)
 __global__ __launch_bounds__(256, 2) void tdnn_kernel(TdnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int SLAB = (TBK / 8) * 2 * TPL;
-    float* imgA = reinterpret_cast<float*>(smem);  // weights [2][SLAB]
-    float* imgB = imgA + 2 * SLAB;                 // rows    [2][SLAB]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fl = lane & 31, h = lane >> 5;
-    const int wr = wave >> 1, wc = wave & 1;  // 2 x 2 waves, each 64 units x 64 rows
+    const int tid = threadIdx.x;
     const int64_t col0 = (int64_t)blockIdx.x * TBN;
     const int d = a.d_in, taps = a.taps;
     const int wstride = taps * d, xshift = a.dil * d;
-    const bool vst = (a.units & 3) == 0 && (reinterpret_cast<uintptr_t>(a.Y) & 15) == 0;
     const int n_kc = (d + TBK - 1) / TBK;
-    const int n_st = n_kc * taps;
     const int n_rb = (a.units + TBM - 1) / TBM;
     // the rows this workgroup's taps reach: its own 128 and the (taps - 1) dil behind them
-    const __amdgpu_buffer_rsrc_t rx = tdnn_rsrc(a.X, col0, a.N, (int64_t)TBN + (int64_t)(taps - 1) * a.dil, d);
+    const __amdgpu_buffer_rsrc_t rx = g128_rsrc(a.X, col0, a.N, (int64_t)TBN + (int64_t)(taps - 1) * a.dil, d);
+    // (the nullable arrays are resolved here, once: the epilogue's element loop tests nothing that is not a register)
+    const float *bias = a.bias, *scale = a.scale, *offset = a.offset;
+    const int relu = a.relu;
+    const bool affine = scale || offset;
     for (int rb = 0; rb < n_rb; ++rb) {
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[rt][ct][i] = 0.f;
-        float4 va[4], vp[4], vq[4];
-        const __amdgpu_buffer_rsrc_t rw = tdnn_rsrc(a.W, (int64_t)rb * TBM, a.units, TBM, wstride);
+        const __amdgpu_buffer_rsrc_t rw = g128_rsrc(a.W, (int64_t)rb * TBM, a.units, TBM, wstride);
         TdnnStep sw{0, 0}, sx{0, 0};  // the next slab each stream loads
-        auto load_w = [&](float4 (&v)[4]) {
-            tdnn_load(rw, wstride, sw.j * d, d, sw.kc * TBK, sw.j < taps, tid, v);
-            sw.next(n_kc);
-        };
-        auto load_x = [&](float4 (&v)[4]) {
-            tdnn_load(rx, d, sx.j * xshift, d, sx.kc * TBK, sx.j < taps, tid, v);
-            sx.next(n_kc);
-        };
-        load_w(va);
-        load_x(vq);
-        load_x(vp);
-        __syncthreads();  // the previous unit block's last slab is consumed
-        tdnn_store(imgA, tid, va);
-        tdnn_store(imgB, tid, vq);
-        load_w(va);
-        load_x(vq);
-        __syncthreads();
-        // step s: MFMAs on image s & 1; `vn` holds row slab s + 1 and is refilled with slab s + 3 once stored (dense.hip)
-        auto slab = [&](int s, float4 (&vn)[4]) {
-            const float* cA = imgA + (s & 1) * SLAB;
-            const float* cB = imgB + (s & 1) * SLAB;
-#pragma unroll
-            for (int q = 0; q < TBK / 8; ++q) {
-                if (q == TBK / 16 && s + 1 < n_st) {
-                    tdnn_store(imgA + ((s + 1) & 1) * SLAB, tid, va);
-                    tdnn_store(imgB + ((s + 1) & 1) * SLAB, tid, vn);
-                    load_w(va);
-                    load_x(vn);
-                }
-                f32x4 av[2], bv[2];
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt)
-                    av[rt] = *reinterpret_cast<const f32x4*>(cA + (size_t)(q * 2 + h) * TPL + (wr * 64 + rt * 32 + fl) * 4);
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-                    bv[ct] = *reinterpret_cast<const f32x4*>(cB + (size_t)(q * 2 + h) * TPL + (wc * 64 + ct * 32 + fl) * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                        for (int ct = 0; ct < 2; ++ct)
-                            acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[rt][e], bv[ct][e], acc[rt][ct], 0, 0, 0);
-            }
-            __syncthreads();  // image s is consumed, image s + 1 is complete
-        };
-        for (int s = 0; s < n_st; s += 2) {
-            slab(s, vp);
-            if (s + 1 < n_st) slab(s + 1, vq);
-        }
-        // epilogue: accumulator register i of a lane = unit (i & 3) + 8 (i >> 2) + 4 h of the 32-unit tile, row fl
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const int64_t gc = col0 + wc * 64 + ct * 32 + fl;
-            if (gc >= a.N) continue;
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int i4 = 0; i4 < 4; ++i4) {
-                    const int row = rb * TBM + wr * 64 + rt * 32 + 8 * i4 + 4 * h;
-                    float v[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float t = acc[rt][ct][i4 * 4 + e];
-                        if (row + e < a.units) {
-                            if (a.bias) t += a.bias[row + e];
-                            if (a.relu) t = t <= 0.f ? 0.f : t;  // (not fmaxf: a NaN stays a NaN, ssp_dense_forward's rule)
-                            if (a.scale || a.offset) t = __builtin_fmaf(a.scale ? a.scale[row + e] : 1.f, t, a.offset ? a.offset[row + e] : 0.f);
-                        }
-                        v[e] = t;
-                    }
-                    float* y = a.Y + gc * a.units + row;
-                    if (vst && row + 3 < a.units) {
-                        *reinterpret_cast<float4*>(y) = make_float4(v[0], v[1], v[2], v[3]);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (row + e < a.units) y[e] = v[e];
-                    }
-                }
-        }
+        f32x16 acc[2][2];
+        g128_product(
+            reinterpret_cast<float*>(smem), n_kc * taps, tid,
+            [&](float4(&v)[4]) {
+                g128_load(rw, wstride, sw.j * d, d, sw.kc * TBK, sw.j < taps, tid, v);
+                sw.next(n_kc);
+            },
+            [&](float4(&v)[4]) {
+                g128_load(rx, d, sx.j * xshift, d, sx.kc * TBK, sx.j < taps, tid, v);
+                sx.next(n_kc);
+            },
+            acc);
+        g128_epilogue(acc, a.Y, a.N, a.units, col0, rb, tid, [=](int unit, float t) {
+            t = g128_bias_relu(t, bias, relu, unit);  // (ssp_dense_forward's rule)
+            if (affine) t = __builtin_fmaf(scale ? scale[unit] : 1.f, t, offset ? offset[unit] : 0.f);
+            return t;
+        });
     }
 }
 
@@ -249,7 +136,7 @@ static int tdnn_launch(const TdnnArgs& a, hipStream_t s) {
     if (a.N <= 0) return SSP_OK;
     const int64_t grid = (a.N + TBN - 1) / TBN;
     if (grid > INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "tdnn: too many rows for one launch");
-    constexpr size_t lds = (size_t)4 * (TBK / 8) * 2 * TPL * sizeof(float);  // two slabs of two operand images: 66 KB
+    constexpr size_t lds = G128_LDS;
     SSP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tdnn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(tdnn_kernel, dim3((unsigned)grid), dim3(256), lds, s, a);
     SSP_HIP(hipGetLastError());

@@ -38,7 +38,7 @@ SLACK = 1.01
 
 # ------------------------------------------------------------------------------------------------- which kernel answers
 def kernel_of(d_in):
-    """ssp_dense_forward's choice.  csrc/dense.hip:203 (`d_in <= 256 && !getenv("SSP_DENSE_NO_REG")`: launch_dense_reg, else
+    """ssp_dense_forward's choice.  csrc/dense.hip:82 (`d_in <= 256 && !getenv("SSP_DENSE_NO_REG")`: launch_dense_reg, else
     dense_kernel) and csrc/cosine.hip:834 (nq = d_in <= 64 ? 8 : d_in <= 128 ? 16 : d_in <= 192 ? 24 : 32)."""
     if d_in > 256:
         return ("tiled",)
@@ -46,7 +46,7 @@ def kernel_of(d_in):
 
 
 CH_W, CH_MAXL = 256, 8      # csrc/dnn_chain.hip:27, :29
-DBK = 32                    # csrc/dense.hip:20: the k-slab of dense_kernel
+DBK = 32                    # csrc/dense.hip:18: the k-slab of dense_kernel
 
 
 def chain_from(dims):
@@ -60,7 +60,7 @@ def chain_from(dims):
 
 
 def n_kc(d_in):
-    """k-slabs of dense_kernel (csrc/dense.hip:88)"""
+    """k-slabs of dense_kernel (csrc/dense.hip:36)"""
     return (d_in + DBK - 1) // DBK
 
 
