@@ -49,6 +49,16 @@ def _as_samples(x, name):
     return _as_f32(x, name) + (False,)
 
 
+def _as_frames(feats, D, frame_seg=None):
+    """_as_f32 of a (frames, D) feature matrix which, given ``frame_seg``, has a row for every frame of it"""
+    keep, ptr, where = _as_f32(feats, "feats")
+    if keep.ndim != 2 or keep.shape[1] != D:
+        raise ValueError("feats must be (frames, %d)" % D)
+    if frame_seg is not None and keep.shape[0] < frame_seg.total:
+        raise ValueError("feats has fewer rows than the frame segments cover")
+    return keep, ptr, where
+
+
 def _current_raw_stream(device: int) -> int:
     """torch's current hipStream_t on ``device`` as an integer (0 = the default stream).  Every device-pointer call asks, so the short
     way is taken where torch has it: no Stream object is built."""
@@ -59,16 +69,72 @@ def _current_raw_stream(device: int) -> int:
         return int(torch.cuda.current_stream(device).cuda_stream)
 
 
-class Context:
+def _raw_ptr(x, where):
+    # the address of an array on the side ``where`` names; None (an output nobody asked for) stays None: NULL for the library
+    if x is None:
+        return None
+    return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
+
+
+def _result(timing, ms, **arrays):
+    """the dict an entry point returns: the named values in the order given, those that are None (not asked for) left out, and
+    "kernel_ms" when ``timing`` is set"""
+    res = {k: v for k, v in arrays.items() if v is not None}
+    if timing:
+        res["kernel_ms"] = ms
+    return res
+
+
+def _new_handle(fn, *args):
+    """a handle made by a create call, which takes the address of the handle last; the return code is checked first"""
+    h = C.c_void_p()
+    _lib.check(fn(*args, C.byref(h)))
+    return h
+
+
+def _read_int(ctype, fn, *args):
+    """the integer a getter of the library writes through its last argument"""
+    n = ctype(0)
+    _lib.check(fn(*args, C.byref(n)))
+    return n.value
+
+
+class _Handle:
+    """What every object over a library handle shares: ``ctx``, ``_lib``, ``_h`` and the handle's life.  A class names its destroy symbol
+    in ``_DESTROY`` and makes ``_h`` with ``_create``.  ``close`` may be called twice, on an object whose __init__ raised, and after the
+    context has gone (the object holds the library itself)."""
+
+    _DESTROY = ""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self._lib = ctx._lib
+
+    def _create(self, fn, *args):
+        self._h = _new_handle(fn, *args)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """One HIP device + one stream (ssp_ctx).  stream=None: the library owns a stream; an int is a borrowed
     hipStream_t (e.g. torch.cuda.current_stream().cuda_stream; 0 = the HIP default stream).  Device-pointer calls are ordered
     against torch's current stream whichever stream the context runs on (_ordered)."""
 
+    _DESTROY = "ssp_ctx_destroy"
+
     def __init__(self, device: int = 0, stream: Optional[int] = None):
         self._lib = _lib.load()
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_ctx_create(int(device), C.c_void_p(stream or 0), 0 if stream is None else 1, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_ctx_create, int(device), C.c_void_p(stream or 0), 0 if stream is None else 1)
         self.device = int(device)
         self.stream = stream
 
@@ -119,6 +185,15 @@ class Context:
                 else:
                     _lib.check(self._lib.ssp_ctx_signal_stream(self._h, ts))
 
+    def _run(self, fn, where, timing, *args):
+        """THE call of an entry point that takes ``float* kernel_ms`` last: inside _ordered, with that argument NULL unless ``timing`` is
+        set, the return code checked before _ordered ends (its ``finally`` signals the stream for a failed call too).  -> the kernel
+        milliseconds (0.0 without timing).  Everything ``args`` points into is a local of the caller, alive until this returns."""
+        ms = C.c_float(0.0)
+        with self._ordered(where):
+            _lib.check(fn(*args, C.byref(ms) if timing else None))
+        return ms.value
+
     # ---- collectives (include/ssp.h: ssp_comm_*): one process and one Context per GPU
     @staticmethod
     def comm_unique_id() -> bytes:
@@ -160,17 +235,6 @@ class Context:
             _lib.check(self._lib.ssp_allreduce_sum(self._h, C.c_void_p(t.data_ptr()), C.c_size_t(t.numel()), int(t.dtype == torch.float64)))
         return t
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _empty(self, shape, where, dtype="float32"):
         if where == _lib.DEVICE:
             import torch
@@ -188,21 +252,20 @@ def default_context(device: int = 0, torch_stream: bool = False) -> Context:
     return _default_ctx[key]
 
 
-class Segments:
+class Segments(_Handle):
     """Per-utterance offsets (ssp_segments): int64[n+1], uploaded once."""
 
+    _DESTROY = "ssp_segments_destroy"
+
     def __init__(self, ctx: Context, offsets=None, _handle=None):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         if _handle is not None:
             self._h = _handle
         else:
             off = np.ascontiguousarray(offsets, dtype=np.int64)
             if off.ndim != 1 or off.size < 1:
                 raise ValueError("offsets must be a 1-D int64 array of length n+1")
-            h = C.c_void_p()
-            _lib.check(self._lib.ssp_segments_create(ctx._h, off.ctypes.data_as(C.POINTER(C.c_int64)), off.size - 1, C.byref(h)))
-            self._h = h
+            self._create(self._lib.ssp_segments_create, ctx._h, off.ctypes.data_as(C.POINTER(C.c_int64)), off.size - 1)
         n, tot = C.c_int64(), C.c_int64()
         _lib.check(self._lib.ssp_segments_count(self._h, C.byref(n), C.byref(tot)))
         self.n = n.value
@@ -220,17 +283,6 @@ class Segments:
     def total(self) -> int:
         return int(self.offsets[-1])
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_segments_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _cfg_struct(cfg: MfccConfig) -> _lib.ssp_mfcc_cfg:
     s = _lib.ssp_mfcc_cfg()
@@ -239,12 +291,13 @@ def _cfg_struct(cfg: MfccConfig) -> _lib.ssp_mfcc_cfg:
     return s
 
 
-class MfccPlan:
+class MfccPlan(_Handle):
     """Fused MFCC (+delta, +CMVN) pass for one dialect (ssp_mfcc_plan)."""
 
+    _DESTROY = "ssp_mfcc_plan_destroy"
+
     def __init__(self, ctx: Context, tables: MfccTables):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         self.cfg = tables.cfg
         nb = self.cfg.n_fft // 2 + 1
         w = np.ascontiguousarray(tables.window, dtype=np.float32)
@@ -253,9 +306,7 @@ class MfccPlan:
         if w.shape != (self.cfg.win_len,) or fb.shape != (self.cfg.n_filt, nb) or dct.shape != (self.cfg.n_ceps, self.cfg.n_filt):
             raise ValueError("table shapes do not match the cfg")
         self._cs = _cfg_struct(self.cfg)
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_mfcc_plan_create(ctx._h, C.byref(self._cs), w.ctypes.data, fb.ctypes.data, dct.ctypes.data, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_mfcc_plan_create, ctx._h, C.byref(self._cs), w.ctypes.data, fb.ctypes.data, dct.ctypes.data)
 
     @property
     def d_out(self) -> int:
@@ -267,14 +318,10 @@ class MfccPlan:
         return self
 
     def num_frames(self, n_samples: int) -> int:
-        out = C.c_int64()
-        _lib.check(self._lib.ssp_mfcc_num_frames(C.byref(self._cs), int(n_samples), C.byref(out)))
-        return out.value
+        return _read_int(C.c_int64, self._lib.ssp_mfcc_num_frames, C.byref(self._cs), int(n_samples))
 
     def frame_segments(self, sample_seg: Segments) -> Segments:
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_mfcc_frame_segments(self._h, sample_seg._h, C.byref(h)))
-        return Segments(self.ctx, _handle=h)
+        return Segments(self.ctx, _handle=_new_handle(self._lib.ssp_mfcc_frame_segments, self._h, sample_seg._h))
 
     def run(self, samples, sample_seg: Segments, frame_seg: Optional[Segments] = None, out=None, variant: int = 0,
             timing: bool = False):
@@ -293,22 +340,9 @@ class MfccPlan:
         okeep, optr, owhere = _as_f32(out, "out")
         if owhere != where or okeep is not out:
             raise ValueError("out must be a contiguous float32 array of the same kind as samples")
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            fn = self._lib.ssp_mfcc_run_i16 if is_i16 else self._lib.ssp_mfcc_run
-            _lib.check(fn(self._h, sample_seg._h, frame_seg._h, ptr, optr, where, int(variant), C.byref(ms) if timing else None))
-        return (out, ms.value) if timing else out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_mfcc_plan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        fn = self._lib.ssp_mfcc_run_i16 if is_i16 else self._lib.ssp_mfcc_run
+        ms = self.ctx._run(fn, where, timing, self._h, sample_seg._h, frame_seg._h, ptr, optr, where, int(variant))
+        return (out, ms) if timing else out
 
 
 def flatten_signals(signals):
@@ -366,12 +400,9 @@ def mfcc_run_list(plan: "MfccPlan", signals, out_dtype=np.float64, timing: bool 
     seg = Segments.from_lengths(plan.ctx, [a.shape[0] for a in keep])
     fseg = plan.frame_segments(seg)
     out = np.empty((fseg.total, plan.d_out), dtype=out_dtype)
-    ms = C.c_float(0.0)
-    with plan.ctx._ordered(_lib.HOST):
-        _lib.check(plan._lib.ssp_mfcc_run_list(plan._h, seg._h, fseg._h, table.ctypes.data if table.size else None, typ, out.ctypes.data,
-                                               1 if out_dtype == np.float64 else 0, 0, C.byref(ms) if timing else None))
-    del keep   # (held until the call has returned)
-    return (out, fseg, ms.value) if timing else (out, fseg)
+    ms = plan.ctx._run(plan._lib.ssp_mfcc_run_list, _lib.HOST, timing, plan._h, seg._h, fseg._h, table.ctypes.data if table.size else None, typ,
+                       out.ctypes.data, 1 if out_dtype == np.float64 else 0, 0)   # (keep owns what the table points into)
+    return (out, fseg, ms) if timing else (out, fseg)
 
 
 def pinned_empty(shape, dtype=np.float32):
@@ -393,9 +424,7 @@ def enframe(ctx: Context, samples, frame_size: int, step: int, window):
     if w.shape != (frame_size,):
         raise ValueError("window must have frame_size taps")
     out = ctx._empty((frame_size, n_frames), where)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_enframe(ctx._h, ptr, n, int(frame_size), int(step), w.ctypes.data, optr, where, None))
+    ctx._run(ctx._lib.ssp_enframe, where, False, ctx._h, ptr, n, int(frame_size), int(step), w.ctypes.data, _raw_ptr(out, where), where)
     return out
 
 
@@ -409,10 +438,8 @@ def cepstrum(ctx: Context, X, fbank, dct, log_mode: int, floor_mode: int, eps: f
     if fb.ndim != 2 or fb.shape[1] != keep.shape[1] or dc.shape != (dc.shape[0], fb.shape[0]):
         raise ValueError("fbank must be (n_filt, bins) and dct (n_ceps, n_filt)")
     out = ctx._empty((int(keep.shape[0]), dc.shape[0]), where)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_cepstrum(ctx._h, ptr, int(keep.shape[0]), int(keep.shape[1]), fb.ctypes.data, fb.shape[0], dc.ctypes.data,
-                                         dc.shape[0], int(log_mode), int(floor_mode), float(eps), optr, where, None))
+    ctx._run(ctx._lib.ssp_cepstrum, where, False, ctx._h, ptr, int(keep.shape[0]), int(keep.shape[1]), fb.ctypes.data, fb.shape[0],
+             dc.ctypes.data, dc.shape[0], int(log_mode), int(floor_mode), float(eps), _raw_ptr(out, where), where)
     return out
 
 
@@ -422,9 +449,8 @@ def spectrum_abs(ctx: Context, reim, n_bins: int, scale: float = 1.0, power: int
     if keep.ndim != 2 or keep.shape[1] != 2 * n_bins:
         raise ValueError("reim must be (rows, 2 * n_bins)")
     out = ctx._empty((int(keep.shape[0]), int(n_bins)), where)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_spectrum_abs(ctx._h, ptr, int(keep.shape[0]), int(n_bins), float(scale), int(power), optr, where, None))
+    ctx._run(ctx._lib.ssp_spectrum_abs, where, False, ctx._h, ptr, int(keep.shape[0]), int(n_bins), float(scale), int(power), _raw_ptr(out, where),
+             where)
     return out
 
 
@@ -433,11 +459,8 @@ def delta_features(ctx: Context, feats, frame_seg: Segments, N: int = 2, timing:
     if keep.ndim != 2:
         raise ValueError("feats must be (frames, dim)")
     out = ctx._empty(tuple(keep.shape), where)
-    ms = C.c_float(0.0)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_delta(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), int(N), optr, where, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_delta, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), int(N), _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
 def cmvn_features(ctx: Context, feats, frame_seg: Segments, timing: bool = False):
@@ -445,11 +468,8 @@ def cmvn_features(ctx: Context, feats, frame_seg: Segments, timing: bool = False
     if keep.ndim != 2:
         raise ValueError("feats must be (frames, dim)")
     out = ctx._empty(tuple(keep.shape), where)
-    ms = C.c_float(0.0)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_cmvn(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), optr, where, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_cmvn, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
 def featnorm_sliding(ctx: Context, feats, frame_seg: Segments, window: int = 300, mode: int = 1, timing: bool = False):
@@ -463,11 +483,9 @@ def featnorm_sliding(ctx: Context, feats, frame_seg: Segments, window: int = 300
     if int(keep.shape[0]) < frame_seg.total:
         raise ValueError("feats has fewer rows than the segment table")
     out = ctx._empty(tuple(keep.shape), where)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_featnorm_sliding(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), int(window), int(mode), _raw_ptr(out, where),
-                                                 where, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_featnorm_sliding, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), int(window), int(mode),
+                  _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
 def featnorm_table(window: int) -> np.ndarray:
@@ -495,14 +513,11 @@ def select_frames(ctx: Context, feats, frame_seg: Segments, mask, timing: bool =
     rows = int(frame_seg.offsets[-1] - frame_seg.offsets[0])
     out = ctx._empty((rows, int(keep.shape[1])), where)
     counts = np.zeros(frame_seg.n, dtype=np.int64)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_select_frames(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), mptr, _raw_ptr(out, where),
-                                              counts.ctypes.data_as(C.POINTER(C.c_int64)), where, C.byref(ms) if timing else None))
-    del mk
+    ms = ctx._run(ctx._lib.ssp_select_frames, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), mptr, _raw_ptr(out, where),
+                  counts.ctypes.data_as(C.POINTER(C.c_int64)), where)
     kept = out[:int(counts.sum())]
     seg = Segments.from_lengths(ctx, counts)
-    return (kept, seg, counts, ms.value) if timing else (kept, seg, counts)
+    return (kept, seg, counts, ms) if timing else (kept, seg, counts)
 
 
 def plp_post(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_order: int = 13, rasta: bool = True, lift: float = 0.6,
@@ -513,12 +528,9 @@ def plp_post(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp_ord
     if keep.ndim != 2:
         raise ValueError("logspec must be (frames, bands)")
     out = ctx._empty((int(keep.shape[0]), int(plp_order)), where)
-    ms = C.c_float(0.0)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_plp_post(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), float(fmax_hz), int(plp_order), int(bool(rasta)),
-                                         float(lift), optr, where, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_plp_post, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), float(fmax_hz), int(plp_order),
+                  int(bool(rasta)), float(lift), _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
 def plp_feature_columns(plp_order: int, left_dim: int = 0, delta_order: int = 0):
@@ -562,30 +574,19 @@ def plp_features(ctx: Context, logspec, frame_seg: Segments, fmax_hz: float, plp
     elif tuple(out.shape) != (F, D) or _is_torch(out) != (where == _lib.DEVICE) or str(out.dtype).split(".")[-1] != out_dtype.name \
             or not (out.is_contiguous() if _is_torch(out) else out.flags.c_contiguous):
         raise ValueError("out must be a contiguous (%d, %d) %s array of the same kind as logspec" % (F, D, out_dtype.name))
-    ms = C.c_float(0.0)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_plp_features(ctx._h, ptr, frame_seg._h, int(keep.shape[1]), float(fmax_hz), int(plp_order), int(bool(rasta)),
-                                             float(lift), lptr, left_dim, int(delta_order), int(bool(scale)), optr,
-                                             1 if out_dtype == np.float64 else 0, where, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_plp_features, where, timing, ctx._h, ptr, frame_seg._h, int(keep.shape[1]), float(fmax_hz), int(plp_order),
+                  int(bool(rasta)), float(lift), lptr, left_dim, int(delta_order), int(bool(scale)), _raw_ptr(out, where),
+                  1 if out_dtype == np.float64 else 0, where)
+    return (out, ms) if timing else out
 
 
 def vad_num_frames(n_samples: int, step: int = 128) -> int:
     """math.ceil(n / step) — VAD.py:37 (no GPU)."""
-    out = C.c_int64()
-    _lib.check(_lib.load().ssp_vad_num_frames(int(n_samples), int(step), C.byref(out)))
-    return out.value
+    return _read_int(C.c_int64, _lib.load().ssp_vad_num_frames, int(n_samples), int(step))
 
 
 def vad_frame_segments(ctx: Context, sample_seg: Segments, step: int = 128) -> Segments:
-    h = C.c_void_p()
-    _lib.check(ctx._lib.ssp_vad_frame_segments(ctx._h, sample_seg._h, int(step), C.byref(h)))
-    return Segments(ctx, _handle=h)
-
-
-def _raw_ptr(x, where):
-    return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
+    return Segments(ctx, _handle=_new_handle(ctx._lib.ssp_vad_frame_segments, ctx._h, sample_seg._h, int(step)))
 
 
 def vad_features(ctx: Context, samples, sample_seg: Segments, frame_seg: Optional[Segments] = None, frame_size: int = 256, step: int = 128,
@@ -601,12 +602,10 @@ def vad_features(ctx: Context, samples, sample_seg: Segments, frame_seg: Optiona
     if int(np.prod(keep.shape)) < sample_seg.total:
         raise ValueError("samples shorter than the segment table")
     zcr, power, ent = (ctx._empty((frame_seg.total,), where) for _ in range(3))
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_vad_features(ctx._h, ptr, 1 if is_i16 else 0, sample_seg._h, frame_seg._h, int(frame_size), int(step),
-                                             1 if normalize else 0, 0 if gate_zcr else _lib.VAD_ZCR_UNGATED, _raw_ptr(zcr, where), _raw_ptr(power, where), _raw_ptr(ent, where),
-                                             where, C.byref(ms) if timing else None))
-    return (zcr, power, ent, frame_seg, ms.value) if timing else (zcr, power, ent, frame_seg)
+    ms = ctx._run(ctx._lib.ssp_vad_features, where, timing, ctx._h, ptr, 1 if is_i16 else 0, sample_seg._h, frame_seg._h, int(frame_size),
+                  int(step), 1 if normalize else 0, 0 if gate_zcr else _lib.VAD_ZCR_UNGATED, _raw_ptr(zcr, where), _raw_ptr(power, where),
+                  _raw_ptr(ent, where), where)
+    return (zcr, power, ent, frame_seg, ms) if timing else (zcr, power, ent, frame_seg)
 
 
 def vad_detect(ctx: Context, zcr, power_or_entropy, frame_seg: Segments, mode: int = 0, zcr_gate: float = 35.0, ampl: float = 0.3,
@@ -625,13 +624,9 @@ def vad_detect(ctx: Context, zcr, power_or_entropy, frame_seg: Segments, mode: i
         raise ValueError("fewer values than frame_seg has frames")
     mask = ctx._empty((frame_seg.total,), where, "uint8")
     count = ctx._empty((frame_seg.n,), where, "int32")
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_vad_detect(ctx._h, zptr, pptr, frame_seg._h, int(mode), float(zcr_gate), float(ampl), float(amph),
-                                           int(min_len), _raw_ptr(mask, where), _raw_ptr(count, where), where,
-                                           C.byref(ms) if timing else None))
-    del zk, pk
-    return (mask, count, ms.value) if timing else (mask, count)
+    ms = ctx._run(ctx._lib.ssp_vad_detect, where, timing, ctx._h, zptr, pptr, frame_seg._h, int(mode), float(zcr_gate), float(ampl), float(amph),
+                  int(min_len), _raw_ptr(mask, where), _raw_ptr(count, where), where)
+    return (mask, count, ms) if timing else (mask, count)
 
 
 def _as_u8(x, name):
@@ -674,13 +669,10 @@ def vad_sweep(ctx: Context, zcr, power_or_entropy, labels, frame_seg: Segments, 
     g, lo, hi = (np.ascontiguousarray(v, dtype=np.float32).reshape(-1) for v in (g, lo, hi))
     n_par = int(lo.shape[0])
     counts = ctx._empty((n_par, frame_seg.n, 3), where, "int32")
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_vad_sweep(ctx._h, zptr, pptr, lptr, frame_seg._h, int(mode), n_par, g.ctypes.data if mode == 0 else None,
-                                          lo.ctypes.data, hi.ctypes.data if mode == 0 else None, int(min_len), _raw_ptr(counts, where), where,
-                                          C.byref(ms) if timing else None))
-    del zk, pk, lk
-    return (counts, ms.value) if timing else counts
+    ms = ctx._run(ctx._lib.ssp_vad_sweep, where, timing, ctx._h, zptr, pptr, lptr, frame_seg._h, int(mode), n_par,
+                  g.ctypes.data if mode == 0 else None, lo.ctypes.data, hi.ctypes.data if mode == 0 else None, int(min_len),
+                  _raw_ptr(counts, where), where)
+    return (counts, ms) if timing else counts
 
 
 def gmm_em_stats(ctx: "Context", weights, means, covars, feats, timing: bool = False) -> dict:
@@ -693,22 +685,14 @@ def gmm_em_stats(ctx: "Context", weights, means, covars, feats, timing: bool = F
     if w.ndim != 1 or mu.ndim != 2 or mu.shape != cv.shape or mu.shape[0] != w.shape[0]:
         raise ValueError("expected weights (K,), means (K,D), covars (K,D)")
     K, D = mu.shape
-    keep, ptr, where = _as_f32(feats, "feats")
-    if keep.ndim != 2 or keep.shape[1] != D:
-        raise ValueError("feats must be (frames, %d)" % D)
+    keep, ptr, where = _as_frames(feats, D)
     nk = np.empty(K, dtype=np.float64)
     sx = np.empty((K, D), dtype=np.float64)
     sxx = np.empty((K, D), dtype=np.float64)
     ll = C.c_double(0.0)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_gmm_em_stats(ctx._h, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
-                                              nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data, C.byref(ll), where,
-                                              C.byref(ms) if timing else None))
-    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll.value}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_gmm_em_stats, where, timing, ctx._h, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
+                  nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data, C.byref(ll), where)
+    return _result(timing, ms, nk=nk, sx=sx, sxx=sxx, loglik_sum=ll.value)
 
 
 def gmm_em_stats_batch(ctx: "Context", weights, means, covars, feats, row_off, n_frames, timing: bool = False) -> dict:
@@ -726,22 +710,14 @@ def gmm_em_stats_batch(ctx: "Context", weights, means, covars, feats, row_off, n
     cnt = np.ascontiguousarray(n_frames, dtype=np.int64)
     if off.shape != (M,) or cnt.shape != (M,):
         raise ValueError("row_off and n_frames must be (%d,)" % M)
-    keep, ptr, where = _as_f32(feats, "feats")
-    if keep.ndim != 2 or keep.shape[1] != D:
-        raise ValueError("feats must be (frames, %d)" % D)
+    keep, ptr, where = _as_frames(feats, D)
     nk = np.empty((M, K), dtype=np.float64)
     sx = np.empty((M, K, D), dtype=np.float64)
     sxx = np.empty((M, K, D), dtype=np.float64)
     ll = np.empty(M, dtype=np.float64)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_gmm_em_stats_batch(ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
-                                                    off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
-                                                    ll.ctypes.data, where, C.byref(ms) if timing else None))
-    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_gmm_em_stats_batch, where, timing, ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr,
+                  int(keep.shape[0]), off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data, ll.ctypes.data, where)
+    return _result(timing, ms, nk=nk, sx=sx, sxx=sxx, loglik_sum=ll)
 
 
 def gmm_em_stats_shared(ctx: "Context", weights, means, covars, feats, row_off, n_frames, timing: bool = False) -> dict:
@@ -759,22 +735,14 @@ def gmm_em_stats_shared(ctx: "Context", weights, means, covars, feats, row_off, 
     if off.ndim != 1 or off.shape != cnt.shape:
         raise ValueError("row_off and n_frames must be (M,)")
     M = int(off.shape[0])
-    keep, ptr, where = _as_f32(feats, "feats")
-    if keep.ndim != 2 or keep.shape[1] != D:
-        raise ValueError("feats must be (frames, %d)" % D)
+    keep, ptr, where = _as_frames(feats, D)
     nk = np.empty((M, K), dtype=np.float64)
     sx = np.empty((M, K, D), dtype=np.float64)
     sxx = np.empty((M, K, D), dtype=np.float64)
     ll = np.empty(M, dtype=np.float64)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_gmm_em_stats_shared(ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr, int(keep.shape[0]),
-                                                     off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
-                                                     ll.ctypes.data, where, C.byref(ms) if timing else None))
-    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_gmm_em_stats_shared, where, timing, ctx._h, M, K, D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, ptr,
+                  int(keep.shape[0]), off.ctypes.data, cnt.ctypes.data, nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data, ll.ctypes.data, where)
+    return _result(timing, ms, nk=nk, sx=sx, sxx=sxx, loglik_sum=ll)
 
 
 GMM_FULL_MAX_D = 64  # ssp_gmm_full_em_stats / ssp_gmm_full_pack's feature dimension (include/ssp.h)
@@ -796,31 +764,25 @@ def gmm_full_em_stats(ctx: "Context", weights, means, prec_chol, feats, shift=No
         sh = np.ascontiguousarray(shift, dtype=np.float64)
         if sh.shape != (D,):
             raise ValueError("shift must be (%d,)" % D)
-    keep, ptr, where = _as_f32(feats, "feats")
-    if keep.ndim != 2 or keep.shape[1] != D:
-        raise ValueError("feats must be (frames, %d)" % D)
+    keep, ptr, where = _as_frames(feats, D)
     nk = np.empty(K, dtype=np.float64)
     sx = np.empty((K, D), dtype=np.float64)
     sxx = np.empty((K, D, D), dtype=np.float64)
     ll = C.c_double(0.0)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_gmm_full_em_stats(ctx._h, K, D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
-                                                   sh.ctypes.data if sh is not None else None, ptr, int(keep.shape[0]), nk.ctypes.data,
-                                                   sx.ctypes.data, sxx.ctypes.data, C.byref(ll), where, C.byref(ms) if timing else None))
-    res = {"nk": nk, "sx": sx, "sxx": sxx, "loglik_sum": ll.value}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_gmm_full_em_stats, where, timing, ctx._h, K, D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
+                  _raw_ptr(sh, _lib.HOST), ptr, int(keep.shape[0]), nk.ctypes.data, sx.ctypes.data, sxx.ctypes.data,
+                  C.byref(ll), where)
+    return _result(timing, ms, nk=nk, sx=sx, sxx=sxx, loglik_sum=ll.value)
 
 
-class GmmFullScorer:
+class GmmFullScorer(_Handle):
     """Packed full-covariance GMMs (ssp_gmm_full).  weights (M,K), means (M,K,D), prec_chol (M,K,D,D) float64 — sklearn's
     precisions_cholesky_ of covariance_type='full', upper triangular.  has_ubm: model 0 is the UBM; scores / argmax as GmmScorer's."""
 
+    _DESTROY = "ssp_gmm_full_destroy"
+
     def __init__(self, ctx: Context, weights, means, prec_chol, has_ubm: bool = True):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         w = np.ascontiguousarray(weights, dtype=np.float64)
         mu = np.ascontiguousarray(means, dtype=np.float64)
         pc = np.ascontiguousarray(prec_chol, dtype=np.float64)
@@ -828,10 +790,8 @@ class GmmFullScorer:
             raise ValueError("expected weights (M,K), means (M,K,D), prec_chol (M,K,D,D)")
         self.n_models, self.K, self.D = mu.shape
         self.has_ubm = bool(has_ubm)
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_gmm_full_pack(ctx._h, self.n_models, self.K, self.D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
-                                                1 if has_ubm else 0, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_gmm_full_pack, ctx._h, self.n_models, self.K, self.D, w.ctypes.data, mu.ctypes.data, pc.ctypes.data,
+                     1 if has_ubm else 0)
 
     @classmethod
     def from_sklearn(cls, ctx: Context, models: Sequence, ubm=None) -> "GmmFullScorer":
@@ -847,33 +807,14 @@ class GmmFullScorer:
     def score(self, feats, frame_seg: Segments, loglik: bool = False, scores: bool = True, argmax: bool = True, timing: bool = False) -> dict:
         """Returns a dict with the requested arrays: loglik (M, F) per-frame log-likelihood per model (= score_samples), scores (U, M)
         mean log-likelihood (= GaussianMixture.score), argmax (U,) int32 over speaker models of score - score_ubm."""
-        keep, ptr, where = _as_f32(feats, "feats")
-        if keep.ndim != 2 or keep.shape[1] != self.D:
-            raise ValueError("feats must be (frames, %d)" % self.D)
-        if keep.shape[0] < frame_seg.total:
-            raise ValueError("feats has fewer rows than the frame segments cover")
+        keep, ptr, where = _as_frames(feats, self.D, frame_seg)
         F, U = frame_seg.total, frame_seg.n
         ll = self.ctx._empty((self.n_models, F), where) if loglik else None
         sc = self.ctx._empty((U, self.n_models), where) if scores else None
         am = self.ctx._empty((U,), where, "int32") if argmax else None
-
-        def p(x):
-            if x is None:
-                return None
-            return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_gmm_full_score(self._h, ptr, frame_seg._h, p(ll), p(sc), p(am), where, C.byref(ms) if timing else None))
-        res = {}
-        if loglik:
-            res["loglik"] = ll
-        if scores:
-            res["scores"] = sc
-        if argmax:
-            res["argmax"] = am
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
+        ms = self.ctx._run(self._lib.ssp_gmm_full_score, where, timing, self._h, ptr, frame_seg._h, _raw_ptr(ll, where), _raw_ptr(sc, where),
+                           _raw_ptr(am, where), where)
+        return _result(timing, ms, loglik=ll, scores=sc, argmax=am)
 
     def score_list(self, feats_list, timing: bool = False) -> dict:
         """score() on a list of (T_j, D) feature matrices, stacked on the host (not the hot path): scores (U, M) and argmax (U,)."""
@@ -884,17 +825,6 @@ class GmmFullScorer:
         fseg = Segments.from_lengths(self.ctx, [a.shape[0] for a in mats])
         X = np.ascontiguousarray(np.concatenate(mats)) if mats else np.zeros((0, self.D), np.float32)
         return self.score(X, fseg, loglik=False, scores=True, argmax=True, timing=timing)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_gmm_full_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 KMEANSPP_MAX_D = 64  # ssp_kmeanspp_seed's feature dimension (include/ssp.h)
@@ -942,27 +872,19 @@ def kmeanspp_seeds(ctx: "Context", feats, K, first, u, row_off=None, n_sel=None,
             raise ValueError("sel is shorter than row_off + n_sel asks for")
     rows = np.empty((P, max(K, 0)), dtype=np.int64)
     cen = np.empty((P, max(K, 0), D), dtype=np.float64) if centres else None
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_kmeanspp_seed(ctx._h, P, K, D, ptr, n_rows, where, off.ctypes.data, cnt.ctypes.data,
-                                              sl.ctypes.data if sl is not None else None, fi.ctypes.data, uu.ctypes.data if uu.size else None,
-                                              rows.ctypes.data, cen.ctypes.data if centres else None, C.byref(ms) if timing else None))
-    del keep
-    res = {"rows": rows}
-    if centres:
-        res["centres"] = cen
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_kmeanspp_seed, where, timing, ctx._h, P, K, D, ptr, n_rows, where, off.ctypes.data, cnt.ctypes.data,
+                  _raw_ptr(sl, _lib.HOST), fi.ctypes.data, uu.ctypes.data if uu.size else None, rows.ctypes.data, _raw_ptr(cen, _lib.HOST))
+    return _result(timing, ms, rows=rows, centres=cen)
 
 
-class GmmScorer:
+class GmmScorer(_Handle):
     """Packed diagonal GMMs (ssp_gmm).  weights (M,K), means (M,K,D), covars (M,K,D) float64.
     has_ubm: model 0 is the UBM (GMM_UBM.py:169-170); scores/argmax are then taken against it."""
 
+    _DESTROY = "ssp_gmm_destroy"
+
     def __init__(self, ctx: Context, weights, means, covars, has_ubm: bool = True):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         w = np.ascontiguousarray(weights, dtype=np.float64)
         mu = np.ascontiguousarray(means, dtype=np.float64)
         cv = np.ascontiguousarray(covars, dtype=np.float64)
@@ -970,10 +892,8 @@ class GmmScorer:
             raise ValueError("expected weights (M,K), means (M,K,D), covars (M,K,D)")
         self.n_models, self.K, self.D = mu.shape
         self.has_ubm = bool(has_ubm)
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_gmm_pack(ctx._h, self.n_models, self.K, self.D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data,
-                                           1 if has_ubm else 0, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_gmm_pack, ctx._h, self.n_models, self.K, self.D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data,
+                     1 if has_ubm else 0)
 
     @classmethod
     def from_sklearn(cls, ctx: Context, models: Sequence, ubm=None) -> "GmmScorer":
@@ -998,34 +918,14 @@ class GmmScorer:
         re-scoring; ``last_auto`` says what it chose (include/ssp.h, ssp_gmm_score)."""
         if precision == "auto":
             precision = 4
-        keep, ptr, where = _as_f32(feats, "feats")
-        if keep.ndim != 2 or keep.shape[1] != self.D:
-            raise ValueError("feats must be (frames, %d)" % self.D)
-        if keep.shape[0] < frame_seg.total:
-            raise ValueError("feats has fewer rows than the frame segments cover")
+        keep, ptr, where = _as_frames(feats, self.D, frame_seg)
         F, U = frame_seg.total, frame_seg.n
-        res = {}
         ll = self.ctx._empty((self.n_models, F), where) if loglik else None
         sc = self.ctx._empty((U, self.n_models), where) if scores else None
         am = self.ctx._empty((U,), where, "int32") if argmax else None
-
-        def p(x):
-            if x is None:
-                return None
-            return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_gmm_score(self._h, ptr, frame_seg._h, p(ll), p(sc), p(am), where, int(precision),
-                                                C.byref(ms) if timing else None))
-        if loglik:
-            res["loglik"] = ll
-        if scores:
-            res["scores"] = sc
-        if argmax:
-            res["argmax"] = am
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
+        ms = self.ctx._run(self._lib.ssp_gmm_score, where, timing, self._h, ptr, frame_seg._h, _raw_ptr(ll, where), _raw_ptr(sc, where),
+                           _raw_ptr(am, where), where, int(precision))
+        return _result(timing, ms, loglik=ll, scores=sc, argmax=am)
 
     def score_list(self, feats_list, precision: int = 0, timing: bool = False) -> dict:
         """score() on a list of (T_j, D) feature matrices without stacking them on the host (ssp_gmm_score_list: the rows are gathered
@@ -1040,21 +940,13 @@ class GmmScorer:
         fseg = Segments.from_lengths(self.ctx, [a.shape[0] for a in keep])
         sc = np.empty((fseg.n, self.n_models), dtype=np.float32)
         am = np.empty((fseg.n,), dtype=np.int32)
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(_lib.HOST):
-            _lib.check(self._lib.ssp_gmm_score_list(self._h, table.ctypes.data if table.size else None, typ, self.D, fseg._h,
-                                                     sc.ctypes.data, am.ctypes.data, int(precision), C.byref(ms) if timing else None))
-        del keep
-        res = {"scores": sc, "argmax": am}
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
+        ms = self.ctx._run(self._lib.ssp_gmm_score_list, _lib.HOST, timing, self._h, table.ctypes.data if table.size else None, typ, self.D,
+                           fseg._h, sc.ctypes.data, am.ctypes.data, int(precision))   # (keep owns what the table points into)
+        return _result(timing, ms, scores=sc, argmax=am)
 
     @property
     def last_rescored(self) -> int:
-        n = C.c_int32(0)
-        _lib.check(self._lib.ssp_gmm_last_rescored(self._h, C.byref(n)))
-        return n.value
+        return _read_int(C.c_int32, self._lib.ssp_gmm_last_rescored, self._h)
 
     @property
     def last_auto(self) -> dict:
@@ -1063,31 +955,21 @@ class GmmScorer:
         _lib.check(self._lib.ssp_gmm_last_auto(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(f)))
         return {"precision_used": a.value, "pilot_utterances": b.value, "pilot_listed": c.value, "predicted_cost_of_precision_1": f.value}
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_gmm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 MAP_MAX_C = 8   # ssp_gmm_map_score's largest top-C (include/ssp.h)
 MAP_MAX_D = 47  # ... and feature dimension
 
 
-class MapScorer:
+class MapScorer(_Handle):
     """Top-C fast scorer of mean-adapted GMM-UBM speaker models (ssp_gmm_map; an extension the reference does not have).
     ubm_w (K,), ubm_mu (K,D), ubm_cv (K,D), spk_means (S,K,D) float64: speaker s is the UBM with its means replaced by spk_means[s].
     Per utterance: diff[u, s] = mean_t (L_s(x_t) - L_ubm(x_t)) over the UBM's best ``top_c`` mixtures of every frame — with top_c = K the
     dense models[s].score(x) - ubm.score(x) of GMM_UBM.py:185."""
 
+    _DESTROY = "ssp_gmm_map_destroy"
+
     def __init__(self, ctx: Context, ubm_w, ubm_mu, ubm_cv, spk_means):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         w = np.ascontiguousarray(ubm_w, dtype=np.float64)
         mu = np.ascontiguousarray(ubm_mu, dtype=np.float64)
         cv = np.ascontiguousarray(ubm_cv, dtype=np.float64)
@@ -1096,10 +978,7 @@ class MapScorer:
             raise ValueError("expected ubm_w (K,), ubm_mu (K,D), ubm_cv (K,D), spk_means (S,K,D)")
         self.K, self.D = mu.shape
         self.S = int(sm.shape[0])
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_gmm_map_pack(ctx._h, self.K, self.D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, self.S, sm.ctypes.data,
-                                               C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_gmm_map_pack, ctx._h, self.K, self.D, w.ctypes.data, mu.ctypes.data, cv.ctypes.data, self.S, sm.ctypes.data)
 
     @classmethod
     def from_sklearn(cls, ctx: Context, models: Sequence, ubm) -> "MapScorer":
@@ -1121,32 +1000,15 @@ class MapScorer:
         """Returns a dict with the requested arrays: diff (U, S) float32, ubm (U,) float32 = mean_t L_ubm, argmax (U,) int32 (first index
         of the row's maximum), idx (F, top_c) int32: the selected mixtures of every frame in rank order (-1: a non-finite frame).  A
         non-finite frame or an empty utterance: a NaN diff row, NaN ubm, arg-max 0 (include/ssp.h, ssp_gmm_map_score)."""
-        keep, ptr, where = _as_f32(feats, "feats")
-        if keep.ndim != 2 or keep.shape[1] != self.D:
-            raise ValueError("feats must be (frames, %d)" % self.D)
-        if keep.shape[0] < frame_seg.total:
-            raise ValueError("feats has fewer rows than the frame segments cover")
+        keep, ptr, where = _as_frames(feats, self.D, frame_seg)
         F, U, Ck = frame_seg.total, frame_seg.n, int(top_c)
         df = self.ctx._empty((U, self.S), where) if diff else None
         ub = self.ctx._empty((U,), where) if ubm else None
         am = self.ctx._empty((U,), where, "int32") if argmax else None
         ix = self.ctx._empty((F, max(Ck, 0)), where, "int32") if idx else None
-
-        def p(x):
-            if x is None:
-                return None
-            return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_gmm_map_score(self._h, ptr, frame_seg._h, Ck, p(df), p(ub), p(am), p(ix), where,
-                                                    C.byref(ms) if timing else None))
-        res = {}
-        for name, v in (("diff", df), ("ubm", ub), ("argmax", am), ("idx", ix)):
-            if v is not None:
-                res[name] = v
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
+        ms = self.ctx._run(self._lib.ssp_gmm_map_score, where, timing, self._h, ptr, frame_seg._h, Ck, _raw_ptr(df, where), _raw_ptr(ub, where),
+                           _raw_ptr(am, where), _raw_ptr(ix, where), where)
+        return _result(timing, ms, diff=df, ubm=ub, argmax=am, idx=ix)
 
     def score_list(self, feats_list, top_c: int = 5, timing: bool = False) -> dict:
         """score() on a list of (T_j, D) feature matrices without stacking them on the host (ssp_gmm_map_score_list: GmmScorer.score_list's
@@ -1159,36 +1021,21 @@ class MapScorer:
         df = np.empty((fseg.n, self.S), dtype=np.float32)
         ub = np.empty((fseg.n,), dtype=np.float32)
         am = np.empty((fseg.n,), dtype=np.int32)
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(_lib.HOST):
-            _lib.check(self._lib.ssp_gmm_map_score_list(self._h, table.ctypes.data if table.size else None, typ, self.D, fseg._h, int(top_c),
-                                                         df.ctypes.data, ub.ctypes.data, am.ctypes.data, None, C.byref(ms) if timing else None))
-        del keep
-        res = {"diff": df, "ubm": ub, "argmax": am}
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_gmm_map_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_gmm_map_score_list, _lib.HOST, timing, self._h, table.ctypes.data if table.size else None, typ, self.D,
+                           fseg._h, int(top_c), df.ctypes.data, ub.ctypes.data, am.ctypes.data, None)   # (keep owns what the table points into)
+        return _result(timing, ms, diff=df, ubm=ub, argmax=am)
 
 
 IVECTOR_MAX_R = 256  # ssp_ivector_create's largest rank (include/ssp.h)
 IVECTOR_STAGES = ("gemm_L", "gemm_b", "cholesky", "gemm_A", "gemm_C")  # ssp_ivector_last_stages
 
 
-class IvectorExtractor:
+class IvectorExtractor(_Handle):
     """i-vector extraction and the E-step of total-variability training (ssp_ivector; an extension the reference does not have).
     ubm_mu (K,D), ubm_cv (K,D), T (K,D,R) float64.  Statistics nk (U,K), sx (U,K,D) float64 on the host, as gmm_em_stats_shared returns
     them; include/ssp.h has the definitions."""
+
+    _DESTROY = "ssp_ivector_destroy"
 
     def __init__(self, ctx: Context, ubm_mu, ubm_cv, T):
         mu = np.ascontiguousarray(ubm_mu, dtype=np.float64)
@@ -1202,11 +1049,8 @@ class IvectorExtractor:
             raise ValueError("T (K,D,R): the rank R must be at least 1")
         if self.R > IVECTOR_MAX_R:
             raise NotImplementedError("R=%d exceeds the supported rank (%d)" % (self.R, IVECTOR_MAX_R))
-        self.ctx = ctx
-        self._lib = ctx._lib
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_ivector_create(ctx._h, self.K, self.D, self.R, mu.ctypes.data, cv.ctypes.data, T.ctypes.data, C.byref(h)))
-        self._h = h
+        super().__init__(ctx)
+        self._create(self._lib.ssp_ivector_create, ctx._h, self.K, self.D, self.R, mu.ctypes.data, cv.ctypes.data, T.ctypes.data)
 
     def set_T(self, T) -> "IvectorExtractor":
         """replace T (K,D,R): P and G are packed again on the device"""
@@ -1223,9 +1067,7 @@ class IvectorExtractor:
 
     @property
     def last_slab(self) -> int:
-        n = C.c_int64(0)
-        _lib.check(self._lib.ssp_ivector_last_slab(self._h, C.byref(n)))
-        return n.value
+        return _read_int(C.c_int64, self._lib.ssp_ivector_last_slab, self._h)
 
     @property
     def last_stages(self) -> dict:
@@ -1255,19 +1097,11 @@ class IvectorExtractor:
         w = np.empty((U, self.R), dtype=np.float32)
         ld = np.empty(U, dtype=np.float32) if logdet else None
         qd = np.empty(U, dtype=np.float32) if quad else None
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.ssp_ivector_extract(self._h, nk.ctypes.data, sx.ctypes.data, U, w.ctypes.data, ld.ctypes.data if logdet else None,
-                                                 qd.ctypes.data if quad else None, C.byref(ms) if timing else None))
+        ms = self.ctx._run(self._lib.ssp_ivector_extract, _lib.HOST, timing, self._h, nk.ctypes.data, sx.ctypes.data, U, w.ctypes.data,
+                           _raw_ptr(ld, _lib.HOST), _raw_ptr(qd, _lib.HOST))
         if not (logdet or quad or timing):
             return w
-        res = {"w": w}
-        if logdet:
-            res["logdet"] = ld
-        if quad:
-            res["quad"] = qd
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
+        return _result(timing, ms, w=w, logdet=ld, quad=qd)
 
     def estep(self, nk, sx, timing: bool = False, check: bool = True) -> dict:
         """-> {"A" (K,R,R), "C" (K,D,R), "objective"} float64 [and "kernel_ms"]: the accumulators of one EM iteration under the current T"""
@@ -1276,24 +1110,9 @@ class IvectorExtractor:
         A = np.empty((self.K, self.R, self.R), dtype=np.float64)
         Cm = np.empty((self.K, self.D, self.R), dtype=np.float64)
         obj = C.c_double(0.0)
-        ms = C.c_float(0.0)
-        _lib.check(self._lib.ssp_ivector_estep(self._h, nk.ctypes.data, sx.ctypes.data, U, A.ctypes.data, Cm.ctypes.data, C.byref(obj),
-                                               C.byref(ms) if timing else None))
-        res = {"A": A, "C": Cm, "objective": obj.value}
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_ivector_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_ivector_estep, _lib.HOST, timing, self._h, nk.ctypes.data, sx.ctypes.data, U, A.ctypes.data, Cm.ctypes.data,
+                           C.byref(obj))
+        return _result(timing, ms, A=A, C=Cm, objective=obj.value)
 
 
 PLDA_MAX_Q = 256  # largest dimension of ssp_plda_stats / ssp_plda_pack (include/ssp.h)
@@ -1330,36 +1149,29 @@ def plda_stats(ctx: Context, X, labels, S: int, timing: bool = False) -> dict:
     cnt = np.zeros(max(S, 0), dtype=np.int64)
     mean = np.zeros(q, dtype=np.float64)
     sw = np.zeros((q, q), dtype=np.float64)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_plda_stats(ctx._h, ptr, lptr, N, q, S, sm.ctypes.data, cnt.ctypes.data, mean.ctypes.data, sw.ctypes.data, where,
-                                           C.byref(ms) if timing else None))
-    del keep, lab
-    res = {"sum": sm, "count": cnt, "mean": mean, "sw": sw}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_plda_stats, where, timing, ctx._h, ptr, lptr, N, q, S, sm.ctypes.data, cnt.ctypes.data, mean.ctypes.data,
+                  sw.ctypes.data, where)
+    return _result(timing, ms, sum=sm, count=cnt, mean=mean, sw=sw)
 
 
-class PldaScorer:
+class PldaScorer(_Handle):
     """Enrolled speakers of a diagonalised PLDA model packed for the log-likelihood-ratio sweep (ssp_plda; an extension the reference
     does not have).  psi (q,) float64 >= 0, enrol_mean (S, q) float64 ALREADY transformed by A (the mean of each speaker's transformed
     enrolment vectors), enrol_count (S,) >= 1.  flags: PLDA_NO_CLASS_PATH keeps the t^2 term off the class-shared path."""
 
+    _DESTROY = "ssp_plda_destroy"
+
     def __init__(self, ctx: Context, psi, enrol_mean, enrol_count, flags: int = 0):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         psi = np.ascontiguousarray(psi, dtype=np.float64)
         em = np.ascontiguousarray(enrol_mean, dtype=np.float64)
         ec = np.ascontiguousarray(enrol_count, dtype=np.int32)
         if psi.ndim != 1 or em.ndim != 2 or em.shape[1] != psi.shape[0] or ec.shape != (em.shape[0],):
             raise ValueError("expected psi (q,), enrol_mean (S, q), enrol_count (S,)")
         self.q, self.S = int(psi.shape[0]), int(em.shape[0])
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_plda_pack(ctx._h, self.q, psi.ctypes.data, self.S, em.ctypes.data, ec.ctypes.data, int(flags), C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_plda_pack, ctx._h, self.q, psi.ctypes.data, self.S, em.ctypes.data, ec.ctypes.data, int(flags))
         g, shared = C.c_int32(0), C.c_int32(0)
-        _lib.check(self._lib.ssp_plda_info(h, C.byref(g), C.byref(shared)))   # what the pack decided, from the handle
+        _lib.check(self._lib.ssp_plda_info(self._h, C.byref(g), C.byref(shared)))   # what the pack decided, from the handle
         self.n_classes, self.class_shared = g.value, bool(shared.value)
 
     def score(self, T, llr: bool = False, argmax: bool = True, maxval: bool = True, timing: bool = False) -> dict:
@@ -1373,32 +1185,9 @@ class PldaScorer:
         lr = self.ctx._empty((N, self.S), where) if llr else None
         am = self.ctx._empty((N,), where, "int32") if argmax else None
         mx = self.ctx._empty((N,), where) if maxval else None
-        ms = C.c_float(0.0)
-
-        def p(x):
-            return None if x is None else _raw_ptr(x, where)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_plda_score(self._h, ptr, N, p(lr), p(am), p(mx), where,
-                                                C.byref(ms) if timing else None))
-        del keep
-        res = {}
-        for name, v in (("argmax", am), ("max", mx), ("llr", lr)):
-            if v is not None:
-                res[name] = v
-        if timing:
-            res["kernel_ms"] = ms.value
-        return res
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_plda_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_plda_score, where, timing, self._h, ptr, N, _raw_ptr(lr, where), _raw_ptr(am, where), _raw_ptr(mx, where),
+                           where)
+        return _result(timing, ms, argmax=am, max=mx, llr=lr)
 
 
 TOPN_MAX_LINE = 65536  # longest line of ssp_topn_stats (include/ssp.h)
@@ -1441,15 +1230,8 @@ def topn_stats(ctx: Context, scores, n: int, axis: int = 1, timing: bool = False
     rows, cols = int(keep.shape[0]), int(keep.shape[1])
     lines = rows if axis == 1 else cols
     out = [ctx._empty((max(lines, 0),), where) for _ in range(3)]
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_topn_stats(ctx._h, ptr, rows, cols, ld, int(axis), int(n), *[_raw_ptr(o, where) for o in out], where,
-                                           C.byref(ms) if timing else None))
-    del keep
-    res = dict(zip(("mean", "std", "kth"), out))
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_topn_stats, where, timing, ctx._h, ptr, rows, cols, ld, int(axis), int(n), *[_raw_ptr(o, where) for o in out], where)
+    return _result(timing, ms, mean=out[0], std=out[1], kth=out[2])
 
 
 def snorm_apply(ctx: Context, scores, row_mean=None, row_std=None, col_mean=None, col_std=None, std_floor: float = 1e-6, out=True,
@@ -1477,21 +1259,9 @@ def snorm_apply(ctx: Context, scores, row_mean=None, row_std=None, col_mean=None
             raise ValueError("out must be a float32 matrix of scores' shape and kind with contiguous rows")
     am = ctx._empty((N,), where, "int32") if argmax else None
     mx = ctx._empty((N,), where) if maxval else None
-    ms = C.c_float(0.0)
-
-    def p(x):
-        return None if x is None else _raw_ptr(x, where)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_snorm_apply(ctx._h, ptr, N, S, ld, rm[1], rs[1], cm[1], cs[1], float(std_floor), zp, ldz, p(am), p(mx), where,
-                                            C.byref(ms) if timing else None))
-    del keep, rm, rs, cm, cs
-    res = {}
-    for name, v in (("argmax", am), ("max", mx), ("scores", z)):
-        if v is not None:
-            res[name] = v
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_snorm_apply, where, timing, ctx._h, ptr, N, S, ld, rm[1], rs[1], cm[1], cs[1], float(std_floor), zp, ldz,
+                  _raw_ptr(am, where), _raw_ptr(mx, where), where)
+    return _result(timing, ms, argmax=am, max=mx, scores=z)
 
 
 def det_counts(ctx: Context, scores, target, thresholds=(), timing: bool = False) -> dict:
@@ -1506,15 +1276,9 @@ def det_counts(ctx: Context, scores, target, thresholds=(), timing: bool = False
     M = int(th.shape[0])
     tar, non = np.zeros(M + 1, dtype=np.int64), np.zeros(M + 1, dtype=np.int64)
     nan, rng = np.zeros(2, dtype=np.int64), np.zeros(4, dtype=np.float32)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_det_counts(ctx._h, ptr, N, S, ld, lptr, th.ctypes.data, M, tar.ctypes.data, non.ctypes.data, nan.ctypes.data,
-                                           rng.ctypes.data, where, C.byref(ms) if timing else None))
-    del keep, lab
-    res = {"tar_hist": tar, "non_hist": non, "nan_count": nan, "range": rng, "thresholds": th}
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_det_counts, where, timing, ctx._h, ptr, N, S, ld, lptr, th.ctypes.data, M, tar.ctypes.data, non.ctypes.data,
+                  nan.ctypes.data, rng.ctypes.data, where)
+    return _result(timing, ms, tar_hist=tar, non_hist=non, nan_count=nan, range=rng, thresholds=th)
 
 
 PAIRWISE_MAX_Q = 1024   # largest dimension of ssp_pairwise_scores (include/ssp.h)
@@ -1535,9 +1299,7 @@ def _as_recordings(ctx: Context, seg_or_counts) -> Segments:
 
 def pairwise_size(seg: Segments) -> int:
     """sum of n_r^2 over the recordings (ssp_pairwise_size): the floats of a packed batch of score matrices"""
-    t = C.c_int64()
-    _lib.check(seg._lib.ssp_pairwise_size(seg._h, C.byref(t)))
-    return t.value
+    return _read_int(C.c_int64, seg._lib.ssp_pairwise_size, seg._h)
 
 
 def pairwise_offsets(seg: Segments) -> np.ndarray:
@@ -1579,13 +1341,9 @@ def pairwise_scores(ctx: Context, X, seg_or_counts, g=None, h=None, c0: float = 
             isinstance(out, np.ndarray) and where == _lib.HOST and out.dtype == np.float32 and out.flags.c_contiguous)
         if not ok or int(np.prod(out.shape)) != total:
             raise ValueError("out must be a contiguous float32 array of X's kind with %d entries" % total)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_pairwise_scores(ctx._h, ptr, seg._h, q, None if vec[0] is None else vec[0].ctypes.data,
-                                                None if vec[1] is None else vec[1].ctypes.data, float(c0), _raw_ptr(out, where), where,
-                                                C.byref(ms) if timing else None))
-    del keep
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_pairwise_scores, where, timing, ctx._h, ptr, seg._h, q, _raw_ptr(vec[0], _lib.HOST), _raw_ptr(vec[1], _lib.HOST),
+                  float(c0), _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
 def ahc_cluster(ctx: Context, scores, seg_or_counts, linkage: str = "average", threshold: float = 0.0, min_clusters: int = 1,
@@ -1614,21 +1372,9 @@ def ahc_cluster(ctx: Context, scores, seg_or_counts, linkage: str = "average", t
     cnt[...] = 0   # (a recording without segments is not written)
     mp = ctx._empty((total, 2), where, "int32") if merges else None
     msc = ctx._empty((total,), where) if merges else None
-    ms = C.c_float(0.0)
-
-    def p(x):
-        return None if x is None else _raw_ptr(x, where)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_ahc_cluster(ctx._h, ptr, seg._h, AHC_LINKAGES[linkage], float(threshold), int(min_clusters),
-                                            None if ns is None else ns.ctypes.data, p(lab), p(cnt), p(mp), p(msc), where,
-                                            C.byref(ms) if timing else None))
-    del keep
-    res = {"labels": lab, "n_clusters": cnt}
-    if merges:
-        res["merge_pair"], res["merge_score"] = mp, msc
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    ms = ctx._run(ctx._lib.ssp_ahc_cluster, where, timing, ctx._h, ptr, seg._h, AHC_LINKAGES[linkage], float(threshold), int(min_clusters),
+                  _raw_ptr(ns, _lib.HOST), _raw_ptr(lab, where), _raw_ptr(cnt, where), _raw_ptr(mp, where), _raw_ptr(msc, where), where)
+    return _result(timing, ms, labels=lab, n_clusters=cnt, merge_pair=mp, merge_score=msc)
 
 
 VBHMM_MAX_STATES = 64     # most HMM states of ssp_vbhmm_resegment (include/ssp.h); its q, rows and iterations: 1024, 4096, 100
@@ -1711,20 +1457,10 @@ def vb_resegment(ctx: Context, X, seg_or_counts, phi, init_labels, n_init=None, 
             res[name] = ctx._empty(shape, where, dt)
             if name in ("n_speakers", "n_iters", "pi", "elbo"):
                 res[name][...] = 0   # (a recording without rows is not written)
-    ms = C.c_float(0.0)
-
-    def p(name):
-        return None if name not in res else _raw_ptr(res[name], where)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_vbhmm_resegment(ctx._h, ptr, seg._h, q, ph.ctypes.data, _raw_ptr(lab0, where),
-                                                None if ni is None else _raw_ptr(ni, where), S, float(loop_prob), float(Fa), float(Fb),
-                                                float(init_smoothing), mi, float(epsilon), p("labels"), p("states"), p("n_speakers"),
-                                                p("n_iters"), p("elbo"), p("gamma"), p("pi"), p("loglik"), where,
-                                                C.byref(ms) if timing else None))
-    del keep, lab0, ni
-    if timing:
-        res["kernel_ms"] = ms.value
-    return res
+    outs = [_raw_ptr(res.get(name), where) for name in ("labels", "states", "n_speakers", "n_iters", "elbo", "gamma", "pi", "loglik")]
+    ms = ctx._run(ctx._lib.ssp_vbhmm_resegment, where, timing, ctx._h, ptr, seg._h, q, ph.ctypes.data, _raw_ptr(lab0, where), _raw_ptr(ni, where), S,
+                  float(loop_prob), float(Fa), float(Fb), float(init_smoothing), mi, float(epsilon), *outs, where)
+    return _result(timing, ms, **res)
 
 
 def centroids(ctx: Context, X, labels, num: int):
@@ -1742,9 +1478,7 @@ def centroids(ctx: Context, X, labels, num: int):
     if int(lab.shape[0]) != int(keep.shape[0]):
         raise ValueError("one label per row of X")
     out = ctx._empty((int(num), int(keep.shape[1])), where)
-    optr = out.data_ptr() if where == _lib.DEVICE else out.ctypes.data
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_centroids(ctx._h, ptr, lptr, int(keep.shape[0]), int(keep.shape[1]), int(num), optr, where, None))
+    ctx._run(ctx._lib.ssp_centroids, where, False, ctx._h, ptr, lptr, int(keep.shape[0]), int(keep.shape[1]), int(num), _raw_ptr(out, where), where)
     return out
 
 
@@ -1768,10 +1502,9 @@ def dtw_distances(ctx: Context, queries, templates, normalize: bool = False, tim
     if dq != dt:
         raise ValueError("queries and templates must share the feature dimension")
     out = np.empty((qs.n, ts.n), dtype=np.float32)
-    ms = C.c_float(0.0)
-    _lib.check(ctx._lib.ssp_dtw_distances(ctx._h, q.ctypes.data, qs._h, t.ctypes.data, ts._h, dq, 1 if normalize else 0,
-                                           out.ctypes.data, _lib.HOST, C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_dtw_distances, _lib.HOST, timing, ctx._h, q.ctypes.data, qs._h, t.ctypes.data, ts._h, dq, 1 if normalize else 0,
+                  out.ctypes.data, _lib.HOST)
+    return (out, ms) if timing else out
 
 
 def fastdtw_distances(ctx: Context, queries, templates, radius: int = 1, timing: bool = False):
@@ -1784,10 +1517,8 @@ def fastdtw_distances(ctx: Context, queries, templates, radius: int = 1, timing:
     fq, sq = pack(queries)
     ft, st = pack(templates)
     out = np.empty((sq.n, st.n), dtype=np.float64)
-    ms = C.c_float(0.0)
-    _lib.check(ctx._lib.ssp_fastdtw_distances(ctx._h, fq.ctypes.data, sq._h, ft.ctypes.data, st._h, int(radius), out.ctypes.data,
-                                               C.byref(ms) if timing else None))
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_fastdtw_distances, _lib.HOST, timing, ctx._h, fq.ctypes.data, sq._h, ft.ctypes.data, st._h, int(radius), out.ctypes.data)
+    return (out, ms) if timing else out
 
 
 def dtw_path(ctx: Context, x, y):
@@ -1860,11 +1591,10 @@ def dtw_templates(ctx, groups, workspace_bytes: int = 0, timing: bool = False):
     longest = [int(np.diff(seq_off[grp_off[g]:grp_off[g + 1] + 1]).max()) for g in range(n_grp)]
     out = np.empty((sum(longest), dim), dtype=np.float64)
     toff = np.empty(n_grp + 1, dtype=np.int64)
-    ms = C.c_float(0.0)
-    _lib.check(ctx._lib.ssp_dtw_templates(ctx._h, x.ctypes.data, seq_off.ctypes.data, len(seq_off) - 1, grp_off.ctypes.data, n_grp, dim,
-                                           int(workspace_bytes), out.ctypes.data, toff.ctypes.data, C.byref(ms) if timing else None))
+    ms = ctx._run(ctx._lib.ssp_dtw_templates, _lib.HOST, timing, ctx._h, x.ctypes.data, seq_off.ctypes.data, len(seq_off) - 1, grp_off.ctypes.data,
+                  n_grp, dim, int(workspace_bytes), out.ctypes.data, toff.ctypes.data)
     res = [out[toff[g]:toff[g + 1]].reshape(-1).copy() if flat else out[toff[g]:toff[g + 1]].copy() for g in range(n_grp)]
-    return (res, ms.value) if timing else res
+    return (res, ms) if timing else res
 
 
 def dense_forward(ctx: Context, X, Wt, bias=None, relu: bool = False, timing: bool = False):
@@ -1883,23 +1613,20 @@ def dense_forward(ctx: Context, X, Wt, bias=None, relu: bool = False, timing: bo
         if bwhere != where or int(np.prod(bk.shape)) != units:
             raise ValueError("bias must have `units` entries and live where X lives")
     Y = ctx._empty((N, units), where)
-    yp = Y.data_ptr() if where == _lib.DEVICE else Y.ctypes.data
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_dense_forward(ctx._h, xp, N, d_in, wp, bp, units, 1 if relu else 0, yp, where,
-                                               C.byref(ms) if timing else None))
-    return (Y, ms.value) if timing else Y
+    ms = ctx._run(ctx._lib.ssp_dense_forward, where, timing, ctx._h, xp, N, d_in, wp, bp, units, 1 if relu else 0, _raw_ptr(Y, where), where)
+    return (Y, ms) if timing else Y
 
 
-class DnnForward:
+class DnnForward(_Handle):
     """A fully connected network packed once for the GPU forward pass (ssp_dnn): ``layers`` = list of (Wt (units, d_in) float32 — the
     Keras kernel transposed —, bias (units,) or None, relu bool).  ``forward(X)`` = predict: the layers whose widths are <= 256 run in
     one kernel with the activations kept in registers (the d-vector network's hidden and output layers), wider layers in front of
     them one GEMM launch each."""
 
+    _DESTROY = "ssp_dnn_destroy"
+
     def __init__(self, ctx: Context, layers):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         n = len(layers)
         if n < 1:
             raise ValueError("at least one layer")
@@ -1914,9 +1641,7 @@ class DnnForward:
         c_w = (C.c_void_p * n)(*[w.ctypes.data for w in ws])
         c_b = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in bs])
         c_r = (C.c_int32 * n)(*[1 if r else 0 for _, _, r in layers])
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_dnn_create(ctx._h, n, c_dims, c_w, c_b, c_r, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_dnn_create, ctx._h, n, c_dims, c_w, c_b, c_r)
 
     def forward(self, X, timing: bool = False):
         xk, xp, where = _as_f32(X, "X")
@@ -1924,25 +1649,11 @@ class DnnForward:
             raise ValueError("X must be (N, %d)" % self.dims[0])
         N = int(xk.shape[0])
         Y = self.ctx._empty((N, self.dims[-1]), where)
-        yp = Y.data_ptr() if where == _lib.DEVICE else Y.ctypes.data
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_dnn_forward(self._h, xp, N, yp, where, C.byref(ms) if timing else None))
-        return (Y, ms.value) if timing else Y
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_dnn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_dnn_forward, where, timing, self._h, xp, N, _raw_ptr(Y, where), where)
+        return (Y, ms) if timing else Y
 
 
-class _Trainer:
+class _Trainer(_Handle):
     """What DnnTrainer, LstmTrainer and GruTrainer share: the data checks, epoch / evaluate, the step counter and the handle's life.  A
     subclass names its entry points' prefix (ssp_<prefix>_trainer_*), creates ``_h`` and sets ``_row``, the shape of one row of X."""
 
@@ -1951,6 +1662,10 @@ class _Trainer:
 
     def _fn(self, name):
         return getattr(self._lib, "ssp_%s_trainer_%s" % (self._PREFIX, name))
+
+    @property
+    def _DESTROY(self):
+        return "ssp_%s_trainer_destroy" % self._PREFIX
 
     def _data(self, X, labels):
         xk, xp, where = _as_f32(X, "X")
@@ -1979,11 +1694,10 @@ class _Trainer:
             if ok.shape != (N,):
                 raise ValueError("order must hold N row indices")
             op = ok.ctypes.data
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._fn("epoch")(self._h, xp, lp, N, op, int(batch_size), float(lr), *extra, C.byref(loss), C.byref(corr), where,
-                                         C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+        loss, corr = C.c_double(0.0), C.c_int64(0)
+        ms = self.ctx._run(self._fn("epoch"), where, timing, self._h, xp, lp, N, op, int(batch_size), float(lr), *extra, C.byref(loss),
+                           C.byref(corr), where)
+        return (loss.value, corr.value, ms) if timing else (loss.value, corr.value)
 
     def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, timing: bool = False):
         """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
@@ -1993,10 +1707,9 @@ class _Trainer:
     def evaluate(self, X, labels, timing: bool = False):
         """loss sum and correct rows over (X, labels), dropout off; nothing is updated"""
         keep, xp, lp, N, where = self._data(X, labels)
-        loss, corr, ms = C.c_double(0.0), C.c_int64(0), C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._fn("evaluate")(self._h, xp, lp, N, C.byref(loss), C.byref(corr), where, C.byref(ms) if timing else None))
-        return (loss.value, corr.value, ms.value) if timing else (loss.value, corr.value)
+        loss, corr = C.c_double(0.0), C.c_int64(0)
+        ms = self.ctx._run(self._fn("evaluate"), where, timing, self._h, xp, lp, N, C.byref(loss), C.byref(corr), where)
+        return (loss.value, corr.value, ms) if timing else (loss.value, corr.value)
 
     def _read_into(self, name, out):
         """the array ``read`` fills for tensor ``name``: a new one, or ``out`` when it is a contiguous float32 array of the tensor's size"""
@@ -2008,20 +1721,7 @@ class _Trainer:
 
     @property
     def steps(self) -> int:
-        t = C.c_int64(0)
-        _lib.check(self._fn("steps")(self._h, C.byref(t)))
-        return t.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._fn("destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _read_int(C.c_int64, self._fn("steps"), self._h)
 
 
 class DnnTrainer(_Trainer):
@@ -2033,8 +1733,7 @@ class DnnTrainer(_Trainer):
     _PREFIX = "dnn"
 
     def __init__(self, ctx: Context, layers, max_batch: int = 128):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         n = len(layers)
         if n < 1:
             raise ValueError("at least one layer")
@@ -2053,9 +1752,7 @@ class DnnTrainer(_Trainer):
         c_p = (C.c_float * n)(*[float(p) for _, _, _, p in layers])
         c_w = (C.c_void_p * n)(*[w.ctypes.data for w in ws])
         c_b = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for b in bs])
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_dnn_trainer_create(ctx._h, n, c_dims, c_r, c_p, c_w, c_b, int(max_batch), C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_dnn_trainer_create, ctx._h, n, c_dims, c_r, c_p, c_w, c_b, int(max_batch))
 
     def epoch(self, X, labels, order=None, batch_size: int = 128, lr: float = 1e-4, seed: int = 0, timing: bool = False):
         """ceil(N / batch_size) training steps over the rows in ``order`` (int64 (N,), default 0..N-1) -> (loss sum, correct rows)
@@ -2101,32 +1798,29 @@ def lstm_pack_weights(W, U, b=None):
     vector laid out as include/ssp.h documents.  W (d_in, 4 units), U (units, 4 units), b (4 units,) or None — Keras' layout."""
     W, U, b = _lstm_arrays(W, U, b)
     lib = _lib.load()
-    n = C.c_int64()
     d_in, units = int(W.shape[0]), int(U.shape[0])
-    _lib.check(lib.ssp_lstm_pack_weights(d_in, units, None, None, None, None, C.byref(n)))
-    img = np.empty(n.value, dtype=np.float32)
-    _lib.check(lib.ssp_lstm_pack_weights(d_in, units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data, img.ctypes.data, None))
+    img = np.empty(_read_int(C.c_int64, lib.ssp_lstm_pack_weights, d_in, units, None, None, None, None), dtype=np.float32)
+    _lib.check(lib.ssp_lstm_pack_weights(d_in, units, W.ctypes.data, U.ctypes.data, _raw_ptr(b, _lib.HOST), img.ctypes.data, None))
     return img
 
 
-class LstmForward:
+class LstmForward(_Handle):
     """One Keras LSTM layer packed once for the GPU forward pass (ssp_lstm; d_vector.py:271-294): W (d_in, 4 units), U (units, 4 units),
     b (4 units,) or None in Keras' layout (gate blocks i | f | c | o), ``recurrent_activation`` 'hard_sigmoid' or 'sigmoid' — named by
     the caller, there is no default.  ``forward`` returns the last hidden state of every sequence.  units: a multiple of 16 up to 128,
     d_in up to 64 (NotImplementedError otherwise)."""
 
+    _DESTROY = "ssp_lstm_destroy"
+
     def __init__(self, ctx: Context, W, U, b, recurrent_activation):
         if recurrent_activation not in LSTM_ACTIVATIONS:
             raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         W, U, b = _lstm_arrays(W, U, b)
         self.d_in, self.units = int(W.shape[0]), int(U.shape[0])
         self.recurrent_activation = recurrent_activation
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_lstm_create(ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data,
-                                             LSTM_ACTIVATIONS[recurrent_activation], C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_lstm_create, ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, _raw_ptr(b, _lib.HOST),
+                     LSTM_ACTIVATIONS[recurrent_activation])
 
     def forward(self, feats, frame_seg: Optional[Segments] = None, timing: bool = False):
         """feats (N, T, d_in) — equal lengths, no segments needed — or (frames, d_in) laid out by ``frame_seg`` (what MfccPlan.run
@@ -2146,22 +1840,8 @@ class LstmForward:
         elif int(keep.shape[0]) < int(frame_seg.offsets[-1]):
             raise ValueError("fewer rows than frame_seg has frames")
         out = self.ctx._empty((frame_seg.n, self.units), where)
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_lstm_forward(self._h, ptr, frame_seg._h, _raw_ptr(out, where), where, C.byref(ms) if timing else None))
-        del keep
-        return (out, ms.value) if timing else out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_lstm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_lstm_forward, where, timing, self._h, ptr, frame_seg._h, _raw_ptr(out, where), where)
+        return (out, ms) if timing else out
 
 
 class LstmTrainer(_Trainer):
@@ -2178,8 +1858,7 @@ class LstmTrainer(_Trainer):
     def __init__(self, ctx: Context, W, U, b, Wd, bd, *, T, recurrent_activation, max_batch: int = 128):
         if recurrent_activation not in LSTM_ACTIVATIONS:
             raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         W, U, b = _lstm_arrays(W, U, b)
         Wd = np.ascontiguousarray(Wd, dtype=np.float32)
         bd = None if bd is None else np.ascontiguousarray(bd, dtype=np.float32).reshape(-1)
@@ -2191,11 +1870,8 @@ class LstmTrainer(_Trainer):
         self.has_bias = {"b": b is not None, "bd": bd is not None}
         self.shapes = {"W": (self.d_in, 4 * self.units), "U": (self.units, 4 * self.units), "b": (4 * self.units,),
                        "Wd": (self.units, self.n_class), "bd": (self.n_class,)}
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_lstm_trainer_create(ctx._h, self.d_in, self.units, self.n_class, self.T, LSTM_ACTIVATIONS[recurrent_activation],
-                                                     W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data, Wd.ctypes.data,
-                                                     None if bd is None else bd.ctypes.data, int(max_batch), C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_lstm_trainer_create, ctx._h, self.d_in, self.units, self.n_class, self.T, LSTM_ACTIVATIONS[recurrent_activation],
+                     W.ctypes.data, U.ctypes.data, _raw_ptr(b, _lib.HOST), Wd.ctypes.data, _raw_ptr(bd, _lib.HOST), int(max_batch))
 
     STEP_LAUNCHES = ("forward+stash", "dense head", "loss", "dWd", "dh_T", "backward through time", "dW+db", "dU", "adam")
 
@@ -2241,26 +1917,25 @@ def _gru_arrays(W, U, b, reset_after):
     return W, U, b
 
 
-class GruForward:
+class GruForward(_Handle):
     """One Keras GRU layer packed once for the GPU forward pass (ssp_gru; the GRU(1024, return_sequences=True) layers of d_vector.py:229-231):
     W (d_in, 3 units), U (units, 3 units), b in Keras' layout (gate blocks z | r | h).  Both switches are named by the caller, there is no
     default: ``recurrent_activation`` 'hard_sigmoid' or 'sigmoid', ``reset_after`` False (stand-alone Keras; b (3 units,) or None) or True
     (tf.keras 2; b (2, 3 units) or None).  units: a multiple of 16 up to 1024, d_in up to 4096 (NotImplementedError otherwise)."""
+
+    _DESTROY = "ssp_gru_destroy"
 
     def __init__(self, ctx: Context, W, U, b, recurrent_activation, reset_after):
         if recurrent_activation not in GRU_ACTIVATIONS:
             raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
         if not isinstance(reset_after, (bool, np.bool_)):
             raise ValueError("reset_after must be True or False")
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         W, U, b = _gru_arrays(W, U, b, reset_after)
         self.d_in, self.units = int(W.shape[0]), int(U.shape[0])
         self.recurrent_activation, self.reset_after = recurrent_activation, bool(reset_after)
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_gru_create(ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, None if b is None else b.ctypes.data,
-                                            GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_gru_create, ctx._h, self.d_in, self.units, W.ctypes.data, U.ctypes.data, _raw_ptr(b, _lib.HOST),
+                     GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0)
 
     def set_workspace(self, nbytes: int) -> "GruForward":
         """cap of the workspace one forward call may hold; larger batches run in slabs of whole chunks (same bits)"""
@@ -2269,9 +1944,7 @@ class GruForward:
 
     @property
     def last_slab(self) -> int:
-        n = C.c_int64(0)
-        _lib.check(self._lib.ssp_gru_last_slab(self._h, C.byref(n)))
-        return n.value
+        return _read_int(C.c_int64, self._lib.ssp_gru_last_slab, self._h)
 
     def forward(self, X, mean: bool = False, timing: bool = False):
         """X (N, T, d_in), numpy (host) or torch CUDA tensor -> the output sequence (N, T, units) of the same kind, or with ``mean=True``
@@ -2281,24 +1954,11 @@ class GruForward:
             raise ValueError("X must be (N, T >= 1, %d)" % self.d_in)
         N, T = int(keep.shape[0]), int(keep.shape[1])
         out = self.ctx._empty((N, self.units) if mean else (N, T, self.units), where)
-        ms = C.c_float(0.0)
+        ms = 0.0
         if N:
-            with self.ctx._ordered(where):
-                _lib.check(self._lib.ssp_gru_forward(self._h, ptr, N, T, None if mean else _raw_ptr(out, where), _raw_ptr(out, where) if mean else None,
-                                                     where, C.byref(ms) if timing else None))
-        del keep
-        return (out, ms.value) if timing else out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_gru_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            ms = self.ctx._run(self._lib.ssp_gru_forward, where, timing, self._h, ptr, N, T, None if mean else _raw_ptr(out, where),
+                               _raw_ptr(out, where) if mean else None, where)
+        return (out, ms) if timing else out
 
 
 def _xv_vec(x, units, what, where=None):
@@ -2347,12 +2007,9 @@ def tdnn_forward(ctx: Context, X, seg_or_counts, W, bias=None, dilation: int = 1
     ok, op = _xv_vec(offset, units, "offset", where)
     Y = ctx._empty((int(xk.shape[0]), units), where)
     lens = np.zeros(seg.n, dtype=np.int64)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_tdnn_forward(ctx._h, xp, seg._h, d_in, wp, bp, taps, int(dilation), units, 1 if relu else 0, sp, op, _raw_ptr(Y, where),
-                                              lens.ctypes.data_as(C.POINTER(C.c_int64)), where, C.byref(ms) if timing else None))
-    del xk, wk, bk, sk, ok
-    return (Y, lens, ms.value) if timing else (Y, lens)
+    ms = ctx._run(ctx._lib.ssp_tdnn_forward, where, timing, ctx._h, xp, seg._h, d_in, wp, bp, taps, int(dilation), units, 1 if relu else 0, sp, op,
+                  _raw_ptr(Y, where), lens.ctypes.data_as(C.POINTER(C.c_int64)), where)
+    return (Y, lens, ms) if timing else (Y, lens)
 
 
 def stats_pool(ctx: Context, X, seg_or_counts, windows=None, var_floor: float = 1e-10, timing: bool = False):
@@ -2367,22 +2024,20 @@ def stats_pool(ctx: Context, X, seg_or_counts, windows=None, var_floor: float = 
     wk, wptr, n_out = _xv_windows(windows, seg)
     dim = int(xk.shape[1])
     out = ctx._empty((n_out, 2 * dim), where)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_stats_pool(ctx._h, xp, seg._h, dim, wptr, n_out if wk is not None else 0, float(var_floor), _raw_ptr(out, where),
-                                            where, C.byref(ms) if timing else None))
-    del xk, wk
-    return (out, ms.value) if timing else out
+    ms = ctx._run(ctx._lib.ssp_stats_pool, where, timing, ctx._h, xp, seg._h, dim, wptr, n_out if wk is not None else 0, float(var_floor),
+                  _raw_ptr(out, where), where)
+    return (out, ms) if timing else out
 
 
-class XVectorForward:
+class XVectorForward(_Handle):
     """An x-vector network packed once for the GPU forward pass (ssp_xvector; include/ssp.h has the model).  ``frame_layers``: a list of
     dicts with W (units, taps, d_in) and optionally b, scale, offset (units,), dilation (1) and relu (False); ``segment_layers``: the same
     with W (units, d_in) and no dilation.  ``forward`` returns one embedding per sequence, or per window of a host table."""
 
+    _DESTROY = "ssp_xvector_destroy"
+
     def __init__(self, ctx: Context, frame_layers, segment_layers=(), var_floor: float = 1e-10):
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         if len(frame_layers) < 1:
             raise ValueError("at least one frame layer")
         keep = []
@@ -2419,11 +2074,8 @@ class XVectorForward:
         self.d_in = int(W0.shape[2])
         nf, fu, ft, fd, fw, fb, fr, fs, fo, last = pack(frame_layers, 3, self.d_in, "frame")
         ns, su, _, _, sw, sb, sr, ss, so, _ = pack(segment_layers, 2, 2 * last, "segment")
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_xvector_create(ctx._h, self.d_in, nf, fu, ft, fd, fw, fb, fr, fs, fo, ns, su, sw, sb, sr, ss, so, float(var_floor),
-                                                C.byref(h)))
-        self._h = h
-        del keep
+        self._create(self._lib.ssp_xvector_create, ctx._h, self.d_in, nf, fu, ft, fd, fw, fb, fr, fs, fo, ns, su, sw, sb, sr, ss, so,
+                     float(var_floor))   # (keep owns what the pointer arrays point into)
         r, p, e = C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(self._lib.ssp_xvector_info(self._h, C.byref(r), C.byref(p), C.byref(e)))
         self.receptive_field, self.pooled_width, self.embed_width = r.value, p.value, e.value
@@ -2435,39 +2087,21 @@ class XVectorForward:
 
     @property
     def last_slab(self) -> int:
-        n = C.c_int64(0)
-        _lib.check(self._lib.ssp_xvector_last_slab(self._h, C.byref(n)))
-        return n.value
+        return _read_int(C.c_int64, self._lib.ssp_xvector_last_slab, self._h)
 
     def forward(self, feats, seg_or_counts, windows=None, timing: bool = False):
         """feats (frames, d_in) laid out by the segments (an api.Segments or the frames per sequence), numpy (host) or torch CUDA tensor;
         windows: None or a host table (n_win, 3) of (sequence, first, end) input frames.  -> (n_seq or n_win, embed width) of feats'
         kind [and kernel milliseconds]."""
-        keep, ptr, where = _as_f32(feats, "feats")
-        if keep.ndim != 2 or int(keep.shape[1]) != self.d_in:
-            raise ValueError("feats must be (frames, %d)" % self.d_in)
+        keep, ptr, where = _as_frames(feats, self.d_in)
         seg = _as_recordings(self.ctx, seg_or_counts)
         if int(keep.shape[0]) < int(seg.offsets[-1]):
             raise ValueError("fewer rows than the segments have frames")
         wk, wptr, n_out = _xv_windows(windows, seg)
         out = self.ctx._empty((n_out, self.embed_width), where)
-        ms = C.c_float(0.0)
-        with self.ctx._ordered(where):
-            _lib.check(self._lib.ssp_xvector_forward(self._h, ptr, seg._h, wptr, n_out if wk is not None else 0, _raw_ptr(out, where), where,
-                                                     C.byref(ms) if timing else None))
-        del keep, wk
-        return (out, ms.value) if timing else out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.ssp_xvector_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self.ctx._run(self._lib.ssp_xvector_forward, where, timing, self._h, ptr, seg._h, wptr, n_out if wk is not None else 0,
+                           _raw_ptr(out, where), where)
+        return (out, ms) if timing else out
 
 
 def conv2d_same_out_shape(T: int, D: int, strides):
@@ -2501,12 +2135,8 @@ def conv2d_same(ctx: Context, X, K, bias=None, strides=(1, 1), timing: bool = Fa
         raise ValueError("strides must be >= 1")
     To, Do = conv2d_same_out_shape(T, D, (sh, sw))
     Y = ctx._empty((N, To, Do * F), where)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_conv2d_same_forward(ctx._h, xp, N, T, D, kp, bp, kh, kw, F, sh, sw, _raw_ptr(Y, where), where,
-                                                     C.byref(ms) if timing else None))
-    del xk, kk, bk
-    return (Y, ms.value) if timing else Y
+    ms = ctx._run(ctx._lib.ssp_conv2d_same_forward, where, timing, ctx._h, xp, N, T, D, kp, bp, kh, kw, F, sh, sw, _raw_ptr(Y, where), where)
+    return (Y, ms) if timing else Y
 
 
 def l2_normalize(ctx: Context, X, eps: float = 1e-12, timing: bool = False):
@@ -2517,11 +2147,8 @@ def l2_normalize(ctx: Context, X, eps: float = 1e-12, timing: bool = False):
         raise ValueError("X must be (N, d >= 1)")
     N, d = int(xk.shape[0]), int(xk.shape[1])
     Y = ctx._empty((N, d), where)
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_l2_normalize(ctx._h, xp, N, d, float(eps), _raw_ptr(Y, where), where, C.byref(ms) if timing else None))
-    del xk
-    return (Y, ms.value) if timing else Y
+    ms = ctx._run(ctx._lib.ssp_l2_normalize, where, timing, ctx._h, xp, N, d, float(eps), _raw_ptr(Y, where), where)
+    return (Y, ms) if timing else Y
 
 
 class GruTrainer(_Trainer):
@@ -2545,8 +2172,7 @@ class GruTrainer(_Trainer):
             raise ValueError("recurrent_activation must be 'hard_sigmoid' or 'sigmoid'")
         if not isinstance(reset_after, (bool, np.bool_)):
             raise ValueError("reset_after must be True or False")
-        self.ctx = ctx
-        self._lib = ctx._lib
+        super().__init__(ctx)
         K, bc, strides = conv
         K = np.ascontiguousarray(K, dtype=np.float32)
         if K.ndim == 4 and K.shape[2] == 1:
@@ -2601,12 +2227,9 @@ class GruTrainer(_Trainer):
         c_w = (C.c_void_p * n)(*[W.ctypes.data for W, _, _ in layers])
         c_u = (C.c_void_p * n)(*[U.ctypes.data for _, U, _ in layers])
         c_b = (C.c_void_p * n)(*[None if b is None else b.ctypes.data for _, _, b in layers])
-        p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-        h = C.c_void_p()
-        _lib.check(self._lib.ssp_gru_trainer_create(ctx._h, self.T, self.D, kh, kw, F, sh, sw, K.ctypes.data, p(bc), n, c_units, c_w, c_u, c_b, E,
-                                                    Wd.ctypes.data, p(bd), self.n_class, Wh.ctypes.data, p(bh),
-                                                    GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, int(max_batch), C.byref(h)))
-        self._h = h
+        self._create(self._lib.ssp_gru_trainer_create, ctx._h, self.T, self.D, kh, kw, F, sh, sw, K.ctypes.data, _raw_ptr(bc, _lib.HOST), n, c_units,
+                     c_w, c_u, c_b, E, Wd.ctypes.data, _raw_ptr(bd, _lib.HOST), self.n_class, Wh.ctypes.data, _raw_ptr(bh, _lib.HOST),
+                     GRU_ACTIVATIONS[recurrent_activation], 1 if reset_after else 0, int(max_batch))
 
     STEP_KINDS = ("conv forward", "mean+dense+l2+head", "loss+regulariser", "head+l2+dense+mean backward", "conv backward", "adam+repack")
     LAYER_KINDS = ("projection", "forward steps", "backward steps", "dW+db", "dU", "dx")
@@ -2675,32 +2298,15 @@ def cosine_identify(ctx: Context, X, Cn, dist: bool = False, argmin: bool = True
     dm = ctx._empty((N, S), where) if dist else None
     am = ctx._empty((N,), where, "int32") if argmin else None
     mv = ctx._empty((N,), where) if minval else None
-
-    def p(x):
-        if x is None:
-            return None
-        return x.data_ptr() if where == _lib.DEVICE else x.ctypes.data
-    ms = C.c_float(0.0)
-    with ctx._ordered(where):
-        _lib.check(ctx._lib.ssp_cosine_identify2(ctx._h, xp, N, d, cp, S, p(dm), p(am), p(mv), where, int(precision),
-                                                 C.byref(ms) if timing else None))
+    ms = ctx._run(ctx._lib.ssp_cosine_identify2, where, timing, ctx._h, xp, N, d, cp, S, _raw_ptr(dm, where), _raw_ptr(am, where), _raw_ptr(mv, where),
+                  where, int(precision))
     res = {}
     if precision == 3:
         a, b, c, e = C.c_int32(-1), C.c_int32(0), C.c_int32(0), C.c_int32(0)
         _lib.check(ctx._lib.ssp_cosine_last_auto(ctx._h, C.byref(a), C.byref(b), C.byref(c), C.byref(e)))
         res["auto"] = {"precision_used": a.value, "pilot_rows": b.value, "pilot_to_bf16x3": c.value, "pilot_to_fp32": e.value}
     if precision >= 1 and counts:
-        n = C.c_int32(0)
-        _lib.check(ctx._lib.ssp_cosine_last_rescored(ctx._h, C.byref(n)))
-        res["rescored"] = n.value
-        _lib.check(ctx._lib.ssp_cosine_last_split_rows(ctx._h, C.byref(n)))
-        res["split_rows"] = n.value   # precision 2: rows the bf16 sweep handed to the bf16x3 sweep
-    if dist:
-        res["dist"] = dm
-    if argmin:
-        res["argmin"] = am
-    if minval:
-        res["min"] = mv
-    if timing:
-        res["kernel_ms"] = ms.value
+        res["rescored"] = _read_int(C.c_int32, ctx._lib.ssp_cosine_last_rescored, ctx._h)
+        res["split_rows"] = _read_int(C.c_int32, ctx._lib.ssp_cosine_last_split_rows, ctx._h)   # precision 2: rows the bf16 sweep handed on
+    res.update(_result(timing, ms, dist=dm, argmin=am, min=mv))
     return res
