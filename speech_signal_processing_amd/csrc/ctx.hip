@@ -1,5 +1,6 @@
 // Context, error reporting and segment handles of libsspgpu.so.
 #include "common.hpp"
+#include "handle.hpp"
 
 #include <dlfcn.h>
 
@@ -84,7 +85,7 @@ void quiesce_ctx(const ssp_ctx* ctx) {
     (void)sync_quietly(ctx->stream);
 }
 
-int segments_make(ssp_ctx* ctx, const int64_t* offsets, int64_t n, ssp_segments** out) {
+int segments_make(ssp_ctx* ctx, const int64_t* offsets, int64_t n, ssp_segments** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "segments: null out");
     *out = nullptr;
     SSP_TRY(use_ctx(ctx));
@@ -92,30 +93,14 @@ int segments_make(ssp_ctx* ctx, const int64_t* offsets, int64_t n, ssp_segments*
     if (offsets[0] < 0) SSP_FAIL(SSP_ERR_INVALID, "segments: offsets[0] < 0");
     for (int64_t i = 0; i < n; ++i)
         if (offsets[i + 1] < offsets[i]) SSP_FAIL(SSP_ERR_INVALID, "segments: offsets decrease at %lld", (long long)i);
-    ssp_segments* s = new (std::nothrow) ssp_segments;
-    if (!s) SSP_FAIL(SSP_ERR_NOMEM, "segments: host alloc");
+    HandleBuild<ssp_segments> s(ctx, "segments");
     static std::atomic<uint64_t> next_serial{1};
-    s->ctx = ctx;
     s->serial = next_serial.fetch_add(1);
     s->n = n;
     s->host.assign(offsets, offsets + n + 1);
-    int rc = s->dev.alloc(sizeof(int64_t) * (size_t)(n + 1));
-    if (rc == SSP_OK) {
-        hipError_t e = hipMemcpyAsync(s->dev.p, s->host.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice,
-                                      ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("segments upload failed: %s", hipGetErrorString(e));
-            rc = SSP_ERR_HIP;
-        }
-    }
-    if (rc != SSP_OK) {
-        delete s;
-        return rc;
-    }
-    *out = s;
-    return SSP_OK;
+    return s.commit(upload(s, s->dev, s->host), out);
 }
+SSP_CREATE_GUARD("segments")
 
 // fills the whole LDS of the CU it lands on with one 32-bit pattern (test aid: a kernel that reads LDS it never wrote then reads
 // this pattern — e.g. a NaN — instead of whatever the previous kernel left behind)
@@ -225,12 +210,7 @@ int ssp_segments_create(ssp_ctx* ctx, const int64_t* offsets, int64_t n_seg, ssp
     return ssp::segments_make(ctx, offsets, n_seg, out);
 }
 
-int ssp_segments_destroy(ssp_segments* seg) {
-    if (!seg) return SSP_OK;
-    ssp::quiesce_ctx(seg->ctx);
-    delete seg;
-    return SSP_OK;
-}
+int ssp_segments_destroy(ssp_segments* seg) { return ssp::destroy_handle(seg); }
 
 int ssp_segments_count(const ssp_segments* seg, int64_t* n_seg, int64_t* total) {
     if (!seg) SSP_FAIL(SSP_ERR_INVALID, "null segments");

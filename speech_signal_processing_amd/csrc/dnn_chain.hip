@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "nn_device.hpp"
 
 namespace ssp {
@@ -177,7 +178,7 @@ using namespace ssp;
 extern "C" {
 
 int ssp_dnn_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const float* const* Wt, const float* const* bias,
-                   const int32_t* relu, ssp_dnn** out) {
+                   const int32_t* relu, ssp_dnn** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_create: null out");
     *out = nullptr;
     SSP_TRY(use_ctx(ctx));
@@ -186,66 +187,44 @@ int ssp_dnn_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const fl
         if (dims[l] < 1) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_create: layer width < 1");
     for (int l = 0; l < n_layers; ++l)
         if (!Wt[l]) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_create: null kernel of layer %d", l);
-    ssp_dnn* d = new (std::nothrow) ssp_dnn;
-    if (!d) SSP_FAIL(SSP_ERR_NOMEM, "dnn: host alloc");
-    d->ctx = ctx;
-    d->n_layers = n_layers;
-    d->dims.assign(dims, dims + n_layers + 1);
-    d->relu.assign(relu, relu + n_layers);
-    d->Wt = std::vector<DevBuf>((size_t)n_layers);
-    d->bias = std::vector<DevBuf>((size_t)n_layers);
-    hipStream_t s = ctx->stream;
-    int rc = SSP_OK;
-    for (int l = 0; l < n_layers && rc == SSP_OK; ++l) {
-        const size_t wb = (size_t)dims[l + 1] * dims[l] * sizeof(float);
-        rc = d->Wt[(size_t)l].alloc(wb);
-        if (rc == SSP_OK && hipMemcpyAsync(d->Wt[(size_t)l].p, Wt[l], wb, hipMemcpyHostToDevice, s) != hipSuccess) rc = SSP_ERR_HIP;
-        if (rc == SSP_OK && bias && bias[l]) {
-            rc = d->bias[(size_t)l].alloc((size_t)dims[l + 1] * sizeof(float));
-            if (rc == SSP_OK && hipMemcpyAsync(d->bias[(size_t)l].p, bias[l], (size_t)dims[l + 1] * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess)
-                rc = SSP_ERR_HIP;
-        }
-    }
     // the chain = the longest tail of layers whose input and output widths fit the register-resident form (at most CH_MAXL of them)
     int from = n_layers;
     while (from > 0 && dims[from - 1] <= CH_W && dims[from] <= CH_W && n_layers - (from - 1) <= CH_MAXL) --from;
     if (getenv("SSP_DNN_NO_CHAIN")) from = n_layers;
-    d->chain_from = from;
     const int nc = n_layers - from;
+    std::vector<float> cb((size_t)nc * CH_W, 0.f);  // the chain's biases
+    for (int l = from; l < n_layers; ++l)
+        if (bias && bias[l])
+            for (int u = 0; u < dims[l + 1]; ++u) cb[(size_t)(l - from) * CH_W + u] = bias[l][u];
+    HandleBuild<ssp_dnn> d(ctx, "ssp_dnn_create");
+    d->n_layers = n_layers;
+    d->chain_from = from;
+    d->dims.assign(dims, dims + n_layers + 1);
+    d->relu.assign(relu, relu + n_layers);
+    d->Wt = std::vector<DevBuf>((size_t)n_layers);
+    d->bias = std::vector<DevBuf>((size_t)n_layers);
+    int rc = SSP_OK;
+    for (int l = 0; l < n_layers && rc == SSP_OK; ++l) {
+        rc = upload(d, d->Wt[(size_t)l], Wt[l], (size_t)dims[l + 1] * dims[l]);
+        if (rc == SSP_OK && bias && bias[l]) rc = upload(d, d->bias[(size_t)l], bias[l], (size_t)dims[l + 1]);
+    }
     if (rc == SSP_OK && nc > 0) {
         rc = d->img.alloc((size_t)nc * 16 * CH_TILE * sizeof(float));
-        if (rc == SSP_OK) rc = d->cbias.alloc((size_t)nc * CH_W * sizeof(float));
-        if (rc == SSP_OK) {
-            std::vector<float> cb((size_t)nc * CH_W, 0.f);
-            for (int l = from; l < n_layers; ++l)
-                if (bias && bias[l])
-                    for (int u = 0; u < dims[l + 1]; ++u) cb[(size_t)(l - from) * CH_W + u] = bias[l][u];
-            if (hipMemcpyAsync(d->cbias.p, cb.data(), cb.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess) rc = SSP_ERR_HIP;
-            for (int l = from; l < n_layers && rc == SSP_OK; ++l) {
-                hipLaunchKernelGGL(dnn_pack_kernel, dim3(16 * CH_TILE / 256), dim3(256), 0, s, d->Wt[(size_t)l].as<float>(), dims[l + 1], dims[l],
-                                   d->img.as<float>() + (size_t)(l - from) * 16 * CH_TILE);
-                if (hipGetLastError() != hipSuccess) rc = SSP_ERR_HIP;
+        if (rc == SSP_OK) rc = upload(d, d->cbias, cb);
+        for (int l = from; l < n_layers && rc == SSP_OK; ++l) {
+            hipLaunchKernelGGL(dnn_pack_kernel, dim3(16 * CH_TILE / 256), dim3(256), 0, ctx->stream, d->Wt[(size_t)l].as<float>(), dims[l + 1], dims[l],
+                               d->img.as<float>() + (size_t)(l - from) * 16 * CH_TILE);
+            if (hipGetLastError() != hipSuccess) {
+                set_error("ssp_dnn_create: pack kernel launch failed");
+                rc = SSP_ERR_HIP;
             }
-            if (rc == SSP_OK && hipStreamSynchronize(s) != hipSuccess) rc = SSP_ERR_HIP;  // cb (host) dies at return
         }
-    } else if (rc == SSP_OK && hipStreamSynchronize(s) != hipSuccess) {
-        rc = SSP_ERR_HIP;
     }
-    if (rc != SSP_OK) {
-        if (rc == SSP_ERR_HIP) set_error("ssp_dnn_create: upload / pack failed");
-        delete d;
-        return rc;
-    }
-    *out = d;
-    return SSP_OK;
+    return d.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_dnn_create")
 
-int ssp_dnn_destroy(ssp_dnn* dnn) {
-    if (!dnn) return SSP_OK;
-    ssp::quiesce_ctx(dnn->ctx);  // (the ctx may already be gone: common.hpp)
-    delete dnn;
-    return SSP_OK;
-}
+int ssp_dnn_destroy(ssp_dnn* dnn) { return destroy_handle(dnn); }
 
 int ssp_dnn_forward(ssp_dnn* dnn, const float* X, int64_t N, float* Y, int where, float* kernel_ms) {
     ssp::TraceRange trace_("ssp_dnn_forward");

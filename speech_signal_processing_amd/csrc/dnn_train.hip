@@ -349,7 +349,7 @@ int ssp_dropout_keep(uint64_t seed, int64_t step, int32_t layer, int32_t rows, i
 }
 
 int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, const int32_t* relu, const float* dropout_rate,
-                           const float* const* W, const float* const* bias, int32_t max_batch, ssp_dnn_trainer** out) {
+                           const float* const* W, const float* const* bias, int32_t max_batch, ssp_dnn_trainer** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_create: null out");
     *out = nullptr;
     if (n_layers < 1 || !dims || !relu || !dropout_rate || !W) SSP_FAIL(SSP_ERR_INVALID, "ssp_dnn_trainer_create: null argument or no layer");
@@ -367,9 +367,7 @@ int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, 
     if (max_batch > DT_MAXB) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dnn_trainer_create: max_batch up to %d (got %d)", DT_MAXB, max_batch);
     if (n_layers > 64) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_dnn_trainer_create: up to 64 layers");
     SSP_TRY(use_ctx(ctx));
-    ssp_dnn_trainer* tr = new (std::nothrow) ssp_dnn_trainer;
-    if (!tr) SSP_FAIL(SSP_ERR_NOMEM, "dnn trainer: host alloc");
-    tr->ctx = ctx;
+    HandleBuild<ssp_dnn_trainer> tr(ctx, "ssp_dnn_trainer_create");
     tr->L = n_layers;
     tr->max_batch = max_batch;
     tr->n_class = dims[n_layers];
@@ -395,17 +393,12 @@ int ssp_dnn_trainer_create(ssp_ctx* ctx, int32_t n_layers, const int32_t* dims, 
     }
     int rc = tr->act.alloc((size_t)na * sizeof(float));
     if (rc == SSP_OK) rc = tr->dz.alloc((size_t)na * sizeof(float));
-    if (rc == SSP_OK) rc = tr->alloc_state("ssp_dnn_trainer_create", flat);
-    if (rc == SSP_OK) rc = tr->wait_state("ssp_dnn_trainer_create");
-    if (rc != SSP_OK) {
-        delete tr;
-        return rc;
-    }
-    *out = tr;
-    return SSP_OK;
+    if (rc == SSP_OK) rc = tr->alloc_state(tr, flat);
+    return tr.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_dnn_trainer_create")
 
-int ssp_dnn_trainer_destroy(ssp_dnn_trainer* trainer) { return trainer_destroy(trainer); }
+int ssp_dnn_trainer_destroy(ssp_dnn_trainer* trainer) { return destroy_handle(trainer); }
 
 int ssp_dnn_trainer_epoch(ssp_dnn_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                           float lr, uint64_t seed, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {

@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "handle.hpp"
 
 namespace ssp {
 
@@ -822,7 +823,7 @@ using namespace ssp;
 extern "C" {
 
 int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const double* weights, const double* means,
-                 const double* covars, int32_t has_ubm, ssp_gmm** out) {
+                 const double* covars, int32_t has_ubm, ssp_gmm** out) try {
     ssp::TraceRange trace_("ssp_gmm_pack");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_pack: null out");
     *out = nullptr;
@@ -942,9 +943,7 @@ int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const dou
             btab[d] = std::max(btab[d], (float)(std::fabs(means[mk * D + d]) * P * (1.0 + 1e-6)));
             btab[D + d] = std::max(btab[D + d], (float)(0.5 * P * (1.0 + 1e-6)));
         }
-    ssp_gmm* g = new (std::nothrow) ssp_gmm;
-    if (!g) SSP_FAIL(SSP_ERR_NOMEM, "gmm: host alloc");
-    g->ctx = ctx;
+    HandleBuild<ssp_gmm> g(ctx, "ssp_gmm_pack");
     g->n_models = n_models;
     g->K = K;
     g->D = D;
@@ -952,41 +951,14 @@ int ssp_gmm_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const dou
     g->nq = nq;
     g->tiles_per_model = tpm;
     g->nk16 = nk16;
-    int rc = g->wimg.alloc(img.size() * sizeof(float));
-    if (rc == SSP_OK) rc = g->bound_tab.alloc(btab.size() * sizeof(float));
-    if (rc == SSP_OK && hipMemcpyAsync(g->bound_tab.p, btab.data(), btab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        set_error("gmm: bound table upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc == SSP_OK && nk16 > 0) {
-        rc = g->wimg16.alloc(img16.size());
-        if (rc == SSP_OK && hipMemcpyAsync(g->wimg16.p, img16.data(), img16.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            set_error("gmm: bf16 image upload failed");
-            rc = SSP_ERR_HIP;
-        }
-    }
-    if (rc == SSP_OK) {
-        hipError_t e = hipMemcpyAsync(g->wimg.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gmm: upload failed: %s", hipGetErrorString(e));
-            rc = SSP_ERR_HIP;
-        }
-    }
-    if (rc != SSP_OK) {
-        delete g;
-        return rc;
-    }
-    *out = g;
-    return SSP_OK;
+    int rc = upload(g, g->bound_tab, btab);
+    if (rc == SSP_OK) rc = upload(g, g->wimg16, img16);  // (empty when no bf16 image exists: nk16 == 0)
+    if (rc == SSP_OK) rc = upload(g, g->wimg, img);
+    return g.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_gmm_pack")
 
-int ssp_gmm_destroy(ssp_gmm* gmm) {
-    if (!gmm) return SSP_OK;
-    ssp::quiesce_ctx(gmm->ctx);  // (the ctx may already be gone: common.hpp)
-    delete gmm;
-    return SSP_OK;
-}
+int ssp_gmm_destroy(ssp_gmm* gmm) { return destroy_handle(gmm); }
 
 }  // extern "C"
 

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "handle.hpp"
 
 namespace ssp {
 
@@ -506,7 +507,7 @@ extern "C" int ssp_gmm_full_em_stats(ssp_ctx* ctx, int32_t K, int32_t D, const d
 }
 
 extern "C" int ssp_gmm_full_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int32_t D, const double* weights, const double* means,
-                                 const double* prec_chol, int32_t has_ubm, ssp_gmm_full** out) {
+                                 const double* prec_chol, int32_t has_ubm, ssp_gmm_full** out) try {
     ssp::TraceRange trace_("ssp_gmm_full_pack");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_full_pack: null out");
     *out = nullptr;
@@ -520,36 +521,16 @@ extern "C" int ssp_gmm_full_pack(ssp_ctx* ctx, int32_t n_models, int32_t K, int3
     const size_t par_n = (size_t)n_models * K * g.IMG + (size_t)n_models * K + D;
     std::vector<float> par(par_n, 0.f);
     SSP_TRY(fg_pack("ssp_gmm_full_pack", n_models, K, D, weights, means, prec_chol, nullptr, g, par.data()));
-    ssp_gmm_full* h = new (std::nothrow) ssp_gmm_full;
-    if (!h) SSP_FAIL(SSP_ERR_NOMEM, "host alloc (ssp_gmm_full)");
-    h->ctx = ctx;
+    HandleBuild<ssp_gmm_full> h(ctx, "ssp_gmm_full_pack");
     h->n_models = n_models;
     h->K = K;
     h->D = D;
     h->has_ubm = has_ubm ? 1 : 0;
-    int rc = h->par.alloc(par_n * sizeof(float));
-    if (rc == SSP_OK) {
-        hipError_t e = hipMemcpyAsync(h->par.p, par.data(), par_n * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (par is a local)
-        if (e != hipSuccess) {
-            set_error("ssp_gmm_full_pack: upload failed: %s", hipGetErrorString(e));
-            rc = SSP_ERR_HIP;
-        }
-    }
-    if (rc != SSP_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
-    return SSP_OK;
+    return h.commit(upload(h, h->par, par), out);
 }
+SSP_CREATE_GUARD("ssp_gmm_full_pack")
 
-extern "C" int ssp_gmm_full_destroy(ssp_gmm_full* h) {
-    if (!h) return SSP_OK;
-    quiesce_ctx(h->ctx);
-    delete h;
-    return SSP_OK;
-}
+extern "C" int ssp_gmm_full_destroy(ssp_gmm_full* h) { return destroy_handle(h); }
 
 extern "C" int ssp_gmm_full_score(ssp_gmm_full* h, const float* feats, const ssp_segments* frame_seg, float* loglik_out, float* scores_out,
                                   int32_t* argmax_out, int where, float* kernel_ms) {

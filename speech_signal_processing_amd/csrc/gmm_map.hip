@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "gmm_lp_tile.hpp"
 
 namespace ssp {
@@ -386,7 +387,7 @@ constexpr size_t MAP_LDS_MAX = 160 * 1024;
 extern "C" {
 
 int ssp_gmm_map_pack(ssp_ctx* ctx, int32_t K, int32_t D, const double* ubm_weights, const double* ubm_means, const double* ubm_covars,
-                     int32_t S, const double* spk_means, ssp_gmm_map** out) {
+                     int32_t S, const double* spk_means, ssp_gmm_map** out) try {
     ssp::TraceRange trace_("ssp_gmm_map_pack");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_gmm_map_pack: null out");
     *out = nullptr;
@@ -440,9 +441,7 @@ int ssp_gmm_map_pack(ssp_ctx* ctx, int32_t K, int32_t D, const double* ubm_weigh
             }
             t[(size_t)DP * Sp] = (float)(0.5 * b);
         }
-    ssp_gmm_map* g = new (std::nothrow) ssp_gmm_map;
-    if (!g) SSP_FAIL(SSP_ERR_NOMEM, "gmm map: host alloc");
-    g->ctx = ctx;
+    HandleBuild<ssp_gmm_map> g(ctx, "ssp_gmm_map_pack");
     g->K = K;
     g->D = D;
     g->S = S;
@@ -450,31 +449,13 @@ int ssp_gmm_map_pack(ssp_ctx* ctx, int32_t K, int32_t D, const double* ubm_weigh
     g->DP = DP;
     g->Sp = Sp;
     g->nnz = nnz;
-    int rc = g->par.alloc(par.size() * sizeof(float));
-    if (rc == SSP_OK) rc = g->tab.alloc(tab.size() * sizeof(float));
-    if (rc == SSP_OK) {
-        hipError_t e = hipMemcpyAsync(g->par.p, par.data(), par.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(g->tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            set_error("gmm map: upload failed: %s", hipGetErrorString(e));
-            rc = SSP_ERR_HIP;
-        }
-    }
-    if (rc != SSP_OK) {
-        delete g;
-        return rc;
-    }
-    *out = g;
-    return SSP_OK;
+    int rc = upload(g, g->par, par);
+    if (rc == SSP_OK) rc = upload(g, g->tab, tab);
+    return g.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_gmm_map_pack")
 
-int ssp_gmm_map_destroy(ssp_gmm_map* map) {
-    if (!map) return SSP_OK;
-    ssp::quiesce_ctx(map->ctx);  // (the ctx may already be gone: common.hpp)
-    delete map;
-    return SSP_OK;
-}
+int ssp_gmm_map_destroy(ssp_gmm_map* map) { return destroy_handle(map); }
 
 // every argument check of ssp_gmm_map_score that needs no GPU work
 static int map_check(const ssp_gmm_map* map, const ssp_segments* frame_seg, int32_t C, const char* fn) {

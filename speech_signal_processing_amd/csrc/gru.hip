@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "nn_device.hpp"
 
 namespace ssp {
@@ -249,12 +250,6 @@ static int gru_launch(const GruStepArgs& a, hipStream_t s) {
     return SSP_OK;
 }
 
-static int upload(ssp_ctx* ctx, DevBuf& b, const float* host, size_t n) {
-    SSP_TRY(b.alloc(n * sizeof(float)));
-    SSP_HIP(hipMemcpyAsync(b.p, host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    return SSP_OK;
-}
-
 }  // namespace ssp
 
 struct ssp_gru {
@@ -276,7 +271,7 @@ using namespace ssp;
 extern "C" {
 
 int ssp_gru_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, const float* U, const float* bias,
-                   int32_t recurrent_activation, int32_t reset_after, ssp_gru** out) {
+                   int32_t recurrent_activation, int32_t reset_after, ssp_gru** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_create: null out");
     *out = nullptr;
     if (!W || !U) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_create: null kernel");
@@ -286,13 +281,7 @@ int ssp_gru_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, co
     SSP_TRY(gru_check_shape("ssp_gru_create", d_in, units));
     SSP_TRY(use_ctx(ctx));
     const int H = units, H3 = 3 * units, KG = H / 16, JT = (KG + 1) / 2 * 2;
-    std::vector<float> image, wt, bi(H3, 0.f), br;
-    try {
-        image.assign((size_t)JT * KG * 768, 0.f);
-        wt.resize((size_t)H3 * d_in);
-    } catch (...) {
-        SSP_FAIL(SSP_ERR_NOMEM, "gru: host alloc");
-    }
+    std::vector<float> image((size_t)JT * KG * 768, 0.f), wt((size_t)H3 * d_in), bi(H3, 0.f), br;
     // image[(((j KG + g) 3 + q) 64 + lane) 4 + r] = U[16 g + 4 (lane >> 4) + r][q H + 16 j + (lane & 15)]; the tile that pads an odd
     // count to an even one stays zero
     for (int j = 0; j < KG; ++j)
@@ -308,36 +297,21 @@ int ssp_gru_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, co
         for (int c = 0; c < H3; ++c) bi[c] = bias[c];
         if (reset_after) br.assign(bias + H3, bias + 2 * H3);
     }
-    ssp_gru* m = new (std::nothrow) ssp_gru;
-    if (!m) SSP_FAIL(SSP_ERR_NOMEM, "gru: host alloc");
-    m->ctx = ctx;
+    HandleBuild<ssp_gru> m(ctx, "ssp_gru_create");
     m->d_in = d_in;
     m->units = units;
     m->act = recurrent_activation;
     m->reset_after = reset_after;
     m->has_rbias = !br.empty();
-    int rc = upload(ctx, m->img, image.data(), image.size());
-    if (rc == SSP_OK) rc = upload(ctx, m->Wt, wt.data(), wt.size());
-    if (rc == SSP_OK) rc = upload(ctx, m->bin, bi.data(), bi.size());
-    if (rc == SSP_OK && m->has_rbias) rc = upload(ctx, m->brec, br.data(), br.size());
-    if (rc == SSP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {  // (the host images die at return)
-        set_error("ssp_gru_create: upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc != SSP_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return SSP_OK;
+    int rc = upload(m, m->img, image);
+    if (rc == SSP_OK) rc = upload(m, m->Wt, wt);
+    if (rc == SSP_OK) rc = upload(m, m->bin, bi);
+    if (rc == SSP_OK) rc = upload(m, m->brec, br);  // (empty without a recurrent bias)
+    return m.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_gru_create")
 
-int ssp_gru_destroy(ssp_gru* gru) {
-    if (!gru) return SSP_OK;
-    ssp::quiesce_ctx(gru->ctx);
-    delete gru;
-    return SSP_OK;
-}
+int ssp_gru_destroy(ssp_gru* gru) { return destroy_handle(gru); }
 
 int ssp_gru_set_workspace(ssp_gru* gru, size_t bytes) {
     if (!gru) SSP_FAIL(SSP_ERR_INVALID, "ssp_gru_set_workspace: null handle");

@@ -611,7 +611,7 @@ extern "C" {
 int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32_t kw, int32_t F, int32_t sh, int32_t sw, const float* conv_K,
                            const float* conv_b, int32_t n_gru, const int32_t* units, const float* const* W, const float* const* U,
                            const float* const* bias, int32_t E, const float* dense_W, const float* dense_b, int32_t n_class, const float* head_W,
-                           const float* head_b, int32_t recurrent_activation, int32_t reset_after, int32_t max_batch, ssp_gru_trainer** out) {
+                           const float* head_b, int32_t recurrent_activation, int32_t reset_after, int32_t max_batch, ssp_gru_trainer** out) try {
     const char* who = "ssp_gru_trainer_create";
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "%s: null out", who);
     *out = nullptr;
@@ -652,9 +652,7 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
         SSP_FAIL(SSP_ERR_UNSUPPORTED, "%s: the workspace of one step would be %.2f GiB, above the cap of %.0f GiB: lower max_batch", who,
                  (double)ws / (double)((size_t)1 << 30), (double)GT_WS_CAP / (double)((size_t)1 << 30));
     SSP_TRY(use_ctx(ctx));
-    ssp_gru_trainer* tr = new (std::nothrow) ssp_gru_trainer;
-    if (!tr) SSP_FAIL(SSP_ERR_NOMEM, "gru trainer: host alloc");
-    tr->ctx = ctx;
+    HandleBuild<ssp_gru_trainer> tr(ctx, who);
     tr->T = T, tr->D = D, tr->kh = kh, tr->kw = kw, tr->F = F, tr->sh = sh, tr->sw = sw, tr->To = To, tr->Do = Do, tr->d0 = (int32_t)d0;
     const int ph = (To - 1) * sh + kh - T, pw = (Do - 1) * sw + kw - D;  // TensorFlow's `same`: the smaller half goes in front
     tr->pt = (ph > 0 ? ph : 0) / 2, tr->pl = (pw > 0 ? pw : 0) / 2;
@@ -708,18 +706,13 @@ int ssp_gru_trainer_create(ssp_ctx* ctx, int32_t T, int32_t D, int32_t kh, int32
     if (rc == SSP_OK) rc = tr->l2s.alloc(mb * f4);
     if (rc == SSP_OK) rc = tr->logits.alloc(mb * n_class * f4);
     if (rc == SSP_OK) rc = tr->cpart.alloc((size_t)(kh * kw + 1) * GT_CCH * F * f4);
-    if (rc == SSP_OK) rc = tr->alloc_state(who, flat);
-    if (rc == SSP_OK) rc = gt_pack(tr, ctx->stream);  // (queued behind the upload: one host wait for both)
-    if (rc == SSP_OK) rc = tr->wait_state(who);
-    if (rc != SSP_OK) {
-        delete tr;
-        return rc;
-    }
-    *out = tr;
-    return SSP_OK;
+    if (rc == SSP_OK) rc = tr->alloc_state(tr, flat);
+    if (rc == SSP_OK) rc = gt_pack(tr.get(), ctx->stream);  // (queued behind the upload: one host wait for both)
+    return tr.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_gru_trainer_create")
 
-int ssp_gru_trainer_destroy(ssp_gru_trainer* trainer) { return trainer_destroy(trainer); }
+int ssp_gru_trainer_destroy(ssp_gru_trainer* trainer) { return destroy_handle(trainer); }
 
 int ssp_gru_trainer_epoch(ssp_gru_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                           float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {

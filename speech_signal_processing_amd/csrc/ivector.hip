@@ -22,6 +22,7 @@
 #include <thread>
 
 #include "common.hpp"
+#include "handle.hpp"
 
 namespace ssp {
 
@@ -510,7 +511,7 @@ static int iv_run(ssp_ivector* iv, const char* fn, const double* nk, const doubl
 extern "C" {
 
 int ssp_ivector_create(ssp_ctx* ctx, int32_t K, int32_t D, int32_t R, const double* ubm_means, const double* ubm_covars, const double* T,
-                       ssp_ivector** out) {
+                       ssp_ivector** out) try {
     ssp::TraceRange trace_("ssp_ivector_create");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_ivector_create: null out");
     *out = nullptr;
@@ -530,38 +531,23 @@ int ssp_ivector_create(ssp_ctx* ctx, int32_t K, int32_t D, int32_t R, const doub
     for (size_t i = 0; i < KD * R; ++i)
         if (!std::isfinite(T[i])) SSP_FAIL(SSP_ERR_INVALID, "ssp_ivector_create: non-finite entry in T (mixture %lld)", (long long)(i / ((size_t)D * R)));
     SSP_TRY(use_ctx(ctx));
-    ssp_ivector* iv = new (std::nothrow) ssp_ivector;
-    if (!iv) SSP_FAIL(SSP_ERR_NOMEM, "ivector: host alloc");
-    iv->ctx = ctx;
+    HandleBuild<ssp_ivector> iv(ctx, "ssp_ivector_create");
     iv->K = K;
     iv->D = D;
     iv->R = R;
     iv->tri = R * (R + 1) / 2;
     iv->mu.assign(ubm_means, ubm_means + KD);
     int rc = iv->T64.alloc(KD * R * sizeof(double));
-    if (rc == SSP_OK) rc = iv->icv.alloc(KD * sizeof(double));
+    if (rc == SSP_OK) rc = upload(iv, iv->icv, icv);
     if (rc == SSP_OK) rc = iv->P.alloc((size_t)K * iv->tri * sizeof(float));
     if (rc == SSP_OK) rc = iv->G.alloc(KD * R * sizeof(float));
-    if (rc == SSP_OK && hipMemcpyAsync(iv->icv.p, icv.data(), KD * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        set_error("ivector: upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc == SSP_OK) rc = iv_upload_T(iv, T);  // (waits for the stream: icv may go)
-    if (rc != SSP_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        delete iv;
-        return rc;
-    }
-    *out = iv;
-    return SSP_OK;
+    if (rc == SSP_OK) rc = iv_upload_T(iv.get(), T);
+    if (rc == SSP_OK) iv.waited();  // (iv_upload_T ends in the create's one host wait)
+    return iv.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_ivector_create")
 
-int ssp_ivector_destroy(ssp_ivector* iv) {
-    if (!iv) return SSP_OK;
-    ssp::quiesce_ctx(iv->ctx);  // (the ctx may already be gone: common.hpp)
-    delete iv;
-    return SSP_OK;
-}
+int ssp_ivector_destroy(ssp_ivector* iv) { return destroy_handle(iv); }
 
 int ssp_ivector_set_t(ssp_ivector* iv, const double* T) {
     ssp::TraceRange trace_("ssp_ivector_set_t");

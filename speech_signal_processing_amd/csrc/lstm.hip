@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "nn_device.hpp"
 
 namespace ssp {
@@ -257,7 +258,7 @@ int ssp_lstm_pack_weights(int32_t d_in, int32_t units, const float* W, const flo
 }
 
 int ssp_lstm_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, const float* U, const float* bias,
-                    int32_t recurrent_activation, ssp_lstm** out) {
+                    int32_t recurrent_activation, ssp_lstm** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_create: null out");
     *out = nullptr;
     if (!W || !U) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_create: null kernel");
@@ -267,41 +268,19 @@ int ssp_lstm_create(ssp_ctx* ctx, int32_t d_in, int32_t units, const float* W, c
     SSP_TRY(use_ctx(ctx));
     int64_t nf = 0;
     SSP_TRY(ssp_lstm_pack_weights(d_in, units, nullptr, nullptr, nullptr, nullptr, &nf));
-    std::vector<float> image;
-    try {
-        image.resize((size_t)nf);
-    } catch (...) {
-        SSP_FAIL(SSP_ERR_NOMEM, "lstm: host alloc");
-    }
+    std::vector<float> image((size_t)nf);
     SSP_TRY(ssp_lstm_pack_weights(d_in, units, W, U, bias, image.data(), nullptr));
-    ssp_lstm* m = new (std::nothrow) ssp_lstm;
-    if (!m) SSP_FAIL(SSP_ERR_NOMEM, "lstm: host alloc");
-    m->ctx = ctx;
+    HandleBuild<ssp_lstm> m(ctx, "ssp_lstm_create");
     m->d_in = d_in;
     m->units = units;
     m->act = recurrent_activation;
     m->HT = lstm_tiles(units);
     m->dT = (d_in + 15) / 16;
-    int rc = m->img.alloc((size_t)nf * sizeof(float));
-    if (rc == SSP_OK && (hipMemcpyAsync(m->img.p, image.data(), (size_t)nf * sizeof(float), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                         hipStreamSynchronize(ctx->stream) != hipSuccess)) {  // (image, on the host, dies at return)
-        set_error("ssp_lstm_create: upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc != SSP_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return SSP_OK;
+    return m.commit(upload(m, m->img, image), out);
 }
+SSP_CREATE_GUARD("ssp_lstm_create")
 
-int ssp_lstm_destroy(ssp_lstm* lstm) {
-    if (!lstm) return SSP_OK;
-    ssp::quiesce_ctx(lstm->ctx);  // (the ctx may already be gone: common.hpp)
-    delete lstm;
-    return SSP_OK;
-}
+int ssp_lstm_destroy(ssp_lstm* lstm) { return destroy_handle(lstm); }
 
 int ssp_lstm_forward(ssp_lstm* lstm, const float* feats, const ssp_segments* frame_seg, float* h_out, int where, float* kernel_ms) {
     ssp::TraceRange trace_("ssp_lstm_forward");

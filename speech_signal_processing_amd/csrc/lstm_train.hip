@@ -398,7 +398,7 @@ int lt_step(ssp_lstm_trainer* tr, const float* X, const int32_t* labels, const i
 extern "C" {
 
 int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n_class, int32_t T, int32_t recurrent_activation, const float* W,
-                            const float* U, const float* bias, const float* Wd, const float* bd, int32_t max_batch, ssp_lstm_trainer** out) {
+                            const float* U, const float* bias, const float* Wd, const float* bd, int32_t max_batch, ssp_lstm_trainer** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_create: null out");
     *out = nullptr;
     if (!W || !U || !Wd) SSP_FAIL(SSP_ERR_INVALID, "ssp_lstm_trainer_create: null kernel");
@@ -412,9 +412,7 @@ int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n
     if (n_class < 2 || n_class > LT_MAXC) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_lstm_trainer_create: n_class in [2, %d] (got %d)", LT_MAXC, n_class);
     if (max_batch < 1 || max_batch > LT_MAXB) SSP_FAIL(SSP_ERR_UNSUPPORTED, "ssp_lstm_trainer_create: max_batch in [1, %d] (got %d)", LT_MAXB, max_batch);
     SSP_TRY(use_ctx(ctx));
-    ssp_lstm_trainer* tr = new (std::nothrow) ssp_lstm_trainer;
-    if (!tr) SSP_FAIL(SSP_ERR_NOMEM, "lstm trainer: host alloc");
-    tr->ctx = ctx;
+    HandleBuild<ssp_lstm_trainer> tr(ctx, "ssp_lstm_trainer_create");
     tr->D = d_in, tr->H = units, tr->n_class = n_class, tr->T = T, tr->act = recurrent_activation, tr->max_batch = max_batch;
     tr->has_b = bias != nullptr, tr->has_bd = bd != nullptr;
     const int64_t H4 = 4 * (int64_t)units;
@@ -433,17 +431,12 @@ int ssp_lstm_trainer_create(ssp_ctx* ctx, int32_t d_in, int32_t units, int32_t n
     if (rc == SSP_OK) rc = tr->hlast.alloc((size_t)max_batch * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->dH.alloc((size_t)max_batch * units * sizeof(float));
     if (rc == SSP_OK) rc = tr->logits.alloc((size_t)max_batch * n_class * sizeof(float));
-    if (rc == SSP_OK) rc = tr->alloc_state("ssp_lstm_trainer_create", flat);
-    if (rc == SSP_OK) rc = tr->wait_state("ssp_lstm_trainer_create");
-    if (rc != SSP_OK) {
-        delete tr;
-        return rc;
-    }
-    *out = tr;
-    return SSP_OK;
+    if (rc == SSP_OK) rc = tr->alloc_state(tr, flat);
+    return tr.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_lstm_trainer_create")
 
-int ssp_lstm_trainer_destroy(ssp_lstm_trainer* trainer) { return trainer_destroy(trainer); }
+int ssp_lstm_trainer_destroy(ssp_lstm_trainer* trainer) { return destroy_handle(trainer); }
 
 int ssp_lstm_trainer_epoch(ssp_lstm_trainer* trainer, const float* X, const int32_t* labels, int64_t N, const int64_t* order, int32_t batch_size,
                            float lr, double* loss_sum, int64_t* n_correct, int where, float* kernel_ms) {

@@ -4,6 +4,7 @@
 #include <cstdlib>
 
 #include "mfcc.hpp"
+#include "handle.hpp"
 
 namespace ssp {
 
@@ -34,13 +35,6 @@ static int64_t frames_for(const ssp_mfcc_cfg& c, int64_t n) {
         case 1: return (n + c.hop - 1) / c.hop;                          // utils/processing.py:27 ceil(wlen/step)
         default: return n <= 0 ? 0 : 1 + n / c.hop;                      // librosa stft(center=True)
     }
-}
-
-template <class T>
-static int upload(DevBuf& b, const std::vector<T>& v, hipStream_t s) {
-    SSP_TRY(b.alloc(sizeof(T) * v.size()));
-    if (!v.empty()) SSP_HIP(hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s));
-    return SSP_OK;
 }
 
 static size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
@@ -232,8 +226,9 @@ static int build_work(ssp_mfcc_plan* p, const ssp_segments* sseg, const ssp_segm
     }
     if (chunks.size() > (size_t)INT32_MAX) SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc: too many chunks");
     p->cache_chunk_first[(size_t)fseg->n] = (int32_t)chunks.size();
-    SSP_TRY(upload(p->chunks, chunks, p->ctx->stream));
     std::vector<StreamChunkRec> recs;
+    UploadScope q(p->ctx, "mfcc work table");  // (`chunks` and `recs`, on the host, outlive it: every way out waits for their copies)
+    SSP_TRY(upload(q, p->chunks, chunks.data(), chunks.size()));
     if (variant == 3) {  // (mfcc_stream_kernel.hpp: the fixed-geometry instances start a chunk from this record)
         recs.reserve(chunks.size());
         for (const MfccChunk& k : chunks) {
@@ -241,9 +236,9 @@ static int build_work(ssp_mfcc_plan* p, const ssp_segments* sseg, const ssp_segm
             const int64_t f0 = fseg->host[(size_t)k.utt], T = fseg->host[(size_t)k.utt + 1] - f0;
             recs.push_back(StreamChunkRec{s0, f0, (int32_t)std::min<int64_t>(N * 4, INT32_MAX), (int32_t)T, k.t0, k.n | (k.pad << 16)});
         }
-        SSP_TRY(upload(p->chunk_rec, recs, p->ctx->stream));
+        SSP_TRY(upload(q, p->chunk_rec, recs.data(), recs.size()));
     }
-    SSP_HIP(hipStreamSynchronize(p->ctx->stream));  // `chunks` and `recs` (host) die at return
+    SSP_TRY(q.wait());
     p->fast_max_samples = sseg->max_len();
     p->cache_n_chunks = (int32_t)chunks.size();
     p->cache_chunk_frames = ch;
@@ -277,16 +272,14 @@ int ssp_mfcc_out_dim(const ssp_mfcc_cfg* cfg, int32_t* d_out) {
 }
 
 int ssp_mfcc_plan_create(ssp_ctx* ctx, const ssp_mfcc_cfg* cfg, const float* window, const float* fbank,
-                         const float* dct, ssp_mfcc_plan** out) {
+                         const float* dct, ssp_mfcc_plan** out) try {
     ssp::TraceRange trace_("ssp_mfcc_plan_create");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_plan_create: null out");
     *out = nullptr;
     SSP_TRY(use_ctx(ctx));
     SSP_TRY(validate_cfg(cfg));
     if (!window || !fbank || !dct) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_plan_create: null table");
-    ssp_mfcc_plan* p = new (std::nothrow) ssp_mfcc_plan;
-    if (!p) SSP_FAIL(SSP_ERR_NOMEM, "mfcc plan: host alloc");
-    p->ctx = ctx;
+    HandleBuild<ssp_mfcc_plan> p(ctx, "ssp_mfcc_plan_create");
     p->cfg = *cfg;
     p->d_out = cfg->n_ceps * (1 + cfg->delta_order);
     const int n_fft = cfg->n_fft, nb = n_fft / 2 + 1;
@@ -343,11 +336,9 @@ int ssp_mfcc_plan_create(ssp_ctx* ctx, const ssp_mfcc_cfg* cfg, const float* win
         }
         const int nl = j1 - g * 64;
         for (int j = g * 64; j < j1; ++j)
-            if (lo4[j] + 4 * steps > buf_floats || len[j] + (lo[j] - lo4[j]) > 4 * steps) {
-                delete p;
+            if (lo4[j] + 4 * steps > buf_floats || len[j] + (lo[j] - lo4[j]) > 4 * steps)
                 SSP_FAIL(SSP_ERR_UNSUPPORTED, "mfcc: filter %d (bins %d..%d) next to %d-tap filters does not fit the kernel's spectrum row",
                          j, lo[j], lo[j] + len[j] - 1, taps);
-            }
         grp[g] = steps;
         grp[8 + g] = (int32_t)(wT.size() / 4);
         const size_t base = wT.size();
@@ -373,29 +364,22 @@ int ssp_mfcc_plan_create(ssp_ctx* ctx, const ssp_mfcc_cfg* cfg, const float* win
         for (int j = 0; j < cfg->n_filt; ++j) dctT[(size_t)j * cfg->n_ceps + q] = dct[(size_t)q * cfg->n_filt + j];
     std::vector<float> dctv(dct, dct + (size_t)cfg->n_ceps * cfg->n_filt);
     std::vector<float> dense(fbank, fbank + (size_t)cfg->n_filt * nb);
-    hipStream_t s = ctx->stream;
-    int rc = upload(p->window, win, s);
-    if (rc == SSP_OK) rc = upload(p->twiddle, tw, s);
-    if (rc == SSP_OK) rc = upload(p->filt_lo4, lo4, s);
-    if (rc == SSP_OK) rc = upload(p->filt_grp, grp, s);
-    if (rc == SSP_OK) rc = upload(p->filt_wT, wT, s);
-    if (rc == SSP_OK) rc = upload(p->dct, dctv, s);
-    if (rc == SSP_OK) rc = upload(p->dctT, dctT, s);
-    if (rc == SSP_OK) rc = upload(p->fbank_dense, dense, s);
-    if (rc == SSP_OK && hipStreamSynchronize(s) != hipSuccess) {
-        set_error("mfcc plan: table upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc == SSP_OK) rc = build_s2k_tables(p);  // (n_fft == 2048 without deltas; leaves s2k_ready false otherwise)
+    int rc = upload(p, p->window, win);
+    if (rc == SSP_OK) rc = upload(p, p->twiddle, tw);
+    if (rc == SSP_OK) rc = upload(p, p->filt_lo4, lo4);
+    if (rc == SSP_OK) rc = upload(p, p->filt_grp, grp);
+    if (rc == SSP_OK) rc = upload(p, p->filt_wT, wT);
+    if (rc == SSP_OK) rc = upload(p, p->dct, dctv);
+    if (rc == SSP_OK) rc = upload(p, p->dctT, dctT);
+    if (rc == SSP_OK) rc = upload(p, p->fbank_dense, dense);
+    if (rc == SSP_OK) rc = p.wait();  // (the create's one host wait: the kernels' own tables below are made from the uploaded ones)
+    if (rc == SSP_OK) rc = build_s2k_tables(p.get());  // (n_fft == 2048 without deltas; leaves s2k_ready false otherwise)
     if (rc == SSP_OK && mfcc_fast_supported(*cfg)) {
-        const int frc = build_fast_tables(p);  // a filterbank the fused kernel cannot lay out only disables that kernel
+        const int frc = build_fast_tables(p.get());  // a filterbank the fused kernel cannot lay out only disables that kernel
         if (frc != SSP_OK && frc != SSP_ERR_UNSUPPORTED) rc = frc;
-        if (frc == SSP_OK && mfcc_stream_supported(p)) rc = build_stream_tables(p);
+        if (frc == SSP_OK && mfcc_stream_supported(p.get())) rc = build_stream_tables(p.get());
     }
-    if (rc != SSP_OK) {
-        delete p;
-        return rc;
-    }
+    if (rc != SSP_OK) return p.commit(rc, out);
     MfccArgs& a = p->args;
     a.window = p->window.as<float>();
     a.twiddle = p->twiddle.as<float2>();
@@ -425,16 +409,11 @@ int ssp_mfcc_plan_create(ssp_ctx* ctx, const ssp_mfcc_cfg* cfg, const float* win
     int den = 0;
     for (int i = 1; i <= a.delta_N; ++i) den += 2 * i * i;  // GMM_UBM.py:61
     a.delta_inv_denom = den > 0 ? 1.0f / (float)den : 0.f;
-    *out = p;
-    return SSP_OK;
+    return p.commit(SSP_OK, out);
 }
+SSP_CREATE_GUARD("ssp_mfcc_plan_create")
 
-int ssp_mfcc_plan_destroy(ssp_mfcc_plan* plan) {
-    if (!plan) return SSP_OK;
-    ssp::quiesce_ctx(plan->ctx);  // (the ctx may already be gone: common.hpp)
-    delete plan;
-    return SSP_OK;
-}
+int ssp_mfcc_plan_destroy(ssp_mfcc_plan* plan) { return destroy_handle(plan); }
 
 int ssp_mfcc_plan_set_flags(ssp_mfcc_plan* plan, uint32_t flags) {
     if (!plan) SSP_FAIL(SSP_ERR_INVALID, "ssp_mfcc_plan_set_flags: null");

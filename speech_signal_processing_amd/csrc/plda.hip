@@ -23,6 +23,7 @@
 #include <map>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "reg_sweep.hpp"  // the operand staging and the LDS-DMA that this sweep shares with cosine_reg_kernel
 
 namespace ssp {
@@ -449,7 +450,7 @@ int ssp_plda_stats(ssp_ctx* ctx, const float* X, const int32_t* labels, int64_t 
 }
 
 int ssp_plda_pack(ssp_ctx* ctx, int32_t q, const double* psi, int32_t S, const double* enrol_mean, const int32_t* enrol_count, int32_t flags,
-                  ssp_plda** out) {
+                  ssp_plda** out) try {
     ssp::TraceRange trace_("ssp_plda_pack");
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_pack: null out");
     *out = nullptr;
@@ -503,43 +504,21 @@ int ssp_plda_pack(ssp_ctx* ctx, int32_t q, const double* psi, int32_t S, const d
         }
         cs[(size_t)s] = (float)(-0.5 * c);
     }
-    ssp_plda* p = new (std::nothrow) ssp_plda;
-    if (!p) SSP_FAIL(SSP_ERR_NOMEM, "plda: host alloc");
-    p->ctx = ctx;
+    HandleBuild<ssp_plda> p(ctx, "ssp_plda_pack");
     p->q = q;
     p->S = S;
     p->nq = nq;
     p->n_tiles = n_tiles;
     p->G = G;
     p->shared = shared;
-    hipStream_t st = ctx->stream;
-    {
-        int rc = p->img.alloc(img.size() * sizeof(float));
-        if (rc == SSP_OK) rc = p->c.alloc(cs.size() * sizeof(float));
-        if (rc == SSP_OK) rc = p->cls.alloc(cls.size() * sizeof(int32_t));
-        if (rc == SSP_OK && (hipMemcpyAsync(p->img.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-                             hipMemcpyAsync(p->c.p, cs.data(), cs.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
-                             hipMemcpyAsync(p->cls.p, cls.data(), cls.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess ||
-                             hipStreamSynchronize(st) != hipSuccess)) {
-            set_error("ssp_plda_pack: upload failed");
-            rc = SSP_ERR_HIP;
-        }
-        if (rc != SSP_OK) {
-            (void)hipStreamSynchronize(st);
-            delete p;
-            return rc;
-        }
-    }
-    *out = p;
-    return SSP_OK;
+    int rc = upload(p, p->img, img);
+    if (rc == SSP_OK) rc = upload(p, p->c, cs);
+    if (rc == SSP_OK) rc = upload(p, p->cls, cls);
+    return p.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_plda_pack")
 
-int ssp_plda_destroy(ssp_plda* p) {
-    if (!p) return SSP_OK;
-    ssp::quiesce_ctx(p->ctx);  // (the ctx may already be gone: common.hpp)
-    delete p;
-    return SSP_OK;
-}
+int ssp_plda_destroy(ssp_plda* p) { return destroy_handle(p); }
 
 int ssp_plda_info(const ssp_plda* p, int32_t* n_classes, int32_t* class_shared) {
     if (!p || !n_classes || !class_shared) SSP_FAIL(SSP_ERR_INVALID, "ssp_plda_info: null argument");

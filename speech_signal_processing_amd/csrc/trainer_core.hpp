@@ -6,6 +6,7 @@
 
 #include "common.hpp"
 #include "dnn_train.hpp"
+#include "handle.hpp"
 
 namespace ssp {
 
@@ -23,13 +24,13 @@ struct TrainerCore {
         return SSP_OK;
     }
 
-    // the flat buffers, the loss buffers and 4096 slots (an epoch of up to 4096 steps allocates nothing), then the upload of `flat` and
-    // the memsets, queued on the ctx stream.  No host wait: the caller synchronises once, after whatever else it queues (`flat` lives
+    // the upload of `flat`, the other flat buffers, the loss buffers and 4096 slots (an epoch of up to 4096 steps allocates nothing), and
+    // the memsets, queued on the ctx stream.  No host wait: the create's commit waits once, after whatever else it queues (`flat` lives
     // until then)
-    int alloc_state(const char* who, const std::vector<float>& flat) {
+    int alloc_state(UploadScope& q, const std::vector<float>& flat) {
         n_params = (int64_t)flat.size();
         const size_t pb = flat.size() * sizeof(float);
-        SSP_TRY(P.alloc(pb));
+        SSP_TRY(upload(q, P, flat.data(), flat.size()));
         SSP_TRY(G.alloc(pb));
         SSP_TRY(Mo.alloc(pb));
         SSP_TRY(Vo.alloc(pb));
@@ -37,17 +38,10 @@ struct TrainerCore {
         SSP_TRY(rowcorr.alloc((size_t)max_batch * sizeof(int32_t)));
         SSP_TRY(ticket.alloc(sizeof(uint32_t)));
         SSP_TRY(slots(4096));
-        hipStream_t s = ctx->stream;
-        if (hipMemcpyAsync(P.p, flat.data(), pb, hipMemcpyHostToDevice, s) != hipSuccess || hipMemsetAsync(G.p, 0, pb, s) != hipSuccess ||
-            hipMemsetAsync(Mo.p, 0, pb, s) != hipSuccess || hipMemsetAsync(Vo.p, 0, pb, s) != hipSuccess ||
-            hipMemsetAsync(ticket.p, 0, sizeof(uint32_t), s) != hipSuccess)
-            SSP_FAIL(SSP_ERR_HIP, "%s: upload failed", who);
-        return SSP_OK;
-    }
-
-    // the host wait that ends a create
-    int wait_state(const char* who) {
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "%s: upload failed", who);
+        hipError_t e = hipMemsetAsync(ticket.p, 0, sizeof(uint32_t), ctx->stream);
+        for (const DevBuf* z : {&G, &Mo, &Vo})
+            if (e == hipSuccess) e = hipMemsetAsync(z->p, 0, pb, ctx->stream);
+        if (e != hipSuccess) SSP_FAIL(SSP_ERR_HIP, "%s: upload failed: %s", q.who, hipGetErrorString(e));
         return SSP_OK;
     }
 
@@ -111,14 +105,6 @@ struct TrainerCore {
 inline int trainer_steps(const char* who, const TrainerCore* c, int64_t* t) {
     if (!c || !t) SSP_FAIL(SSP_ERR_INVALID, "%s: null argument", who);
     *t = c->t;
-    return SSP_OK;
-}
-
-template <class Trainer>
-int trainer_destroy(Trainer* tr) {
-    if (!tr) return SSP_OK;
-    quiesce_ctx(tr->ctx);
-    delete tr;
     return SSP_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "handle.hpp"
 #include "gemm128.hpp"
 
 namespace ssp {
@@ -171,12 +172,6 @@ struct XvLayer {
     DevBuf W, bias, scale, offset;  // (bias / scale / offset: empty = none)
 };
 
-static int xv_upload(ssp_ctx* ctx, DevBuf& b, const float* host, size_t n) {
-    SSP_TRY(b.alloc(n * sizeof(float)));
-    SSP_HIP(hipMemcpyAsync(b.p, host, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    return SSP_OK;
-}
-
 }  // namespace ssp
 
 struct ssp_xvector {
@@ -282,7 +277,7 @@ int ssp_stats_pool(ssp_ctx* ctx, const float* X, const ssp_segments* frame_seg, 
 int ssp_xvector_create(ssp_ctx* ctx, int32_t d_in, int32_t n_frame_layers, const int32_t* units, const int32_t* taps, const int32_t* dilation,
                        const float* const* W, const float* const* bias, const int32_t* relu, const float* const* scale, const float* const* offset,
                        int32_t n_segment_layers, const int32_t* seg_units, const float* const* seg_W, const float* const* seg_bias,
-                       const int32_t* seg_relu, const float* const* seg_scale, const float* const* seg_offset, double var_floor, ssp_xvector** out) {
+                       const int32_t* seg_relu, const float* const* seg_scale, const float* const* seg_offset, double var_floor, ssp_xvector** out) try {
     if (!out) SSP_FAIL(SSP_ERR_INVALID, "ssp_xvector_create: null out");
     *out = nullptr;
     if (n_frame_layers < 1 || n_segment_layers < 0 || !units || !taps || !dilation || !W || !relu)
@@ -308,29 +303,22 @@ int ssp_xvector_create(ssp_ctx* ctx, int32_t d_in, int32_t n_frame_layers, const
         d = seg_units[l];
     }
     SSP_TRY(use_ctx(ctx));
-    ssp_xvector* m = new (std::nothrow) ssp_xvector;
-    if (!m) SSP_FAIL(SSP_ERR_NOMEM, "xvector: host alloc");
-    m->ctx = ctx;
+    HandleBuild<ssp_xvector> m(ctx, "ssp_xvector_create");
     m->d_in = d_in;
     m->receptive = (int32_t)R;
     m->pooled = pooled;
     m->embed = d;
     m->var_floor = var_floor;
     int rc = SSP_OK;
-    try {
-        m->frame = std::vector<XvLayer>((size_t)n_frame_layers);
-        m->segment = std::vector<XvLayer>((size_t)n_segment_layers);
-    } catch (...) {
-        delete m;
-        SSP_FAIL(SSP_ERR_NOMEM, "xvector: host alloc");
-    }
+    m->frame = std::vector<XvLayer>((size_t)n_frame_layers);
+    m->segment = std::vector<XvLayer>((size_t)n_segment_layers);
     auto fill = [&](XvLayer& L, int32_t din, int32_t u, int32_t tp, int32_t dl, int32_t rl, const float* w, const float* b, const float* sc,
                     const float* of) -> int {
         L.d_in = din, L.units = u, L.taps = tp, L.dil = dl, L.relu = rl ? 1 : 0;
-        SSP_TRY(xv_upload(ctx, L.W, w, (size_t)u * tp * din));
-        if (b) SSP_TRY(xv_upload(ctx, L.bias, b, (size_t)u));
-        if (sc) SSP_TRY(xv_upload(ctx, L.scale, sc, (size_t)u));
-        if (of) SSP_TRY(xv_upload(ctx, L.offset, of, (size_t)u));
+        SSP_TRY(upload(m, L.W, w, (size_t)u * tp * din));
+        if (b) SSP_TRY(upload(m, L.bias, b, (size_t)u));
+        if (sc) SSP_TRY(upload(m, L.scale, sc, (size_t)u));
+        if (of) SSP_TRY(upload(m, L.offset, of, (size_t)u));
         return SSP_OK;
     };
     d = d_in;
@@ -346,24 +334,11 @@ int ssp_xvector_create(ssp_ctx* ctx, int32_t d_in, int32_t n_frame_layers, const
                   seg_scale ? seg_scale[l] : nullptr, seg_offset ? seg_offset[l] : nullptr);
         d = seg_units[l];
     }
-    if (rc == SSP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {  // (the caller's host arrays may die at return)
-        set_error("ssp_xvector_create: upload failed");
-        rc = SSP_ERR_HIP;
-    }
-    if (rc != SSP_OK) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return SSP_OK;
+    return m.commit(rc, out);
 }
+SSP_CREATE_GUARD("ssp_xvector_create")
 
-int ssp_xvector_destroy(ssp_xvector* xv) {
-    if (!xv) return SSP_OK;
-    ssp::quiesce_ctx(xv->ctx);  // (the ctx may already be gone: common.hpp)
-    delete xv;
-    return SSP_OK;
-}
+int ssp_xvector_destroy(ssp_xvector* xv) { return destroy_handle(xv); }
 
 int ssp_xvector_info(const ssp_xvector* xv, int32_t* receptive_field, int32_t* pooled_width, int32_t* embed_width) {
     if (!xv) SSP_FAIL(SSP_ERR_INVALID, "ssp_xvector_info: null handle");

@@ -394,6 +394,27 @@ def test_stage_scope_under_address_sanitizer(tmp_path):
     assert "stage_scope: 0 failed checks" in r.stdout
 
 
+def test_handle_life_under_address_sanitizer(tmp_path):
+    """how every C-ABI handle is born and dies (csrc/handle.hpp: upload, HandleBuildT, destroy_handle_on, SSP_CREATE_GUARD), driven
+    without a HIP runtime by tests/native/handle_life.cpp (a malloc-backed runtime stand-in that logs allocations, queued copies, waits,
+    quiet waits and destructor calls and fails the k-th allocation, the k-th copy or the wait on request), compiled with
+    -fsanitize=address,undefined and run as a process of its own: a three-buffer create waits once, behind its last copy, and hands the
+    handle out; a failed allocation or copy stops the create, waits quietly if and only if a copy was queued, then deletes the handle
+    once and leaves *out null and the first failure's message; a failed final wait names the entry point; a builder dropped without a
+    commit and a body that throws std::bad_alloc clean up the same way and leak nothing; destroy quiesces, then deletes; a null handle
+    and an empty table are no-ops."""
+    import subprocess
+    exe = str(tmp_path / "handle_life_asan")
+    src = os.path.join(ROOT, "tests", "native", "handle_life.cpp")
+    b = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", src, "-o", exe],
+                       capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    assert "handle_life: 0 failed checks" in r.stdout
+
+
 def test_flatten_signals_keeps_int16_pcm():
     """api.flatten_signals (what every reference-shaped extractor feeds the device from): a list whose utterances are ALL int16 PCM stays
     int16 (ssp_mfcc_run_i16 widens on the device: half the PCIe bytes, no host pass); anything else becomes float32 as before."""
